@@ -4,12 +4,16 @@ ray-sample through the 16-level x 2^19 x F8 hash-grid encoder (forward), scatter
 (backward); at N>1 each rank does that for its own camera and the table gradient is all-reduced
 over RCCL.  Prints ONE JSON line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]         (N > 1: spawns N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (N > 1: spawns N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 metric: encoded ray-samples/s (BASELINE.json).  `value` counts every marched sample once per
 step and divides by the wall time of the WHOLE step (march + positions + encode fwd + encode bwd
-[+ all-reduce]); per-kernel rates are in `kernels`, the dominant kernel's roofline in `roofline`.
+[+ all-reduce]); per-kernel rates of the timed steps are in `kernels`.  A plain run does only that:
+set up, warm up, time K steps, print the line.  --full adds what runs outside the timed region: the
+dominant kernel's roofline (`roofline`, `roofline_forward`) and the probes it needs, the fused field,
+Input B, the whole-model training step (+ eval render, codec) and the CPU baselines.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see `dump_outputs`).
 """
 from __future__ import annotations
 
@@ -131,12 +135,13 @@ def probe_chunk_of(x):
     return x[mid:mid + min(CHUNK, S)]
 
 
-def step(w, timed, world):
-    """One pass of the hot path over one 800x800 frame.  Returns the number of ray-samples."""
+def step(w, timed, world, keep=None):
+    """One pass of the hot path over one 800x800 frame.  Returns the number of ray-samples; `keep` (a dict) receives
+    the frame's march results (for --dump-outputs)."""
     rays_o, rays_d = w["rays_o"], w["rays_d"]
     n_rays = rays_o.shape[0]
     t0 = time.perf_counter()
-    box = {}
+    box = keep if keep is not None else {}
     timed.launch("march(ray_aabb+count+cumsum+fill incl. positions)", n_rays, lambda: march_frame(w, box))
     ray_indices, t_starts, t_ends = box["s"][:3]
     S = t_starts.shape[0]
@@ -178,6 +183,56 @@ def finish_exchange(w, timed, world):
         work.wait()
         w["bucket"].flat.div_(world)
     timed.launch("allreduce(grad_table): wait + mean, after the next march", w["bucket"].flat.numel() * 4, join)
+
+
+DUMP_SAMPLES = 1 << 19         # marched samples kept by --dump-outputs (of ~68 M)
+DUMP_ENCODED = 1 << 15         # encoder output rows kept (of the last chunk's ~1 M)
+DUMP_GRAD_ROWS = 1 << 18       # table-gradient rows kept (of 6,120,776)
+
+
+def dump_outputs(w, box, out_dir):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files (~45 MB), so that two
+    builds can be compared output for output.  The full arrays are larger than that; fixed, seeded samples of them are
+    kept (the same positions from run to run as long as the sample count is the same; the positions are dumped too):
+      chunk_cnts [n_rays]            samples per ray (the march), complete
+      n_samples [1]                  total marched samples S
+      sample_index [K]               the sampled sample positions, sorted (rng seed 0)
+      ray_indices, t_starts, t_ends [K], positions [K, 3]   the march's outputs at those positions
+      encoding_index [E]             positions (in the frame) of the encoder-output rows kept, from the last chunk (seed 1)
+      encoding [L, E, F]             the last chunk's encoder forward output at those rows
+      grad_table_row_index [R]       table rows kept (seed 2), sorted
+      grad_table_rows [R, F]         the table gradient of the step (the mean over ranks at N > 1) at those rows
+      grad_table_sums [2, F]         float64 column sums of the whole gradient and of its absolute values
+      clip_count [1]                 the STE clip counter the step left"""
+    os.makedirs(out_dir, exist_ok=True)
+    ri, t_starts, t_ends, _, counts = box["s"][:5]
+    pos = box["ex"]["positions"]
+    S = t_starts.shape[0]
+    dev = t_starts.device
+    arrays = {"chunk_cnts": counts.to(torch.float32), "n_samples": torch.tensor([S], dtype=torch.float64)}
+    idx = np.sort(np.random.default_rng(0).integers(0, S, min(DUMP_SAMPLES, S)))
+    idx_d = torch.as_tensor(idx, device=dev)
+    arrays.update(sample_index=torch.as_tensor(idx, dtype=torch.float64), ray_indices=ri[idx_d].to(torch.float32),
+                  t_starts=t_starts[idx_d], t_ends=t_ends[idx_d], positions=pos[idx_d])
+    last = ((S - 1) // CHUNK) * CHUNK if S else 0           # the encoder output buffer holds the last chunk
+    n = S - last
+    if n:
+        o = w["out"][:, :n, :] if n == CHUNK else w["out"].view(-1)[: L * n * F].view(L, n, F)
+        e = np.sort(np.random.default_rng(1).integers(0, n, min(DUMP_ENCODED, n)))
+        arrays.update(encoding_index=torch.as_tensor(e + last, dtype=torch.float64),
+                      encoding=o[:, torch.as_tensor(e, device=dev), :])
+    gt = w["grad_table"]
+    rows = np.sort(np.random.default_rng(2).integers(0, gt.shape[0], min(DUMP_GRAD_ROWS, gt.shape[0])))
+    g64 = gt.to(torch.float64)
+    arrays.update(grad_table_row_index=torch.as_tensor(rows, dtype=torch.float64),
+                  grad_table_rows=gt[torch.as_tensor(rows, device=dev)],
+                  grad_table_sums=torch.stack([g64.sum(0), g64.abs().sum(0)]), clip_count=w["clip"].to(torch.float64))
+    del g64
+    host = {name: a.detach().cpu().numpy() for name, a in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in host.values())
+    assert sum(a.nbytes for a in host.values()) <= 64e6
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(w):
@@ -617,15 +672,198 @@ def trained_model_entries(tr, dev):
     return out
 
 
+def probe_extras(w, dev):
+    """--full, outside the timed region (rank 0): (i) the generic fp32-table gather (the `_gridencoder` drop-in entry
+    point, no bit plane); (ii) the backward call's two halves one after the other on ONE stream (coarse levels =
+    k_grid_encode_bwd_merge, finest levels = k_bwd_bin + k_bwd_owner), so each half has its own duration next to its own
+    bound in `roofline.parts`.  Returns their timings."""
+    extra = Timed()
+    n = CHUNK
+    xs = torch.rand((n, 3), device=dev)
+    for _ in range(5):
+        extra.launch("grid_encode_forward_fp32_table(uniform pts)", n, lambda: enc.grid_encode_forward(
+            xs, w["table"], w["offsets"], w["resolutions"], w["out"], n, D, F, L, 0, 128, 0.0, None, None, None,
+            ste_binary=True))
+    if w.get("probe_chunk") is not None and w["probe_chunk"].shape[0] == CHUNK:
+        # the forward as the product's field issues it: point-major rows straight into a 256-wide MLP input
+        # (out_ld / out_col, cnc_amd/field.py) instead of the [L, N, F] array of the drop-in entry
+        feat = torch.empty((CHUNK, 256), device=dev)
+        for it in range(7):
+            if it == 2:
+                torch.cuda.synchronize()
+                extra.pending = [p_ for p_ in extra.pending if not p_[0].startswith("grid_encode_forward(point-major")]
+            extra.launch("grid_encode_forward(point-major into a [N,256] MLP input)", CHUNK, lambda: enc.grid_encode_forward_bits(
+                w["probe_chunk"], w["bits"], w["offsets"], w["resolutions"], feat, CHUNK, D, F, L, 128, None, None, None,
+                out_ld=256, out_col=0))
+        del feat
+    ngrid.traverse_grids(w["rays_o"], w["rays_d"], w["binaries"], w["aabbs"], step_size=STEP_SIZE, cone_angle=0.0)
+    for _ in range(3):      # the `nerfacc.csrc` drop-in entry (intervals + samples, 27 B / sample), for the record
+        extra.launch("traverse_grids drop-in (ray_aabb+traverse x2+cumsum)", w["rays_o"].shape[0],
+                     lambda: ngrid.traverse_grids(w["rays_o"], w["rays_d"], w["binaries"], w["aabbs"],
+                                                  step_size=STEP_SIZE, cone_angle=0.0))
+    nb_plan = enc.plan_binned_levels(synthetic.RES_16L, w["offsets_host"], D, F, n)
+    if nb_plan is not None and w.get("probe_chunk") is not None and w["probe_chunk"].shape[0] == CHUNK:
+        xs_r, o_r = w["probe_chunk"], w["out"]
+        nr = xs_r.shape[0]
+        enc.grid_encode_forward_bits(xs_r, w["bits"], w["offsets"], w["resolutions"], o_r, nr, D, F, L, 128)
+        nb = nb_plan[0]
+        k = L - nb
+        gt = w["grad_table"]
+        for it in range(7):
+            if it == 2:               # two untimed rounds first (scratch allocation, caches)
+                torch.cuda.synchronize()
+                extra.pending = [p_ for p_ in extra.pending if not p_[0].startswith("bwd_")]
+            extra.launch("bwd_coarse_levels(k_grid_encode_bwd_merge), alone", nr, lambda: enc.grid_encode_backward(
+                o_r[:k], xs_r, w["table"], w["offsets"][:k + 1], w["resolutions"][:k], gt, nr, D, F, k, 0, 128,
+                None, None, None, None, ste_binary=True, ste_clip_count=w["clip"], binned=None,
+                interleave_levels=True))
+            extra.launch("bwd_finest_levels(k_bwd_bin+k_bwd_owner), alone", nr, lambda: enc.grid_encode_backward(
+                o_r[k:], xs_r, w["table"], w["offsets"][k:], w["resolutions"][k:], gt, nr, D, F, nb, 0, 128,
+                None, None, None, None, ste_binary=True, ste_clip_count=w["clip"], binned=(nb, nb_plan[1]),
+                overlap_streams=False))
+    torch.cuda.synchronize()
+    extra.collect()
+    return extra
+
+
+def roofline_blocks(w, timed, extra):
+    """--full: the dominant kernel of the timed steps against its bound (`roofline`), the forward beside it
+    (`roofline_forward`), from the timed steps' durations, the probes of `probe_extras` and the measured traffic of
+    profiles/traffic.json.  Returns (roofline, roofline_forward, the traffic table)."""
+    kb = timed.acc["grid_encode_backward"]
+    kf = timed.acc["grid_encode_forward"]
+    # dominant kernel = the one with the most accumulated time in the timed region
+    dom_name, bytes_per, k = (("grid_encode_backward", BYTES_BWD, kb) if kb[0] >= kf[0]
+                              else ("grid_encode_forward", BYTES_FWD, kf))
+    launch_s = k[0] / k[1]
+    algorithmic = bytes_per * k[2] / k[0]   # SURVEY §8(d) bytes / s, averaged over launches
+    # Measured HBM bytes per launch (PMC FETCH_SIZE/WRITE_SIZE, profiles/traffic.json).  The kernels move
+    # FEWER bytes than the algorithmic count (bit-plane gather, cells merged before the table is touched),
+    # so the algorithmic rate can exceed the HBM peak and is no fraction of anything; `frac` is the
+    # measured traffic over the measured duration against the HBM peak.
+    tj = {}
+    tp = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tp):
+        tj = json.load(open(tp))
+    # the byte counts are tied to the kernels they were measured on: a kernel source that changed since
+    # (git blob hash) marks them stale
+    measured_on = tj.get("_sources", {})
+    now = kernel_source_hashes()
+    stale = sorted(k for k in now if measured_on.get(k) != now[k]) if measured_on else ["(no source hashes in traffic.json)"]
+    req_peak = float(tj.get("_fabric_request_rate_peak_G_per_s", 50.0)) * 1e9
+
+    def entry_of(name):
+        e = tj.get(name)
+        return e if isinstance(e, dict) else None
+
+    def rates(e, dur):
+        """calibrated bytes / s, both bounds, and the L2 -> fabric request rate of one entry over `dur` seconds"""
+        if not e:
+            return {}
+        req = (e.get("read_requests") or 0) + (e.get("write_requests") or 0)
+        return {"traffic": e["bytes"], "achieved": e["bytes"] / dur / 1e9, "frac": e["bytes"] / dur / HBM_PEAK,
+                "traffic_bounds": [e["bytes_min(read requests x 64 B)"], e["bytes_max(read requests x 128 B)"]],
+                "frac_bounds": [e["bytes_min(read requests x 64 B)"] / dur / HBM_PEAK,
+                                e["bytes_max(read requests x 128 B)"] / dur / HBM_PEAK],
+                "fabric_requests": {"read": e.get("read_requests"), "write": e.get("write_requests"),
+                                    "achieved_G_per_s": req / dur / 1e9, "peak_G_per_s": req_peak / 1e9,
+                                    "frac": req / dur / req_peak},
+                # row atomics and plain requests are served by ONE memory-side unit in which an atomic takes the place
+                # of ~2.7 reads (tools/mix_probe.hip, profiles/r05_backward_closure.md): its busy time for this entry
+                "memory_side_unit": {"atomic_requests": e.get("atomic_requests") or 0.0, "atomic_peak_G_per_s": 21.0,
+                                     "plain_requests": req - (e.get("atomic_requests") or 0.0),
+                                     "plain_peak_G_per_s": [req_peak / 1e9, 57.0],
+                                     "busy_frac": [((e.get("atomic_requests") or 0.0) / 21.0e9
+                                                    + (req - (e.get("atomic_requests") or 0.0)) / pk) / dur
+                                                   for pk in (57.0e9, req_peak)]}}
+
+    dom = entry_of(dom_name)
+    rr = rates(dom, launch_s)
+    nb = (enc.plan_binned_levels(synthetic.RES_16L, w["offsets_host"], D, F, CHUNK) or (0, 0))[0]
+    desc = {"grid_encode_backward": f"one cnc_grid_encode_backward_overlapped call = k_grid_encode_bwd_merge ({L - nb} coarse "
+                                    f"levels, runs merged across rays, atomics) + k_bwd_bin + k_bwd_owner ({nb} finest levels, LDS "
+                                    "accumulation); avg_launch_ms is the whole call between two events on the "
+                                    "caller's stream (the library joins its side streams before returning)",
+            "grid_encode_forward": "k_grid_encode_fwd_bits"}
+    comp = None
+    if dom_name == "grid_encode_backward" and w.get("probe_chunk") is not None and w["probe_chunk"].shape[0] == CHUNK:
+        comp = compulsory_backward_bytes(w["probe_chunk"], w["offsets_host"])
+    roofline = {"kernel": dom_name, "kernel_parts": desc[dom_name], "bound": "hbm",
+                "achieved": rr.get("achieved"), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                "frac": rr.get("frac"), "traffic": rr.get("traffic"),
+                "frac_basis": "HBM bytes per launch from rocprofv3 --pmc passes (profiles/traffic.json), corrected per access "
+                              "class as calibrated in profiles/r03_counter_calibration.md — a streamed read request = 128 B "
+                              "(FETCH_SIZE tallies 64), a gathered 32-byte row = one 64-byte request, WRITE_SIZE as reported — "
+                              "over avg_launch_ms over 8 TB/s.  frac_bounds: every read request 64 B / 128 B.",
+                "frac_bounds": rr.get("frac_bounds"), "traffic_bounds": rr.get("traffic_bounds"),
+                "traffic_stale": bool(stale), "traffic_stale_sources": stale,
+                "fabric_requests": rr.get("fabric_requests"),
+                "memory_side_unit": rr.get("memory_side_unit"),
+                "fabric_requests_note": "the finest levels sit on the L2 -> fabric REQUEST rate, not on bytes: a gather of one "
+                                        "32-byte gradient row costs a whole request (tools/fetch_calib.hip: 51.5 G gathers/s "
+                                        "from 2 GiB, a 16 B/lane stream 46.9 G requests/s = 6.0 TB/s)",
+                "achieved_algorithmic": algorithmic / 1e9,
+                "algorithmic_over_peak": algorithmic / HBM_PEAK,
+                "traffic_over_algorithmic": None if not rr else rr["traffic"] / (bytes_per * k[2] / k[1]),
+                "compulsory_bytes": None if comp is None else comp["total"], "compulsory_parts": comp,
+                "traffic_over_compulsory": None if (comp is None or not rr) else rr["traffic"] / comp["total"],
+                "bytes_per_sample": bytes_per, "samples_per_launch": k[2] / k[1],
+                "avg_launch_ms": launch_s * 1e3}
+    # each half of the backward call against the bound it actually sits on
+    parts = {}
+    pc = extra.acc.get("bwd_coarse_levels(k_grid_encode_bwd_merge), alone")
+    pf = extra.acc.get("bwd_finest_levels(k_bwd_bin+k_bwd_owner), alone")
+    if pc:
+        dur = pc[0] / pc[1]
+        e = entry_of("k_grid_encode_bwd_merge")
+        req = None if not e else e.get("atomic_requests")
+        parts["k_grid_encode_bwd_merge"] = {
+            "avg_ms": dur * 1e3, "bound": "memory-side fp32 atomic requests (tools/atomic_probe.hip: 21 G requests/s)",
+            "note": "since the cells are merged across rays the kernel is vector-issue-bound, not request-bound: without "
+                    "its atomics it runs 10 % faster, without the MFMA accumulation 35 % (docs/engineering_log.md §4.2b, second pass)",
+            "atomic_requests_per_launch": req, "achieved_G_requests_per_s": None if not req else req / dur / 1e9,
+            "peak_G_requests_per_s": 21.0, "frac": None if not req else req / dur / 21e9}
+        parts["k_grid_encode_bwd_merge"].update({"hbm_" + k_: v for k_, v in rates(e, dur).items() if k_ in ("traffic", "frac")})
+    if pf:
+        dur = pf[0] / pf[1]
+        e = entry_of("k_bwd_bin+k_bwd_owner")
+        parts["k_bwd_bin+k_bwd_owner"] = dict({"avg_ms": dur * 1e3, "bound": "L2 -> fabric request rate (gathers); hbm bytes beside it",
+                                               "peak_GBps": HBM_PEAK / 1e9}, **rates(e, dur))
+    roofline["parts"] = parts
+    ef = entry_of("grid_encode_forward")
+    fl = kf[0] / kf[1]
+    other = dict({"kernel": "grid_encode_forward", "bound": "L2->L1 line rate of the byte gathers (docs/engineering_log.md §4.3); HBM only for "
+                                                           "the 512 B/sample output stream", "unit": "GB/s",
+                  "achieved_algorithmic": BYTES_FWD * kf[2] / kf[0] / 1e9, "bytes_per_sample": BYTES_FWD,
+                  "avg_launch_ms": fl * 1e3}, **rates(ef, fl))
+    pm = extra.acc.get("grid_encode_forward(point-major into a [N,256] MLP input)")
+    if pm:
+        other["point_major_variant"] = {
+            "avg_launch_ms": pm[0] / pm[1] * 1e3, "samples_per_s": pm[2] / pm[0],
+            "note": "the same gather writing point-major rows into a [N, 256] feature matrix (out_ld=256), the form the "
+                    "product's field uses (no [L,N,F] array, no permute / cat afterwards); the 512 B/sample still have to "
+                    "reach HBM once — only a gather fused into the MLP kernel would remove them",
+            "output_bytes_per_sample": L * F * 4}
+    return roofline, other, tj
+
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)      # the backward keeps getting faster for ~8 steps (786 vs 732 M/s at 6 vs 2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train-step", action="store_true")
-    ap.add_argument("--no-field", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure outside the timed region: roofline and its probes, field, Input B, training step "
+                         "(+ eval render, codec), CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: leave out the training step")
+    ap.add_argument("--no-field", action="store_true", help="with --full: leave out the field and Input B blocks")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     world = int(os.environ.get("WORLD_SIZE", str(args.gpus) if args.gpus > 1 else "1"))
     if world != args.gpus:
@@ -667,6 +905,7 @@ def main():
     else:
         ranks = [{"rank": 0, "device": str(dev), "world_size": 1, "backend": backend}]
 
+    # also in a plain run: the timed frames then run on the same hardware-queue layout with or without --full
     if not args.no_train_step:
         reserve_training_streams(dev)
     w = build_workload(dev, rank)
@@ -685,64 +924,18 @@ def main():
     timed.pending, timed.acc = [], {}
     t0 = time.perf_counter()
     samples = 0
-    for _ in range(args.steps):
-        samples += step(w, timed, world)
+    last = {}
+    for i in range(args.steps):
+        samples += step(w, timed, world, keep=last if args.dump_outputs and i == args.steps - 1 else None)
     finish_exchange(w, timed, world)          # the last frame's exchange ends inside the timed region
     barrier()
     elapsed = time.perf_counter() - t0
     timed.collect()
+    if args.dump_outputs and rank == 0:       # before the --full probes, which reuse the encoder's buffers
+        dump_outputs(w, last, args.dump_outputs)
+    del last
 
-    # outside the timed region (rank 0): (i) the generic fp32-table gather (the `_gridencoder` drop-in
-    # entry point, no bit plane); (ii) the backward call's two halves one after the other on ONE stream
-    # (coarse levels = k_grid_encode_bwd_merge, finest levels = k_bwd_bin + k_bwd_owner), so each half
-    # has its own duration next to its own bound in `roofline.parts`
-    extra = Timed()
-    if rank == 0:
-        n = CHUNK
-        xs = torch.rand((n, 3), device=dev)
-        for _ in range(5):
-            extra.launch("grid_encode_forward_fp32_table(uniform pts)", n, lambda: enc.grid_encode_forward(
-                xs, w["table"], w["offsets"], w["resolutions"], w["out"], n, D, F, L, 0, 128, 0.0, None, None, None,
-                ste_binary=True))
-        if w.get("probe_chunk") is not None and w["probe_chunk"].shape[0] == CHUNK:
-            # the forward as the product's field issues it: point-major rows straight into a 256-wide MLP input
-            # (out_ld / out_col, cnc_amd/field.py) instead of the [L, N, F] array of the drop-in entry
-            feat = torch.empty((CHUNK, 256), device=dev)
-            for it in range(7):
-                if it == 2:
-                    torch.cuda.synchronize()
-                    extra.pending = [p_ for p_ in extra.pending if not p_[0].startswith("grid_encode_forward(point-major")]
-                extra.launch("grid_encode_forward(point-major into a [N,256] MLP input)", CHUNK, lambda: enc.grid_encode_forward_bits(
-                    w["probe_chunk"], w["bits"], w["offsets"], w["resolutions"], feat, CHUNK, D, F, L, 128, None, None, None,
-                    out_ld=256, out_col=0))
-            del feat
-        ngrid.traverse_grids(w["rays_o"], w["rays_d"], w["binaries"], w["aabbs"], step_size=STEP_SIZE, cone_angle=0.0)
-        for _ in range(3):      # the `nerfacc.csrc` drop-in entry (intervals + samples, 27 B / sample), for the record
-            extra.launch("traverse_grids drop-in (ray_aabb+traverse x2+cumsum)", w["rays_o"].shape[0],
-                         lambda: ngrid.traverse_grids(w["rays_o"], w["rays_d"], w["binaries"], w["aabbs"],
-                                                      step_size=STEP_SIZE, cone_angle=0.0))
-        nb_plan = enc.plan_binned_levels(synthetic.RES_16L, w["offsets_host"], D, F, n)
-        if nb_plan is not None and w.get("probe_chunk") is not None and w["probe_chunk"].shape[0] == CHUNK:
-            xs_r, o_r = w["probe_chunk"], w["out"]
-            nr = xs_r.shape[0]
-            enc.grid_encode_forward_bits(xs_r, w["bits"], w["offsets"], w["resolutions"], o_r, nr, D, F, L, 128)
-            nb = nb_plan[0]
-            k = L - nb
-            gt = w["grad_table"]
-            for it in range(7):
-                if it == 2:               # two untimed rounds first (scratch allocation, caches)
-                    torch.cuda.synchronize()
-                    extra.pending = [p_ for p_ in extra.pending if not p_[0].startswith("bwd_")]
-                extra.launch("bwd_coarse_levels(k_grid_encode_bwd_merge), alone", nr, lambda: enc.grid_encode_backward(
-                    o_r[:k], xs_r, w["table"], w["offsets"][:k + 1], w["resolutions"][:k], gt, nr, D, F, k, 0, 128,
-                    None, None, None, None, ste_binary=True, ste_clip_count=w["clip"], binned=None,
-                    interleave_levels=True))
-                extra.launch("bwd_finest_levels(k_bwd_bin+k_bwd_owner), alone", nr, lambda: enc.grid_encode_backward(
-                    o_r[k:], xs_r, w["table"], w["offsets"][k:], w["resolutions"][k:], gt, nr, D, F, nb, 0, 128,
-                    None, None, None, None, ste_binary=True, ste_clip_count=w["clip"], binned=(nb, nb_plan[1]),
-                    overlap_streams=False))
-        torch.cuda.synchronize()
-        extra.collect()
+    extra = probe_extras(w, dev) if args.full and rank == 0 else Timed()
 
     tot = torch.tensor([float(samples), elapsed], dtype=torch.float64, device=dev)
     if exchange_on:
@@ -757,7 +950,7 @@ def main():
     # the DP training step (configs[3]) runs on EVERY rank; rank 0 reports the aggregate.  It comes after the
     # headline numbers are in and must not take the line down with it.
     ts_multi = None
-    if world > 1 and not args.no_train_step:
+    if args.full and world > 1 and not args.no_train_step:
         ts_multi = guarded_train_step(dev, world, rank)
 
     if rank == 0:
@@ -768,120 +961,6 @@ def main():
         for name, (secs, launches, units) in extra.acc.items():
             kernels[name] = {"launches": launches, "avg_ms": secs / launches * 1e3,
                              "units_per_s": units / secs, "timed_region": False}
-        kb = timed.acc["grid_encode_backward"]
-        kf = timed.acc["grid_encode_forward"]
-        # dominant kernel = the one with the most accumulated time in the timed region
-        dom_name, bytes_per, k = (("grid_encode_backward", BYTES_BWD, kb) if kb[0] >= kf[0]
-                                  else ("grid_encode_forward", BYTES_FWD, kf))
-        launch_s = k[0] / k[1]
-        algorithmic = bytes_per * k[2] / k[0]   # SURVEY §8(d) bytes / s, averaged over launches
-        # Measured HBM bytes per launch (PMC FETCH_SIZE/WRITE_SIZE, profiles/traffic.json).  The kernels move
-        # FEWER bytes than the algorithmic count (bit-plane gather, cells merged before the table is touched),
-        # so the algorithmic rate can exceed the HBM peak and is no fraction of anything; `frac` is the
-        # measured traffic over the measured duration against the HBM peak.
-        tj = {}
-        tp = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tp):
-            tj = json.load(open(tp))
-        # the byte counts are tied to the kernels they were measured on: a kernel source that changed since
-        # (git blob hash) marks them stale
-        measured_on = tj.get("_sources", {})
-        now = kernel_source_hashes()
-        stale = sorted(k for k in now if measured_on.get(k) != now[k]) if measured_on else ["(no source hashes in traffic.json)"]
-        req_peak = float(tj.get("_fabric_request_rate_peak_G_per_s", 50.0)) * 1e9
-
-        def entry_of(name):
-            e = tj.get(name)
-            return e if isinstance(e, dict) else None
-
-        def rates(e, dur):
-            """calibrated bytes / s, both bounds, and the L2 -> fabric request rate of one entry over `dur` seconds"""
-            if not e:
-                return {}
-            req = (e.get("read_requests") or 0) + (e.get("write_requests") or 0)
-            return {"traffic": e["bytes"], "achieved": e["bytes"] / dur / 1e9, "frac": e["bytes"] / dur / HBM_PEAK,
-                    "traffic_bounds": [e["bytes_min(read requests x 64 B)"], e["bytes_max(read requests x 128 B)"]],
-                    "frac_bounds": [e["bytes_min(read requests x 64 B)"] / dur / HBM_PEAK,
-                                    e["bytes_max(read requests x 128 B)"] / dur / HBM_PEAK],
-                    "fabric_requests": {"read": e.get("read_requests"), "write": e.get("write_requests"),
-                                        "achieved_G_per_s": req / dur / 1e9, "peak_G_per_s": req_peak / 1e9,
-                                        "frac": req / dur / req_peak},
-                    # row atomics and plain requests are served by ONE memory-side unit in which an atomic takes the place
-                    # of ~2.7 reads (tools/mix_probe.hip, profiles/r05_backward_closure.md): its busy time for this entry
-                    "memory_side_unit": {"atomic_requests": e.get("atomic_requests") or 0.0, "atomic_peak_G_per_s": 21.0,
-                                         "plain_requests": req - (e.get("atomic_requests") or 0.0),
-                                         "plain_peak_G_per_s": [req_peak / 1e9, 57.0],
-                                         "busy_frac": [((e.get("atomic_requests") or 0.0) / 21.0e9
-                                                        + (req - (e.get("atomic_requests") or 0.0)) / pk) / dur
-                                                       for pk in (57.0e9, req_peak)]}}
-
-        dom = entry_of(dom_name)
-        rr = rates(dom, launch_s)
-        nb = (enc.plan_binned_levels(synthetic.RES_16L, w["offsets_host"], D, F, CHUNK) or (0, 0))[0]
-        desc = {"grid_encode_backward": f"one cnc_grid_encode_backward_overlapped call = k_grid_encode_bwd_merge ({L - nb} coarse "
-                                        f"levels, runs merged across rays, atomics) + k_bwd_bin + k_bwd_owner ({nb} finest levels, LDS "
-                                        "accumulation); avg_launch_ms is the whole call between two events on the "
-                                        "caller's stream (the library joins its side streams before returning)",
-                "grid_encode_forward": "k_grid_encode_fwd_bits"}
-        comp = None
-        if dom_name == "grid_encode_backward" and w.get("probe_chunk") is not None and w["probe_chunk"].shape[0] == CHUNK:
-            comp = compulsory_backward_bytes(w["probe_chunk"], w["offsets_host"])
-        roofline = {"kernel": dom_name, "kernel_parts": desc[dom_name], "bound": "hbm",
-                    "achieved": rr.get("achieved"), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                    "frac": rr.get("frac"), "traffic": rr.get("traffic"),
-                    "frac_basis": "HBM bytes per launch from rocprofv3 --pmc passes (profiles/traffic.json), corrected per access "
-                                  "class as calibrated in profiles/r03_counter_calibration.md — a streamed read request = 128 B "
-                                  "(FETCH_SIZE tallies 64), a gathered 32-byte row = one 64-byte request, WRITE_SIZE as reported — "
-                                  "over avg_launch_ms over 8 TB/s.  frac_bounds: every read request 64 B / 128 B.",
-                    "frac_bounds": rr.get("frac_bounds"), "traffic_bounds": rr.get("traffic_bounds"),
-                    "traffic_stale": bool(stale), "traffic_stale_sources": stale,
-                    "fabric_requests": rr.get("fabric_requests"),
-                    "memory_side_unit": rr.get("memory_side_unit"),
-                    "fabric_requests_note": "the finest levels sit on the L2 -> fabric REQUEST rate, not on bytes: a gather of one "
-                                            "32-byte gradient row costs a whole request (tools/fetch_calib.hip: 51.5 G gathers/s "
-                                            "from 2 GiB, a 16 B/lane stream 46.9 G requests/s = 6.0 TB/s)",
-                    "achieved_algorithmic": algorithmic / 1e9,
-                    "algorithmic_over_peak": algorithmic / HBM_PEAK,
-                    "traffic_over_algorithmic": None if not rr else rr["traffic"] / (bytes_per * k[2] / k[1]),
-                    "compulsory_bytes": None if comp is None else comp["total"], "compulsory_parts": comp,
-                    "traffic_over_compulsory": None if (comp is None or not rr) else rr["traffic"] / comp["total"],
-                    "bytes_per_sample": bytes_per, "samples_per_launch": k[2] / k[1],
-                    "avg_launch_ms": launch_s * 1e3}
-        # each half of the backward call against the bound it actually sits on
-        parts = {}
-        pc = extra.acc.get("bwd_coarse_levels(k_grid_encode_bwd_merge), alone")
-        pf = extra.acc.get("bwd_finest_levels(k_bwd_bin+k_bwd_owner), alone")
-        if pc:
-            dur = pc[0] / pc[1]
-            e = entry_of("k_grid_encode_bwd_merge")
-            req = None if not e else e.get("atomic_requests")
-            parts["k_grid_encode_bwd_merge"] = {
-                "avg_ms": dur * 1e3, "bound": "memory-side fp32 atomic requests (tools/atomic_probe.hip: 21 G requests/s)",
-                "note": "since the cells are merged across rays the kernel is vector-issue-bound, not request-bound: without "
-                        "its atomics it runs 10 % faster, without the MFMA accumulation 35 % (docs/engineering_log.md §4.2b, second pass)",
-                "atomic_requests_per_launch": req, "achieved_G_requests_per_s": None if not req else req / dur / 1e9,
-                "peak_G_requests_per_s": 21.0, "frac": None if not req else req / dur / 21e9}
-            parts["k_grid_encode_bwd_merge"].update({"hbm_" + k_: v for k_, v in rates(e, dur).items() if k_ in ("traffic", "frac")})
-        if pf:
-            dur = pf[0] / pf[1]
-            e = entry_of("k_bwd_bin+k_bwd_owner")
-            parts["k_bwd_bin+k_bwd_owner"] = dict({"avg_ms": dur * 1e3, "bound": "L2 -> fabric request rate (gathers); hbm bytes beside it",
-                                                   "peak_GBps": HBM_PEAK / 1e9}, **rates(e, dur))
-        roofline["parts"] = parts
-        ef = entry_of("grid_encode_forward")
-        fl = kf[0] / kf[1]
-        other = dict({"kernel": "grid_encode_forward", "bound": "L2->L1 line rate of the byte gathers (docs/engineering_log.md §4.3); HBM only for "
-                                                               "the 512 B/sample output stream", "unit": "GB/s",
-                      "achieved_algorithmic": BYTES_FWD * kf[2] / kf[0] / 1e9, "bytes_per_sample": BYTES_FWD,
-                      "avg_launch_ms": fl * 1e3}, **rates(ef, fl))
-        pm = extra.acc.get("grid_encode_forward(point-major into a [N,256] MLP input)")
-        if pm:
-            other["point_major_variant"] = {
-                "avg_launch_ms": pm[0] / pm[1] * 1e3, "samples_per_s": pm[2] / pm[0],
-                "note": "the same gather writing point-major rows into a [N, 256] feature matrix (out_ld=256), the form the "
-                        "product's field uses (no [L,N,F] array, no permute / cat afterwards); the 512 B/sample still have to "
-                        "reach HBM once — only a gather fused into the MLP kernel would remove them",
-                "output_bytes_per_sample": L * F * 4}
         out = {
             "metric": "ray-samples/s/GPU (16Lx2^19xF8 grid)", "value": samples_all / elapsed_max,
             "unit": "ray-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -893,10 +972,12 @@ def main():
                                    + (", grad table all-reduced (RCCL)" if world > 1 else ""),
                        "rays_per_gpu": 640000, "samples_per_step_rank0": samples // args.steps,
                        "chunk": CHUNK, "table_rows": 6120776, "n_features": F, "levels": L},
-            "ranks": ranks,
-            "roofline": roofline, "roofline_forward": other, "kernels": kernels,
+            "ranks": ranks, "kernels": kernels,
         }
-        if not args.no_field:
+        tj = {}
+        if args.full:
+            out["roofline"], out["roofline_forward"], tj = roofline_blocks(w, timed, extra)
+        if args.full and not args.no_field:
             try:
                 fe = field_entries(dev)
                 out["field"] = {k: fe.pop(k) for k in ("field_note", "field_density_speedup", "field_rgb_speedup")}
@@ -905,7 +986,7 @@ def main():
                 import traceback
                 print(f"[bench rank {rank}] field entries failed:\n{traceback.format_exc()}", file=sys.stderr, flush=True)
                 out["field"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not args.no_field and w.get("probe_chunk") is not None:
+        if args.full and not args.no_field and w.get("probe_chunk") is not None:
             try:
                 kb_, rb_ = input_B_entries(dev, w["probe_chunk"], tj)
                 kernels.update(kb_)
@@ -914,7 +995,7 @@ def main():
                 import traceback
                 print(f"[bench rank {rank}] input B failed:\n{traceback.format_exc()}", file=sys.stderr, flush=True)
                 out["roofline_input_B"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not args.no_train_step:
+        if args.full and not args.no_train_step:
             ts = guarded_train_step(dev) if world == 1 else ts_multi
             if isinstance(ts, dict) and "extras" in ts:
                 out.update(ts.pop("extras"))
@@ -923,7 +1004,7 @@ def main():
                 kernels["train_step(full model: march+field+render+context+adam)"] = {
                     "launches": ts["steps"], "avg_ms": ts["ms_per_step"], "units_per_s": ts["rendered_samples_per_s"],
                     "timed_region": False}
-        if not args.no_cpu_baseline and world == 1:   # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported on rank 0 at N=1 only
             out["cpu_baseline"], out["cpu_baseline_torch"] = cpu_baseline(w)
         print(json.dumps(out), flush=True)
     if exchange_on:

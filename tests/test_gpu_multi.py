@@ -50,7 +50,7 @@ def test_bench_reports_the_data_parallel_training_step(cuda):
     all-reduced while the context backward runs): aggregate samples / s, the all-reduce alone and what of it the
     step still waits for."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=1500,
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=1500,
                        env=_clean_env(CNC_BENCH_ONE_DEVICE="1", CNC_BENCH_BACKEND="gloo", CNC_BENCH_TRAIN_WARM="20",
                                       CNC_BENCH_TRAIN_STEPS="6"))
     assert r.returncode == 0, r.stderr[-3000:]

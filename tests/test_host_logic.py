@@ -354,6 +354,17 @@ def test_bench_refuses_a_world_that_contradicts_gpus():
         assert r.returncode != 0 and "needs an MI355X" in r.stderr
 
 
+def test_bench_options_for_the_full_run_and_the_output_dump():
+    """`--full` (everything outside the timed region) and `--dump-outputs DIR` are offered; a dump without a timed step
+    to take it from is refused before any work."""
+    import os, subprocess, sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    r = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    r = subprocess.run([sys.executable, bench, "--steps", "0", "--dump-outputs", "unused"], capture_output=True, text=True)
+    assert r.returncode != 0 and "at least one timed step" in r.stderr
+
+
 def test_per_rank_sampling_streams_of_the_real_scene_loaders(tmp_path):
     """Data parallelism: `LoaderDataset.seed_sampling(seed + 1000 * rank)` gives every rank its own stream of images /
     pixels / backgrounds (without it all ranks would draw the same batch from the identically seeded global

@@ -13,9 +13,9 @@ rm -rf $OUT
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 WHAT=${2:-all}
-timeout 1200 python $ROOT/bench.py > $OUT/bench.json 2> $OUT/bench.err
-CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train-step"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $ROOT/bench.py --no-cpu-baseline --no-train-step > $OUT/stats.json 2> $OUT/stats.log
+timeout 1200 python $ROOT/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+CMD="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train-step"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $ROOT/bench.py --full --no-cpu-baseline --no-train-step > $OUT/stats.json 2> $OUT/stats.log
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o p -- $CMD > $OUT/pmc_fetch.log 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o p -- $CMD > $OUT/pmc_write.log 2>&1
 timeout 900 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --output-format csv -d $OUT/pmc_req -o p -- $CMD > $OUT/pmc_req.log 2>&1
@@ -27,7 +27,7 @@ timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_b_write -
 timeout 600 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --output-format csv -d $OUT/pmc_b_req -o p -- $CMDB > $OUT/pmc_b_req.log 2>&1
 timeout 600 rocprofv3 --pmc TCC_ATOMIC_sum --output-format csv -d $OUT/pmc_b_atomic -o p -- $CMDB > $OUT/pmc_b_atomic.log 2>&1
 timeout 600 python $ROOT/tools/bench_input_b.py > $OUT/input_b.log 2>&1
-CNC_BWD_OVERLAP=0 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_no_overlap -o bench -- python $ROOT/bench.py --no-cpu-baseline --no-train-step > $OUT/bench_no_overlap.json 2> $OUT/stats_no_overlap.log
+CNC_BWD_OVERLAP=0 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_no_overlap -o bench -- python $ROOT/bench.py --full --no-cpu-baseline --no-train-step > $OUT/bench_no_overlap.json 2> $OUT/stats_no_overlap.log
 if [ "$WHAT" = "all" ]; then
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_train -o train -- python $ROOT/tools/bench_train.py --no-profile > $OUT/train.log 2>&1
   bash $ROOT/tools/collect_calib.sh > $OUT/calib.log 2>&1

@@ -154,7 +154,7 @@ traffic = {
     "_sources": {p: blob_hash(os.path.join(ROOT, p)) for p in KERNEL_SOURCES if os.path.exists(os.path.join(ROOT, p))},
     "_fabric_request_rate_peak_G_per_s": 50.0,
     "_samples_per_call": N_CHUNK,
-    "_note": "per encoder call of the bench frame (_samples_per_call samples on average); separate rocprofv3 --pmc passes of `python bench.py --steps 2 "
+    "_note": "per encoder call of the bench frame (_samples_per_call samples on average); separate rocprofv3 --pmc passes of `python bench.py --full --steps 2 "
              "--warmup 1 --no-cpu-baseline --no-train-step` (tools/collect_profiles.sh, profiles/" + TAG + "_pmc_hbm_traffic.csv); counter "
              "arithmetic per profiles/r03_counter_calibration.md: FETCH_SIZE = read requests x 64 B, a streamed request carries 128 B, a "
              "gathered 32-byte row is one request; the fabric sustains ~50 G requests/s (streaming 46.9, gathers 51.5: "
