@@ -50,6 +50,14 @@ __device__ __forceinline__ void store_vec_nt(float* __restrict__ p, const float 
     }
 }
 
+// The merging backward kernels (k_grid_encode_bwd, k_grid_encode_bwd_merge, k_grid_encode_bwd_cells) key a cell by its
+// integer coordinates, 16 bits per axis, and rebuild corner rows (coordinate + 1) or probe x-neighbours (key +- 1) from
+// those fields.  Cell coordinates reach R - 2 and their +1 neighbours R - 1, so the key holds a level exactly when
+// R <= kCellKeyMaxRes.  A point on a finer level joins no run or cell and is scattered on its own, one atomic per valid
+// corner and feature (scatter_point): inside the run and the cell kernels, by k_grid_encode_bwd_wide after the merge
+// kernel (whose own code measured 2 % slower on the bench with the branch in it).
+constexpr uint32_t kCellKeyMaxRes = 1u << 16;
+
 // Corner set-up for one (point, level): weights, validity and row indices.
 // Mirrors gridencoder.cu:166-291 (forward) / :443-562 (backward).
 template <uint32_t D, bool VXL>
@@ -157,6 +165,37 @@ struct Corners {
         wn_re = 1.0f / wn;         // == (float)(1.0 / (double)wn)
     }
 };
+
+// One point's gradient row g[0 .. F) scattered to the table rows of its valid corners (bit i of `valid`): the path of
+// the points the merging kernels cannot key (kCellKeyMaxRes).  The STE mask (|param| <= 1) when mask_on.  Weights and
+// rows are rebuilt corner by corner from the cell and the fractions with the arithmetic of Corners::setup and grid_row
+// (the same values), in a loop that is not unrolled: the path is cold, and it stays small next to the kernels' own code.
+// `g` indexes like an array: the lane's registers or its LDS row.
+template <uint32_t D, uint32_t F, typename G>
+__device__ __forceinline__ void scatter_point(const uint32_t (&cell)[D], const float (&frac)[D], uint32_t valid,
+                                              float wn_re, uint32_t off, uint32_t hs, uint32_t R, const G& g,
+                                              const float* __restrict__ emb, float* __restrict__ grad_emb, bool mask_on)
+{
+#pragma unroll 1
+    for (uint32_t i = 0; i < (1u << D); i++) {
+        if (!((valid >> i) & 1u)) continue;
+        float    w = 1;
+        uint32_t q[D];
+#pragma unroll
+        for (uint32_t d = 0; d < D; d++) {
+            const bool bit = (i >> d) & 1u;
+            w *= bit ? frac[d] : 1 - frac[d];
+            q[d] = bit ? min(cell[d] + 1, R - 1) : cell[d];
+        }
+        const float  tw = w * wn_re;
+        const size_t at = (size_t)(off + grid_row<D>(q, hs, R)) * F;
+#pragma unroll
+        for (uint32_t k = 0; k < F; k++) {
+            if (mask_on && !(emb[at + k] >= -1.0f && emb[at + k] <= 1.0f)) continue;
+            unsafeAtomicAdd(grad_emb + at + k, tw * g[k]);
+        }
+    }
+}
 
 // F sign bits of one table row from the bit plane cnc_pack_sign_bits writes (bit k of row r = table[r][k] >= 0)
 template <uint32_t F>

@@ -379,37 +379,62 @@ __global__ __launch_bounds__(256) void k_grid_encode_bwd(
             const uint32_t R = (uint32_t)resolutions[level];
             Corners<D, VXL> c;
             c.setup(x, R, hs, Rb, vxl, sat, vertex_plane(lay, level));
-            uint64_t cell = 0;   // integer cell coordinates, 16 bits per axis (R <= 65535)
+            if (R > kCellKeyMaxRes) {
+                // a level whose cell coordinates the key's 16-bit fields cannot hold (block-uniform unless levels are
+                // per point): this point's corners go out as atomics here, and it joins no run (key stays ~0)
+                float g[F];
+                bool  nonzero = false;
 #pragma unroll
-            for (uint32_t d = D; d-- > 0;) {
-                float p = x[d] * (float)(R - 2);
-                p = p + 0.5f;
-                cell = (cell << 16) | (uint32_t)floorf(p);
-            }
-            key = ((uint64_t)level << 52) | cell;
+                for (uint32_t k = 0; k < F; k += V) {
+                    float gv[V];
+                    load_vec<V>(grad + feat_index(lay, slot, N, b, F) + k, gv);
 #pragma unroll
-            for (uint32_t i = 0; i < C; i++) {
-                s_tw[tid][i] = c.valid[i] ? c.w[i] * c.wn_re : 0.0f;
-                if constexpr (!kRowsFromKey) s_row[tid][i] = off + c.row[i];
-                validmask |= (c.valid[i] ? 1u : 0u) << i;
-            }
-            const float* gp = grad + feat_index(lay, slot, N, b, F);
-            bool         nonzero = false;
-#pragma unroll
-            for (uint32_t k = 0; k < F; k += V) {
-                float gv[V];
-                load_vec<V>(gp + k, gv);
-#pragma unroll
-                for (uint32_t j = 0; j < V; j++) {
-                    s_g[tid][k + j] = gv[j];
-                    nonzero |= gv[j] != 0.0f;
+                    for (uint32_t j = 0; j < V; j++) {
+                        g[k + j] = gv[j];
+                        nonzero |= gv[j] != 0.0f;
+                    }
                 }
-            }
-            // a point whose gradient row is all zeros adds nothing: no atomics for it (samples behind an opaque surface;
-            // the levels outside a vertex's context window when several windows share one call, context.py _plane_bits)
-            if (!nonzero) {
-                key = ~0ull;
-                validmask = 0;
+                uint32_t valid = 0;
+#pragma unroll
+                for (uint32_t i = 0; i < C; i++) valid |= (c.valid[i] ? 1u : 0u) << i;
+                // (a zero gradient row adds nothing: no atomics for it, as below)
+                if (nonzero) scatter_point<D, F>(c.cell, c.frac, valid, c.wn_re, off, hs, R, g, emb, grad_emb, mask_on);
+            } else {
+                // integer cell coordinates, 16 bits per axis: exact for R <= kCellKeyMaxRes, where phase B's row_of
+                // rebuilds rows from these fields
+                uint64_t cell = 0;
+#pragma unroll
+                for (uint32_t d = D; d-- > 0;) {
+                    float p = x[d] * (float)(R - 2);
+                    p = p + 0.5f;
+                    cell = (cell << 16) | (uint32_t)floorf(p);
+                }
+                key = ((uint64_t)level << 52) | cell;
+#pragma unroll
+                for (uint32_t i = 0; i < C; i++) {
+                    s_tw[tid][i] = c.valid[i] ? c.w[i] * c.wn_re : 0.0f;
+                    if constexpr (!kRowsFromKey) s_row[tid][i] = off + c.row[i];
+                    validmask |= (c.valid[i] ? 1u : 0u) << i;
+                }
+                const float* gp = grad + feat_index(lay, slot, N, b, F);
+                bool         nonzero = false;
+#pragma unroll
+                for (uint32_t k = 0; k < F; k += V) {
+                    float gv[V];
+                    load_vec<V>(gp + k, gv);
+#pragma unroll
+                    for (uint32_t j = 0; j < V; j++) {
+                        s_g[tid][k + j] = gv[j];
+                        nonzero |= gv[j] != 0.0f;
+                    }
+                }
+                // a point whose gradient row is all zeros adds nothing: no atomics for it (samples behind an opaque
+                // surface; the levels outside a vertex's context window when several windows share one call,
+                // context.py _plane_bits)
+                if (!nonzero) {
+                    key = ~0ull;
+                    validmask = 0;
+                }
             }
         }
         s_key[tid] = key;

@@ -104,18 +104,11 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_cells(const CellsArgs a)
             for (uint32_t i = 0; i < C; i++) validmask |= (c.valid[i] ? 1u : 0u) << i;
             // a zero gradient row adds nothing (the levels outside a vertex's context window when several windows share
             // one call); neither does a point none of whose corners is valid
-            if (nonzero && validmask != 0 && level >= kLv) {
-                // a level the key cannot name (never the case for the encoders CNC builds: 12 to 16 levels): this
-                // point's corners go out one by one
-#pragma unroll
-                for (uint32_t i = 0; i < C; i++) {
-                    if (!c.valid[i]) continue;
-                    const size_t at = (size_t)(off + c.row[i]) * F;
-                    for (uint32_t k = 0; k < F; k++) {
-                        if (mask_on && !(j.emb[at + k] >= -1.0f && j.emb[at + k] <= 1.0f)) continue;
-                        unsafeAtomicAdd(j.grad_emb + at + k, (c.w[i] * c.wn_re) * g[k]);
-                    }
-                }
+            if (nonzero && validmask != 0 && (level >= kLv || R > kCellKeyMaxRes)) {
+                // a level the key cannot name (never the case for the encoders CNC builds: 12 to 16 levels), or whose
+                // cell coordinates do not fit its 16-bit fields (encoder_common.hpp): this point's corners go out one
+                // by one
+                scatter_point<D, F>(c.cell, c.frac, validmask, c.wn_re, off, hs, R, g, j.emb, j.grad_emb, mask_on);
             } else if (nonzero && validmask != 0) {
                 key = (uint64_t)level << 48 | (uint64_t)c.cell[0] | (uint64_t)c.cell[1] << 16;
                 if constexpr (D == 3) key |= (uint64_t)c.cell[2] << 32;
@@ -369,7 +362,8 @@ static void launch_cells_flags(const CellsArgs& a, bool ste, hipStream_t s)
     else launch_cells_t<D, F, false, false>(a, s);
 }
 
-// D in {2, 3}, F in {2, 4, 8}, resolutions below 2^16; false = not built for this shape (the caller keeps its own kernel)
+// D in {2, 3}, F in {2, 4, 8} (any resolution: points on levels above kCellKeyMaxRes are scattered one by one); false =
+// not built for this shape (the caller keeps its own kernel)
 bool launch_bwd_cells(const CellsArgs& a, uint32_t D, uint32_t F, bool ste, hipStream_t s)
 {
     if ((uint64_t)div_up(a.N, 512u) * a.L >= (1ull << 31)) return false;

@@ -22,7 +22,8 @@
 //
 // D = 3, F = 8 (one cell per wave at a time: 64 lanes = 8 corners x 8 features), no occupancy mask, no
 // per-point level window: the coarse half of a binned backward call.  Everything else stays on
-// k_grid_encode_bwd.
+// k_grid_encode_bwd.  The cell key holds 16 bits per axis: the samples of a level of R > kCellKeyMaxRes
+// (encoder_common.hpp) are left to k_grid_encode_bwd_wide, which scatters them one by one.
 #include <cstdlib>
 
 #include "common.hpp"
@@ -84,6 +85,7 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
             Corners<D, false> c;
             c.setup(x, R, hs, 0, nullptr);
             key = (uint64_t)c.cell[0] | (uint64_t)c.cell[1] << 16 | (uint64_t)c.cell[2] << 32;
+            if (R > kCellKeyMaxRes) key = ~0ull;               // cells the key cannot hold: k_grid_encode_bwd_wide
 #pragma unroll
             for (uint32_t i = 0; i < C; i++) validmask |= (c.valid[i] ? 1u : 0u) << i;
             *reinterpret_cast<float4*>(s_w4[tid]) = make_float4(c.frac[0], c.frac[1], c.frac[2], c.wn_re);
@@ -245,6 +247,66 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     }
 }
 
+// The levels of a merge call whose cells the 16-bit key fields cannot hold (R > kCellKeyMaxRes: k_grid_encode_bwd_merge
+// gives their samples the key ~0 and leaves them alone): every sample goes out on its own.  A separate launch, so that
+// the merge kernel's code stays what it was; its blocks leave at once on every other level.
+template <bool STE>
+__global__ __launch_bounds__(256) void k_grid_encode_bwd_wide(
+    const float* __restrict__ grad, const float* __restrict__ inputs, const float* __restrict__ emb,
+    const int32_t* __restrict__ offsets, const int32_t* __restrict__ resolutions,
+    float* __restrict__ grad_emb, uint32_t N, const uint32_t* __restrict__ clip_count, FeatLayout lay)
+{
+    constexpr uint32_t D = 3, F = 8, C = 8;
+    const uint32_t slot = blockIdx.y;
+    const uint32_t R = (uint32_t)resolutions[slot];
+    if (R <= kCellKeyMaxRes) return;
+    const bool     mask_on = STE && (clip_count == nullptr || *clip_count != 0);
+    const uint32_t off = (uint32_t)offsets[slot];
+    const uint32_t hs = (uint32_t)offsets[slot + 1] - off;
+    for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < N; b += gridDim.x * blockDim.x) {
+        // (the corner set-up of Corners<D, false>, in a loop that is not unrolled: same cells, weights and validity)
+        float x[D];
+        if (load_point<D>(inputs, b, x)) {
+            uint32_t cell[D];
+            float    frac[D];
+#pragma unroll
+            for (uint32_t d = 0; d < D; d++) {
+                float p = x[d] * (float)(R - 2);
+                p = p + 0.5f;
+                const float fl = floorf(p);
+                cell[d] = (uint32_t)fl;
+                frac[d] = p - fl;
+            }
+            uint32_t valid = 0;
+            float    wn = 0;
+#pragma unroll 1
+            for (uint32_t i = 0; i < C; i++) {
+                float wi = 1;
+                bool  border = false;
+#pragma unroll
+                for (uint32_t d = 0; d < D; d++) {
+                    const bool     bit = (i >> d) & 1u;
+                    const uint32_t q = bit ? min(cell[d] + 1, R - 1) : cell[d];
+                    wi *= bit ? frac[d] : 1 - frac[d];
+                    border |= (q == 0) | (q == R - 1);
+                }
+                valid |= (border ? 0u : 1u) << i;
+                wn += border ? 0.0f : wi;
+            }
+            if (wn == 0) wn = 1e-9f;
+            const float* gp = grad + feat_index(lay, slot, N, b, F);
+            float        g[F];
+            bool         nonzero = false;
+#pragma unroll
+            for (uint32_t k = 0; k < F; k++) {
+                g[k] = gp[k];
+                nonzero |= g[k] != 0.0f;
+            }
+            if (nonzero) scatter_point<D, F>(cell, frac, valid, 1.0f / wn, off, hs, R, g, emb, grad_emb, mask_on);
+        }
+    }
+}
+
 // grid_encode.hip launches this for the coarse half of a binned call (D = 3, F = 8)
 void launch_bwd_merge(const float* grad, const float* inputs, const float* emb, const int32_t* offsets,
                       const int32_t* resolutions, float* grad_emb, uint32_t N, uint32_t L,
@@ -263,6 +325,12 @@ void launch_bwd_merge(const float* grad, const float* inputs, const float* emb, 
         if (ste) hipLaunchKernelGGL((k_grid_encode_bwd_merge<true, 1024>), grid, dim3(1024), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
         else hipLaunchKernelGGL((k_grid_encode_bwd_merge<false, 1024>), grid, dim3(1024), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
     }
+    // (a few blocks per level slot: they leave at once unless the level is one of those, and the launch is all the call
+    // pays for it.  On such a level the 4096 threads walk the samples grid-stride, 2^D F atomics each: slow for millions
+    // of samples, but no encoder CNC builds has a level of R > 2^16, and the merge kernel keeps its speed)
+    const dim3 wide(div_up(N, 256u) < 16u ? div_up(N, 256u) : 16u, L);
+    if (ste) hipLaunchKernelGGL((k_grid_encode_bwd_wide<true>), wide, dim3(256), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
+    else hipLaunchKernelGGL((k_grid_encode_bwd_wide<false>), wide, dim3(256), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
 }
 
 }  // namespace cnc

@@ -66,8 +66,10 @@ extern "C" {
                                  * without occupancy mask / per-point level windows, volumes and planes.  For the calls
                                  * of a training step's context pass: lattice vertices in hash-slot order, which share
                                  * cells inside a block but never consecutively (0.70 -> 0.43 ms for its 3-D call).
-                                 * D in {2, 3}, F in {2, 4, 8}, no dy_dx, fewer than 64 levels of resolution < 2^16
-                                 * (points on higher levels are scattered one by one); other shapes ignore the flag. */
+                                 * D in {2, 3}, F in {2, 4, 8}, no dy_dx; points on a level past the 64th or of
+                                 * resolution > 2^16 (cell coordinates wider than the key's 16 bits per axis) are
+                                 * scattered one by one, as every merging backward kernel does; other shapes ignore
+                                 * the flag.                                                                        */
 #define CNC_FLAG_CELL_CARRY 16u  /* with CNC_FLAG_CELL_MERGE: two cells of a block that are neighbours along x share
                                  * 2^(D-1) vertices; each shared vertex is written once, next to its partner in the
                                  * 64-byte segment, by one of the two cells, which walks the other's points as well

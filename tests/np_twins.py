@@ -73,6 +73,52 @@ def _box_any(q, R, vxl):
     return tot > 0
 
 
+def grid_cells(x, R):
+    """Integer cell coordinates [N, D] of points at resolution R: floor(x (R-2) + 0.5), float32 as
+    gridencoder.cu:166-176 computes them (the same expression as `grid_corners`)."""
+    pos = ((np.asarray(x, f32) * f32(R - 2)).astype(np.float64) + 0.5).astype(f32)
+    return np.floor(pos).astype(np.uint32)
+
+
+def points_in_cells(cells, R, rng):
+    """float32 points [n, D] inside the given integer cells [n, D] of resolution R, at least 0.2 cells away from the
+    cell's faces where the cell allows it; every point is checked with `grid_cells`, so a constructed point that would
+    miss its cell (and test nothing) fails here instead."""
+    cells = np.asarray(cells, np.int64)
+    if R == 2:                                   # every point of [0, 1] sits in cell 0
+        x = rng.uniform(0, 1, size=cells.shape).astype(f32)
+    else:
+        t = np.clip(cells + rng.uniform(-0.3, 0.3, size=cells.shape), 0.0, R - 2.0)
+        x = np.minimum(t / (R - 2.0), 1.0).astype(f32)
+    assert np.array_equal(grid_cells(x, R).astype(np.int64), cells), "a constructed point misses its cell"
+    return x
+
+
+def make_grid_wide(res_list, log2_T, D, F, seed=0, log2_T_wide=17):
+    """tests/conftest.py `make_grid` (the offsets GridEncoder builds, a U(-1.5, 1.5) table), except that every level of
+    R > 2^16 gets a table of 2^log2_T_wide rows.  A hashed row is (x ^ y p1 ^ z p2) mod T: with T <= 2^16 its bits
+    depend on the low 16 bits of each coordinate only, so a kernel that cut its coordinates to 16 bits would still find
+    the right rows; with T >= 2^17 it finds other ones (and a dense 1-D row is the coordinate itself)."""
+    rng = np.random.default_rng(seed)
+    offs = [0]
+    for R in res_list:
+        n = min(2 ** (log2_T_wide if R > 1 << 16 else log2_T), int(R) ** D)
+        offs.append(offs[-1] + int(np.ceil(n / 8) * 8))
+    offs = np.asarray(offs, np.int32)
+    res = np.asarray(res_list, np.int32)
+    emb = rng.uniform(-1.5, 1.5, size=(offs[-1], F)).astype(np.float32)
+    return offs, res, emb
+
+
+def cut_coordinate_moves_rows(cells, axis, hashmap_size, R):
+    """Whether cutting coordinate `axis` of every cell [n, D] to 16 bits changes the row of the cell's corner 0: the
+    proof that a table is large enough for its level to tell a 16-bit cell key from the real cell."""
+    cells = np.asarray(cells, np.uint32)
+    cut = cells.copy()
+    cut[:, axis] &= np.uint32(0xFFFF)
+    return bool(np.all(grid_index(cut, hashmap_size, R) != grid_index(cells, hashmap_size, R)))
+
+
 def grid_corners(x, R, hashmap_size, vxl=None):
     """Per point and corner: table row, normalised weight w/sum(w_valid), validity; plus the
     in-range flag of the point.  gridencoder.cu:143-291."""

@@ -203,3 +203,60 @@ def check_against_reference_lookup(o, d, t, ri, cand_t, cand_ray, ref_occ, res):
     pos = o[cand_ray[diff]].astype(np.float64) + d[cand_ray[diff]].astype(np.float64) * cand_t[diff, None]
     u = (pos + 1.5) / 3.0 * res
     assert np.all(np.abs(u - np.round(u)).min(axis=1) < 1e-3)
+
+
+# The regime of tests/test_gpu_encoder_matrix.py: 1-D tables, levels where every corner is a border corner (R = 2) or
+# one vertex per axis is interior (R = 3), levels exactly as large as their table (R^D == T: dense, no padding) and
+# just above it (hashed; in 1-D, R = T + 1 wraps by the modulus), and cell coordinates that do not fit 16 bits, on tables
+# of 2^17 rows (np_twins.make_grid_wide): large enough that a coordinate cut to 16 bits would name another row.
+EDGE_GRIDS = [(1, [2, 3, 1001, 4096, 4097, 65536, 65537, 65538, 100003, (1 << 20) + 3], 12),
+              (2, [2, 3, 63, 64, 65, 65536, 65537, 65538, 100003], 12),
+              (3, [2, 3, 15, 16, 17, 65536, 65537, 65538, 100003], 12)]
+
+
+def _edge_points(D, res, offs, seed):
+    """`_points` plus points in the top cells (65535, 65536, R - 3, R - 2) of the large levels along every axis."""
+    rng = np.random.default_rng(seed)
+    pts = [_points(3000, D, seed)]
+    for l, R in enumerate(res):
+        if R < 65537:
+            continue
+        for d in range(D):
+            for gd in sorted({65535, 65536, R - 3, R - 2}):
+                if 1 <= gd <= R - 2:
+                    cells = rng.integers(1, R - 2, size=(20, D))
+                    cells[:, d] = gd
+                    if gd == 65536:
+                        assert tw.cut_coordinate_moves_rows(cells, d, int(offs[l + 1] - offs[l]), R)
+                    pts.append(tw.points_in_cells(cells, R, rng))
+    return np.concatenate(pts).astype(np.float32)
+
+
+@pytest.mark.parametrize("D,res,log2T", EDGE_GRIDS, ids=["D1", "D2", "D3"])
+@pytest.mark.parametrize("F", [1, 8])
+def test_forward_bitexact_on_sign_tables_at_edge_resolutions(oracle, D, res, log2T, F):
+    offs, resl, emb = tw.make_grid_wide(res, log2T, D, F, seed=30 + D)
+    assert any(R ** D == offs[l + 1] - offs[l] for l, R in enumerate(res))        # the R^D == T level is there
+    x = _edge_points(D, res, offs, seed=31 + D)
+    want = oracle.grid_encode_forward(x, emb, offs, resl, ste_binary=True)
+    got = tw.grid_encode_forward(x, emb, offs, resl, ste_binary=True)
+    assert np.array_equal(got, want)
+    assert np.all(want[0] == 0) and np.any(want[1] != 0)                          # R = 2: all corners on the border
+
+
+@pytest.mark.parametrize("D,res,log2T", EDGE_GRIDS, ids=["D1", "D2", "D3"])
+@pytest.mark.parametrize("ste", [False, True])
+def test_backward_float64_sums_agree_at_edge_resolutions(oracle, D, res, log2T, ste):
+    offs, resl, emb = tw.make_grid_wide(res, log2T, D, 4, seed=40 + D)
+    x = _edge_points(D, res, offs, seed=41 + D)
+    g = np.random.default_rng(42).normal(size=(len(resl), x.shape[0], 4)).astype(np.float32)
+    _, acc = oracle.grid_encode_backward(g, x, emb, offs, resl, ste_binary=ste, want_acc64=True)
+    acc_np, mag_np, cnt = tw.grid_encode_backward64(g, x, emb, offs, resl, ste_binary=ste)
+    assert np.all(np.abs(acc - acc_np) <= 1e-12 * (mag_np + 1e-300) * np.maximum(cnt, 1)[:, None])
+    assert np.array_equal(acc == 0, acc_np == 0)
+    assert np.all(acc[offs[0]:offs[1]] == 0)                                      # R = 2: no gradient
+    for l, R in enumerate(res):
+        assert cnt[offs[l]:offs[l + 1]].sum() > 0 or R == 2                       # every other level is reached
+        if R >= 65537:                                                            # ... up to its top cells
+            for d in range(D):
+                assert (tw.grid_cells(x[np.all((x >= 0) & (x <= 1), axis=1)], R)[:, d] == R - 2).any()
