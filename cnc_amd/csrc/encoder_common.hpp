@@ -336,6 +336,58 @@ __device__ __forceinline__ void unit_finish_fast(const UnitFast& u, float (&acc)
     }
 }
 
+// The same sum with the signs from a table instead of shift + bfi per feature.  Entry n of the nibble table holds the
+// four features of the sign nibble n as +-1.0f (bit j set: +1), 16 bytes per entry, 256 bytes in all: a corner's F
+// signs are F/4 ds_read_b128, and two features at a time take one v_pk_fma_f32 with the weight in both halves.
+// fmaf(tw, +-1, acc) is acc +- tw rounded once, the value the bfi form adds: BIT-IDENTICAL, same corner order.  The
+// table's 16 entries are the 16 four-bank slots of one 256-byte bank row, so a ds_read_b128 lane group reads distinct
+// slots or broadcasts: conflict-free whatever the patterns.  F = 4, 8, 16, 32 (a whole nibble per read).
+#ifndef CNC_SIGN_LUT
+#define CNC_SIGN_LUT 1          // 0: k_grid_encode_fwd_bits is built with unit_finish_fast alone
+#endif
+
+__device__ __forceinline__ float4 sign_nibble(uint32_t n)
+{
+    return make_float4((n & 1u) ? 1.0f : -1.0f, (n & 2u) ? 1.0f : -1.0f, (n & 4u) ? 1.0f : -1.0f,
+                       (n & 8u) ? 1.0f : -1.0f);
+}
+
+// A workgroup's table: the first 16 lanes fill it; the caller puts a barrier between this and the first read.
+__device__ __forceinline__ void fill_sign_lut(float4* lut)
+{
+    if (threadIdx.x < 16) lut[threadIdx.x] = sign_nibble(threadIdx.x);
+}
+
+template <uint32_t D, uint32_t F>
+__device__ __forceinline__ void unit_finish_lut(const UnitFast& u, const float4* __restrict__ lut, float (&acc)[F])
+{
+    static_assert(F % 4 == 0, "whole nibbles");
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    constexpr uint32_t C = 1u << D;
+    float wn = u.wn;
+    if (wn == 0) wn = 1e-9f;
+    const float wn_re = 1.0f / wn;
+    f2 a[F / 2];
+#pragma unroll
+    for (uint32_t k = 0; k < F / 2; k++) a[k] = f2{0.0f, 0.0f};
+#pragma unroll
+    for (uint32_t i = 0; i < C; i++) {
+        const float tw = u.m[i] * wn_re;
+        const f2    t2 = f2{tw, tw};
+#pragma unroll
+        for (uint32_t j = 0; j < F / 4; j++) {
+            const float4 s = lut[(u.rb[i] >> (4 * j)) & 15u];
+            a[2 * j] = __builtin_elementwise_fma(t2, f2{s.x, s.y}, a[2 * j]);
+            a[2 * j + 1] = __builtin_elementwise_fma(t2, f2{s.z, s.w}, a[2 * j + 1]);
+        }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < F / 2; k++) {
+        acc[2 * k] = a[k].x;
+        acc[2 * k + 1] = a[k].y;
+    }
+}
+
 template <uint32_t D, uint32_t F>
 __device__ __forceinline__ void unit_features_fast(const float (&x)[D], bool inside, const uint8_t* __restrict__ bits,
                                                    const UnitRec& r, float (&acc)[F])

@@ -146,11 +146,17 @@ __global__ CNC_FWD_BITS_BOUNDS void k_grid_encode_fwd_bits(
     const int32_t* __restrict__ offsets, const int32_t* __restrict__ resolutions,
     float* __restrict__ out, uint32_t N, uint32_t L, uint32_t P, uint32_t cp_log2, uint32_t Rb,
     const uint8_t* __restrict__ vxl, const int32_t* __restrict__ min_level_id, const int32_t* __restrict__ sat,
-    FeatLayout lay)
+    FeatLayout lay, uint32_t lut_mode)
 {
     constexpr uint32_t C = 1u << D;
     constexpr uint32_t V = F < 4 ? F : 4;
+    constexpr bool     LUT = CNC_SIGN_LUT && !VXL && (D == 2 || D == 3) && F % 4 == 0;
     extern __shared__ float s_tile[];            // TR only: [4 waves][64 points][Cp chunks of 4 floats], swizzled
+    __shared__ float4 s_sign[LUT ? 16 : 1];      // the sign-nibble table of unit_finish_lut
+    if constexpr (LUT) {
+        fill_sign_lut(s_sign);
+        __syncthreads();
+    }
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t Cp = 1u << cp_log2;           // 16-byte chunks per point and pass
@@ -184,7 +190,15 @@ __global__ CNC_FWD_BITS_BOUNDS void k_grid_encode_fwd_bits(
                 for (uint32_t d = 0; d < D; d++) rd *= R;
                 const bool dense = rd <= hs, pow2 = (hs & (hs - 1u)) == 0u;
                 if ((dense || pow2) && (off & 7u) == 0u) {
-                    unit_features_fast<D, F>(x, inside, bits, UnitRec{off, hs, R, 0u}, acc);
+                    // the sign table (lut_mode 1: every level, 2: dense levels only) or shift + bfi
+                    UnitFast u;
+                    unit_issue_fast<D, F>(x, inside, bits, UnitRec{off, hs, R, 0u}, u);
+                    bool lut = false;
+                    if constexpr (LUT) {
+                        lut = lut_mode == 1 || (lut_mode == 2 && dense);
+                        if (lut) unit_finish_lut<D, F>(u, s_sign, acc);
+                    }
+                    if (!lut) unit_finish_fast<D, F>(u, acc);
                     done = true;
                 }
             }
@@ -1030,11 +1044,13 @@ static void launch_fwd_bits(const float* inputs, const uint8_t* bits, const int3
     // pieces need the L2 to merge into lines (streamed they cost 3.7x).
     const int nt_mode = getenv("CNC_FWD_NT") ? atoi(getenv("CNC_FWD_NT")) : 1;
     lay.nt = (nt_mode == 1 && lay.ld == 0) || (nt_mode == 2 && tr) ? 1u : 0u;
+    // sign table of the lean evaluator (CNC_FWD_LUT: 0 shift + bfi, 1 every level, 2 dense levels only)
+    const uint32_t lut_mode = getenv("CNC_FWD_LUT") ? (uint32_t)atoi(getenv("CNC_FWD_LUT")) : 1u;
     const dim3 grid(div_up(N, 256), div_up(L, P), 1);
     const size_t lds = tr ? (size_t)256 * W * sizeof(float) : 0;
 #define CNC_FWD_BITS(VX, TRV)                                                                                        \
     hipLaunchKernelGGL((k_grid_encode_fwd_bits<D, F, VX, TRV>), grid, dim3(256), TRV ? lds : 0, s, inputs, bits, offsets, \
-                       resolutions, outputs, N, L, P, cp_log2, Rb, vxl, mli, VX ? sat : nullptr, lay)
+                       resolutions, outputs, N, L, P, cp_log2, Rb, vxl, mli, VX ? sat : nullptr, lay, lut_mode)
     if (vxl) { if (tr) CNC_FWD_BITS(true, true); else CNC_FWD_BITS(true, false); }
     else     { if (tr) CNC_FWD_BITS(false, true); else CNC_FWD_BITS(false, false); }
 #undef CNC_FWD_BITS
