@@ -22,6 +22,11 @@ class RaySegments(C.Structure):
                 ("is_left", _vp), ("is_right", _vp), ("is_valid", _vp)]
 
 
+class PdfRows(C.Structure):
+    """cnc_pdf_rows_t (include/cnc_hip.h)."""
+    _fields_ = [("seg", RaySegments), ("n_rays", _i64), ("n_edges_per_ray", _i64), ("n_edges", _i64)]
+
+
 class CtxWindow(C.Structure):
     """cnc_ctx_window_t (include/cnc_hip.h)."""
     _fields_ = [("pos", _vp * 16), ("cnt", _vp * 16), ("val", _vp * 16), ("p_at", _i64 * 17), ("v_at", _i64 * 17),
@@ -131,6 +136,8 @@ SIGNATURES = {
     "cnc_march_samples_coarse": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cnc_sample_positions": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "cnc_importance_sampling": [C.POINTER(PdfRows), _vp, _vp, C.POINTER(PdfRows), C.POINTER(PdfRows), _vp],
+    "cnc_searchsorted": [C.POINTER(PdfRows), C.POINTER(PdfRows), _vp, _vp, _vp],
     "cnc_inclusive_sum": [_vp, _vp, _vp, _vp, _u32, _i64, _i32, _i32, _vp],
     "cnc_exclusive_sum": [_vp, _vp, _vp, _vp, _u32, _i64, _i32, _i32, _vp],
     "cnc_inclusive_prod_forward": [_vp, _vp, _vp, _vp, _u32, _i64, _vp],
@@ -197,7 +204,7 @@ CNC_PACK_TRANSPOSE = 1
 CNC_PACK_ZERO_FIRST = 2
 CNC_VOLREND_ACCUMULATE = 1
 CNC_VOLREND_FINALIZE = 2
-ABI_VERSION = 31          # cnc_abi_version() of the library this table was written for
+ABI_VERSION = 32          # cnc_abi_version() of the library this table was written for
 
 
 def lib() -> C.CDLL:

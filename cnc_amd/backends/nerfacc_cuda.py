@@ -1,5 +1,6 @@
 """Drop-in for the reference's `nerfacc.csrc` extension (nerfacc/cuda/csrc/nerfacc.cpp:100-129):
-ray_aabb_intersect, traverse_grids, the six segmented scans and the RaySegmentsSpec record.
+ray_aabb_intersect, traverse_grids, the six segmented scans, importance_sampling, searchsorted and the
+RaySegmentsSpec record.
 
 The callee allocates and returns tensors on the inputs' device, like the reference's host
 functions; the allocation / cumsum logic of grid.cu:356-510 and data_spec.hpp:53-106 lives here
@@ -343,8 +344,102 @@ def _not_built(name):
     return f
 
 
-# bound by the reference module but unused by CNC
-importance_sampling = _not_built("importance_sampling")
-searchsorted = _not_built("searchsorted")
+def _rows(spec, name):
+    """cnc_pdf_rows_t of a RaySegmentsSpec after the checks of data_spec.hpp:15-53: batched when vals has more than
+    one axis (rows along the last), else flattened by chunk_starts / chunk_cnts."""
+    if spec.vals is None:
+        raise RuntimeError(f"{name}: vals must be defined")
+    check_input(spec.vals, f"{name}.vals")
+    if spec.vals.dtype != torch.float32:
+        raise RuntimeError(f"{name}: vals must be float32")
+    if spec.vals.dim() > 1:
+        e = spec.vals.shape[-1]
+        n_rays = spec.vals.numel() // e if e else int(torch.Size(spec.vals.shape[:-1]).numel())
+        return _lib.PdfRows(spec._view(), n_rays, e, spec.vals.numel())
+    if spec.chunk_starts is None or spec.chunk_cnts is None:
+        raise RuntimeError(f"{name}: a flattened segment needs chunk_starts and chunk_cnts")
+    for k in ("chunk_starts", "chunk_cnts", "ray_indices", "is_left", "is_right"):
+        t = getattr(spec, k)
+        if t is not None:
+            check_input(t, f"{name}.{k}")
+            if t.dim() != 1:
+                raise RuntimeError(f"{name}.{k} must be 1-D")
+    if spec.chunk_starts.numel() != spec.chunk_cnts.numel():
+        raise RuntimeError(f"{name}: chunk_starts and chunk_cnts differ in length")
+    if spec.chunk_starts.dtype != torch.int64 or spec.chunk_cnts.dtype != torch.int64:
+        raise RuntimeError(f"{name}: chunk_starts and chunk_cnts must be int64")
+    if spec.ray_indices is not None and (spec.ray_indices.numel() != spec.vals.numel()
+                                         or spec.ray_indices.dtype != torch.int64):
+        raise RuntimeError(f"{name}: ray_indices must be int64 with one entry per value")
+    return _lib.PdfRows(spec._view(), spec.chunk_cnts.numel(), -1, spec.vals.numel())
+
+
+def importance_sampling(ray_segments, cdfs, n_intervals_per_ray, stratified, jitter=None):
+    """pdf.cu:294-424 -> [intervals, samples] (RaySegmentsSpec), one launch of cnc_importance_sampling.  An int
+    n gives batched outputs ((..., n) and (..., n + 1), or (n_rays, n) for a flattened input) with no host
+    synchronisation; a tensor [n_rays] gives flattened outputs sized by one host read of the two totals.
+    stratified: one bias per ray drawn here with torch.rand on the device ([0, 1); the reference draws (0, 1] from
+    its Philox stream inside the kernel); `jitter` (extension) supplies that f32 [n_rays] bias instead."""
+    seg = _rows(ray_segments, "ray_segments")
+    check_input(cdfs, "cdfs")
+    if cdfs.dtype != torch.float32 or cdfs.numel() != ray_segments.vals.numel():
+        raise RuntimeError("importance_sampling: cdfs must be float32 with one value per edge")
+    dev = cdfs.device
+    n_rays = seg.n_rays
+    if jitter is None and stratified:
+        jitter = torch.rand(n_rays, dtype=torch.float32, device=dev)
+    if jitter is not None:
+        check_input(jitter, "jitter")
+        if jitter.dtype != torch.float32 or jitter.numel() != n_rays:
+            raise RuntimeError("importance_sampling: jitter must be float32 [n_rays]")
+    samples, intervals = RaySegmentsSpec(), RaySegmentsSpec()
+    if isinstance(n_intervals_per_ray, torch.Tensor):
+        check_input(n_intervals_per_ray, "n_intervals_per_ray")
+        if n_intervals_per_ray.numel() != n_rays:
+            raise RuntimeError("importance_sampling: n_intervals_per_ray must hold one count per ray")
+        cnt = n_intervals_per_ray.reshape(-1).to(torch.int64)
+        samples.chunk_cnts = cnt
+        intervals.chunk_cnts = (cnt + 1) * (cnt > 0)
+        ends_s, ends_i = torch.cumsum(samples.chunk_cnts, 0), torch.cumsum(intervals.chunk_cnts, 0)
+        # the one host read (data_spec.hpp:86-96 makes it once per allocation; here both totals come together)
+        n_s, n_i = torch.stack([ends_s[-1], ends_i[-1]]).tolist() if n_rays else (0, 0)
+        samples.chunk_starts, intervals.chunk_starts = ends_s - samples.chunk_cnts, ends_i - intervals.chunk_cnts
+        samples.memalloc_data(n_s, alloc_masks=False, zero_init=False)
+        intervals.memalloc_data(n_i, alloc_masks=True, zero_init=False)
+        smp_rows = _lib.PdfRows(samples._view(), n_rays, -1, n_s)
+        itv_rows = _lib.PdfRows(intervals._view(), n_rays, -1, n_i)
+    else:
+        n = int(n_intervals_per_ray)
+        if n < 0:
+            raise RuntimeError("importance_sampling: n_intervals_per_ray must be >= 0")
+        lead = list(ray_segments.vals.shape[:-1]) if ray_segments.vals.dim() > 1 else [n_rays]
+        samples.vals = torch.empty(lead + [n], dtype=torch.float32, device=dev)
+        intervals.vals = torch.empty(lead + [n + 1], dtype=torch.float32, device=dev)
+        smp_rows = _lib.PdfRows(samples._view(), n_rays, n, samples.vals.numel())
+        itv_rows = _lib.PdfRows(intervals._view(), n_rays, n + 1, intervals.vals.numel())
+    if n_rays:
+        rc = _lib.lib().cnc_importance_sampling(C.byref(seg), ptr(cdfs), ptr(jitter), C.byref(smp_rows),
+                                                C.byref(itv_rows), stream(dev))
+        check(rc, "importance_sampling")
+    return [intervals, samples]
+
+
+def searchsorted(query, key):
+    """pdf.cu:424-456 -> [ids_left, ids_right] i64 shaped like query.vals: key[left] <= query < key[right] in the
+    key segment of each query entry's ray, clamped to it; ids local to the row for a batched query, global for a
+    flattened one (see cnc_searchsorted)."""
+    q, k = _rows(query, "query"), _rows(key, "key")
+    if q.n_edges_per_ray >= 0 and k.n_rays < q.n_rays:
+        raise RuntimeError("searchsorted: the key has fewer rays than the batched query has rows")
+    ids_left = torch.empty(query.vals.shape, dtype=torch.int64, device=query.vals.device)
+    ids_right = torch.empty(query.vals.shape, dtype=torch.int64, device=query.vals.device)
+    if q.n_edges:
+        rc = _lib.lib().cnc_searchsorted(C.byref(q), C.byref(k), ptr(ids_left), ptr(ids_right),
+                                         stream(query.vals.device))
+        check(rc, "searchsorted")
+    return [ids_left, ids_right]
+
+
+# bound by the reference module but unused by CNC (SURVEY.md §2 row 12)
 opencv_lens_undistortion = _not_built("opencv_lens_undistortion")
 opencv_lens_undistortion_fisheye = _not_built("opencv_lens_undistortion_fisheye")

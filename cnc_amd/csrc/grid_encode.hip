@@ -1152,4 +1152,4 @@ extern "C" const char* cnc_error_string(int code)
     }
 }
 
-extern "C" int cnc_abi_version(void) { return 31; }
+extern "C" int cnc_abi_version(void) { return 32; }

@@ -1,6 +1,7 @@
 """Image rendering with an occupancy-grid sampler: the two functions the CNC drivers call,
 `render_image_with_occgrid` (training batches, chunked evaluation) and `render_image_with_occgrid_test`
-(whole-image evaluation that marches all rays a few steps at a time), plus `Rays`, `namedtuple_map`,
+(whole-image evaluation that marches all rays a few steps at a time), the proposal-network render
+`render_image_with_propnet` (examples/utils.py:219-313), plus `Rays`, `namedtuple_map`,
 `set_random_seed` and the scene lists — the names of the reference's examples/utils.py (:77-80, :83-216,
 :316-489) and examples/datasets/utils.py, with the same arguments and return tuples.
 
@@ -13,12 +14,12 @@ from __future__ import annotations
 
 import collections
 import random
-from typing import Optional
+from typing import Literal, Optional, Sequence
 
 import numpy as np
 import torch
 
-from .nerfacc import OccGridEstimator
+from .nerfacc import OccGridEstimator, PropNetEstimator
 from .nerfacc.volrend import rendering
 
 Rays = collections.namedtuple("Rays", ("origins", "viewdirs"))
@@ -119,6 +120,67 @@ def render_image_with_occgrid(radiance_field: torch.nn.Module, estimator: OccGri
         n_samples += t_starts.shape[0]
     rgb, opacity, depth = (torch.cat(p, dim=0).view(*lead, -1) for p in zip(*parts))
     return (rgb, opacity, depth, n_samples, extras) if return_extra else (rgb, opacity, depth, n_samples)
+
+
+def _midpoints_on_rows(origins, dirs, t_starts, t_ends):
+    """Midpoints o + d (t0 + t1) / 2 of batched samples (n_rays, S) -> (n_rays, S, 3)."""
+    return origins[:, None, :] + dirs[:, None, :] * (t_starts + t_ends)[..., None] / 2.0
+
+
+def _last_sample_opaque(sigmas):
+    """Densities (n_rays, S) with the last sample of every ray made opaque (inf): a solid background."""
+    last = torch.zeros_like(sigmas, dtype=torch.bool)
+    last[:, -1] = True
+    return torch.where(last, torch.full_like(sigmas, float("inf")), sigmas)
+
+
+def render_image_with_propnet(radiance_field: torch.nn.Module, proposal_networks: Sequence[torch.nn.Module],
+                              estimator: PropNetEstimator, rays: Rays, num_samples: int,
+                              num_samples_per_prop: Sequence[int], near_plane: Optional[float] = None,
+                              far_plane: Optional[float] = None,
+                              sampling_type: Literal["uniform", "lindisp"] = "lindisp", opaque_bkgd: bool = True,
+                              render_bkgd: Optional[torch.Tensor] = None, proposal_requires_grad: bool = False,
+                              test_chunk_size: int = 8192):
+    """(rgb, opacity, depth, extras) for a batch or an image of rays, sampled by proposal networks: the estimator
+    resamples every ray through `proposal_networks` (num_samples_per_prop samples each, densities only) and hands
+    num_samples intervals per ray to the radiance field, whose colours and densities are composited.  Training
+    renders all rays at once with stratified samples; evaluation goes test_chunk_size rays at a time.  With
+    `proposal_requires_grad` the proposal levels are evaluated with gradients and cached for
+    `estimator.update_every_n_steps`.  `opaque_bkgd` makes the last sample of every ray opaque.
+
+    The networks take this package's flat inputs: a proposal network maps positions (N, 3) to densities (N, 1),
+    the radiance field maps (positions (N, 3), directions (N, 3)) to (rgb (N, 3), density (N, 1))."""
+    rays, lead = _as_ray_list(rays)
+    total = rays.origins.shape[0]
+    chunk = total if radiance_field.training else test_chunk_size
+    parts, extras = [], None
+    for first in range(0, total, max(chunk, 1)):
+        o, d = rays.origins[first:first + chunk], rays.viewdirs[first:first + chunk]
+
+        def level_fn(net, o=o, d=d):
+            # one closure per network, so that every level evaluates its own proposal network
+            def sigma_fn(t_starts, t_ends):
+                x = _midpoints_on_rows(o, d, t_starts, t_ends)
+                sigmas = net(x.reshape(-1, 3)).reshape(t_starts.shape)
+                return _last_sample_opaque(sigmas) if opaque_bkgd else sigmas
+            return sigma_fn
+
+        def rgb_sigma_fn(t_starts, t_ends, ray_indices, o=o, d=d):
+            x = _midpoints_on_rows(o, d, t_starts, t_ends)
+            v = d[:, None, :].expand(x.shape)
+            rgb, sigmas = radiance_field(x.reshape(-1, 3), v.reshape(-1, 3))
+            rgb, sigmas = rgb.reshape(x.shape), sigmas.reshape(t_starts.shape)
+            return rgb, (_last_sample_opaque(sigmas) if opaque_bkgd else sigmas), x
+
+        t_starts, t_ends = estimator.sampling(
+            prop_sigma_fns=[level_fn(net) for net in proposal_networks], prop_samples=num_samples_per_prop,
+            num_samples=num_samples, n_rays=o.shape[0], near_plane=near_plane, far_plane=far_plane,
+            sampling_type=sampling_type, stratified=radiance_field.training, requires_grad=proposal_requires_grad)
+        rgb, opacity, depth, extras = rendering(t_starts, t_ends, ray_indices=None, n_rays=None,
+                                                rgb_sigma_fn=rgb_sigma_fn, render_bkgd=render_bkgd)
+        parts.append((rgb, opacity, depth))
+    rgb, opacity, depth = (torch.cat(p, dim=0).view(*lead, -1) for p in zip(*parts))
+    return rgb, opacity, depth, extras
 
 
 @torch.no_grad()

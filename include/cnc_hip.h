@@ -457,6 +457,53 @@ int cnc_sample_positions(const float* rays_o, const float* rays_d, const int64_t
                          float* positions, float* dirs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Proposal sampling — replaces nerfacc/cuda/csrc/nerfacc.cpp:73-86,111-118 (pdf.cu), ABI v32
+ * ---------------------------------------------------------------------------------------- */
+
+/* Ray segments with their layout: batched rows of n_edges_per_ray entries (n_edges_per_ray >= 0; row r starts at
+ * r * n_edges_per_ray), or flattened (n_edges_per_ray == -1) by seg.chunk_starts / seg.chunk_cnts [n_rays].
+ * n_edges: the entries of seg.vals.                                                                               */
+typedef struct {
+    cnc_ray_segments_t seg;
+    int64_t            n_rays;
+    int64_t            n_edges_per_ray;
+    int64_t            n_edges;
+} cnc_pdf_rows_t;
+
+/* importance_sampling (pdf.cu:294-400) in one launch: samples and interval edges together.
+ *   segments: the input edges t (vals) of n_rays rays, batched or flattened; cdfs: f32, same layout.
+ *   samples / intervals: the outputs.  Batched: samples->n_edges_per_ray = n (>= 0), intervals' = n + 1, rows at
+ *     r * n and r * (n + 1) of .vals.  Flattened (both -1): n_r = samples->seg.chunk_cnts[r]; the caller allocates
+ *     samples (vals, ray_indices at chunk_starts) and intervals (chunk_cnts = (n_r + 1) (n_r > 0); vals, ray_indices,
+ *     is_left, is_right at intervals->seg.chunk_starts).
+ *   jitter: NULL, or f32 [n_rays]: the per-ray bias of stratified sampling (the reference draws it in the kernel
+ *     from the CUDA Philox generator, (0,1]; here the caller supplies it, e.g. torch.rand, [0,1): no RNG state).
+ * For ray r with input edges base..last (ne = last - base + 1) and sid in 0..n_r-1:
+ *   u_step = (cdf[last] - cdf[base]) / n_r (correctly rounded), bias = jitter ? jitter[r] : 0.5,
+ *   u = fmaf(sid + bias, u_step, cdf[base]); p = upper bound of u in cdf[base, last) (NaN goes right);
+ *   p0 = clamp(p - 1, base, last), p1 = clamp(p, base, last);
+ *   t = cdf[p1] - cdf[p0] < 1e-10 ? (vals[p0] + vals[p1]) / 2 : fmaf(u - cdf[p0], dv / dc, vals[p0]).
+ *   Edges: edge 0 = max(t0 - (t1 - t0) / 2, vals[base]), edge k = (t_k + t_{k-1}) / 2,
+ *   edge n = min(t_{n-1} + (t_{n-1} - t_{n-2}) / 2, vals[last]); packed: edge 0 is left only, the last edge right
+ *   only, the others both.
+ * Cases the reference leaves undefined, defined here (no read outside the ray's segment or write outside its row):
+ *   n_r == 1      : the edges are [vals[base], vals[last]] (the sample follows the formula above);
+ *   ne == 1       : the formula as written: every sample and edge is vals[base];
+ *   ne == 0, n_r>0: every sample and edge is NaN (flags and ray_indices as usual);
+ *   n_r == 0      : flattened: nothing is written; batched: the single edge is vals[base] (NaN when ne == 0).    */
+int cnc_importance_sampling(const cnc_pdf_rows_t* segments, const float* cdfs, const float* jitter,
+                            const cnc_pdf_rows_t* samples, const cnc_pdf_rows_t* intervals, void* stream);
+
+/* searchsorted (pdf.cu:240-290,424-456): for every query entry, (ids_left, ids_right) i64 [query->n_edges] with
+ * key[left] <= q < key[right] in the key segment of the entry's ray, both clamped to the segment.  The ray of an entry:
+ * its row (batched query; key->n_rays >= query->n_rays), else query->seg.ray_indices when given, else the last chunk
+ * whose query chunk_starts is <= the entry.  Ids are local to the row for a batched query, indices into the key's
+ * vals as a whole for a flattened one.  An empty key segment gives base (local 0) for both; a flattened entry whose
+ * ray lies outside [0, key->n_rays) gets -1 for both.                                                                */
+int cnc_searchsorted(const cnc_pdf_rows_t* query, const cnc_pdf_rows_t* key, int64_t* ids_left, int64_t* ids_right,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-ray segmented scans — replaces nerfacc/cuda/csrc/nerfacc.cpp:8-39 (scan.cu)
  * ---------------------------------------------------------------------------------------- */
 
