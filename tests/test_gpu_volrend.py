@@ -97,18 +97,24 @@ def test_forward_against_reference_golden(cuda):
         assert np.allclose(dep.cpu().numpy(), g[f"{case}_depth"], rtol=2e-5, atol=1e-5)
 
 
-def _chain64(t0, t1, sig, rgb, starts, cnts, bk):
-    """The reference's op chain in float64 torch (CPU, autograd)."""
+def _chain64(t0, t1, sig, rgb, starts, cnts, bk, prefix=None, finalize=True, expm1=False):
+    """The reference's op chain in float64 torch (CPU, autograd).  `prefix`: per-sample prefix transmittance;
+    `finalize=False`: the plain sums (colour without background, depth not divided by opacity); `expm1`: alpha as
+    -expm1(-tau), the same function without the cancellation of 1 - exp(-tau) at small tau."""
     tau = sig * (t1 - t0)
     before = torch.cat([torch.cumsum(torch.nn.functional.pad(tau[a:a + n][:-1], (1, 0)), 0)
                         for a, n in zip(starts.tolist(), cnts.tolist()) if n > 0])
-    trans, alpha = torch.exp(-before), 1 - torch.exp(-tau)
+    trans, alpha = torch.exp(-before), -torch.expm1(-tau) if expm1 else 1 - torch.exp(-tau)
+    if prefix is not None:
+        trans = trans * prefix
     w = trans * alpha
     ri = torch.repeat_interleave(torch.arange(len(cnts)), torch.as_tensor(cnts))
     R = len(cnts)
     col = torch.zeros(R, 3, dtype=torch.float64).index_add(0, ri, w[:, None] * rgb)
     op = torch.zeros(R, 1, dtype=torch.float64).index_add(0, ri, w[:, None])
     dsum = torch.zeros(R, 1, dtype=torch.float64).index_add(0, ri, (w * (t0 + t1) / 2)[:, None])
+    if not finalize:
+        return col, op, dsum, w, trans, alpha
     dep = dsum / op.clamp_min(torch.finfo(torch.float32).eps)
     return col + bk * (1 - op), op, dep, w, trans, alpha
 
