@@ -59,10 +59,12 @@ struct BinnedArgs {
     const int32_t*  resolutions;
     float*          grad_emb;
     uint32_t        N;
-    uint32_t        first_level;     // binned levels are [first_level, first_level + gridDim.y)
+    uint32_t        first_level;     // binned levels are [first_level, first_level + n_binned)
     uint32_t        bins;            // slabs per level = ceil(level_rows / 256)
     uint32_t        cap;             // item slots per bin
     uint32_t        part;            // items one owner wave takes (a fuller bin is shared by several waves)
+    uint32_t        parts;           // owner waves per bin = ceil(cap / part)
+    uint32_t        n_pairs;         // owner pass: levels [0, 2 * n_pairs) are placed pairwise (owner_slab)
     uint32_t*       bin_count;       // [n_binned][bins]
     Item*           items;           // [n_binned][bins][cap]
     const uint32_t* clip_count;
@@ -403,6 +405,47 @@ __device__ __forceinline__ void lds_row_add(float* __restrict__ acc, uint32_t ro
     }
 }
 
+// ---- pass 2: which slab a workgroup of the 1-D owner grid takes ------------------------------------------------
+// Workgroups are dealt round-robin over the chip's 8 XCDs (observed: ids w and w + 8 share one; tools/xcd_label_probe.hip
+// checks it) and each XCD has its own L2.  The paired placement (CNC_FLAG_OWNER_XCD_PAIRS, a measurement switch) puts the
+// owner waves of a level on 4 of the 8: levels 2p and 2p + 1 share one id range in which ids with (w % 8) < 4 enumerate
+// the first level's (part, bin) slabs and the others the second's, 4 per 8 consecutive ids; `bins` is padded to a multiple
+// of 8 there and the surplus ids own nothing.  The levels from 2 * n_pairs on (all of them with the flag unset, a trailing
+// odd one with it) follow level by level, part * bins + bin within each, over all 8 labels.
+// What it was built to test: if a 64-byte gradient sector, wanted by 8 items in 8 unrelated bins, were fetched once per
+// XCD hosting one of them, 4 XCDs would need 3.60 fetches where 8 need 5.25.  Measured: read requests -2 %, time
+// unchanged — the bins' waves are too far apart in the sample stream to share through an L2
+// (profiles/r09_owner_xcd_placement.md); off by default.
+// w % 8 is a group label, not an XCD id, and nothing depends on it for correctness: every id decodes to its own
+// (level, bin, part) and the workgroup owns exactly that slab, so another dispatch order changes speed only.
+// (tests/test_owner_grid.py holds a Python twin of this function.)
+__host__ __device__ __forceinline__ uint32_t owner_bins_padded(uint32_t bins) { return (bins + 7u) & ~7u; }
+
+__host__ __device__ __forceinline__ uint64_t owner_grid_size(uint32_t n_binned, uint32_t bins, uint32_t parts, uint32_t n_pairs)
+{
+    return (uint64_t)n_pairs * 2 * parts * owner_bins_padded(bins) + (uint64_t)(n_binned - 2 * n_pairs) * parts * bins;
+}
+
+__device__ __forceinline__ void owner_slab(uint32_t w, uint32_t bins, uint32_t parts, uint32_t n_pairs, uint32_t& level,
+                                           uint32_t& bin, uint32_t& part)
+{
+    const uint32_t padded = owner_bins_padded(bins);
+    const uint32_t pair_ids = 2 * parts * padded;       // a multiple of 16: every pair starts at label 0
+    if (w < n_pairs * pair_ids) {
+        const uint32_t pair = w / pair_ids, v = w % pair_ids;
+        const uint32_t idx = (v >> 3) * 4 + (v & 3u);   // position among its half's ids
+        level = 2 * pair + ((v >> 2) & 1u);
+        part = idx / padded;
+        bin = idx % padded;
+    } else {
+        const uint32_t v = w - n_pairs * pair_ids, per_level = parts * bins;
+        const uint32_t u = v % per_level;
+        level = 2 * n_pairs + v / per_level;
+        part = u / bins;
+        bin = u % bins;
+    }
+}
+
 template <uint32_t F, bool STE>
 __global__ __launch_bounds__(64) void k_bwd_owner(BinnedArgs a)
 {
@@ -410,20 +453,22 @@ __global__ __launch_bounds__(64) void k_bwd_owner(BinnedArgs a)
     __shared__ __attribute__((aligned(16))) float s_acc[kSlab * F];
     __shared__ __attribute__((aligned(16))) uint32_t s_cnt[kSlab];
     static_assert(kSlab * sizeof(uint32_t) == 64 * sizeof(uint4), "one uint4 per lane clears the tickets");
-    // blockIdx.x = part * bins + bin: the waves that take the second, third ... `part` items of a bin are
-    // scheduled after every bin's first wave — they exist only for bins far above the mean (thin slices of
+    // Within a level the id runs as part * bins + bin: the waves that take the second, third ... `part` items of a
+    // bin are scheduled after every bin's first wave — they exist only for bins far above the mean (thin slices of
     // space hash unevenly onto the slabs: up to 7.7x the mean at resolution 296 on the first chunk of the
     // bench frame, where one wave per bin made the pass 2x slower than on the other chunks)
-    const uint32_t bin = blockIdx.x % a.bins, part = blockIdx.x / a.bins, lane = threadIdx.x;
-    const uint32_t slot = a.first_level + blockIdx.y;
+    uint32_t level, bin, part;
+    owner_slab(blockIdx.x, a.bins, a.parts, a.n_pairs, level, bin, part);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t slot = a.first_level + level;
     const uint32_t off = (uint32_t)a.offsets[slot];
     const uint32_t hs = (uint32_t)a.offsets[slot + 1] - off;
-    if (bin * kSlab >= hs) return;
-    uint32_t n = a.bin_count[(size_t)blockIdx.y * a.bins + bin];
+    if (bin >= a.bins || bin * kSlab >= hs) return;     // padding of the paired ranges, rows past the level's end
+    uint32_t n = a.bin_count[(size_t)level * a.bins + bin];
     n = n < a.cap ? n : a.cap;
     if (n <= part * a.part) return;     // nothing (more) landed here: the table slab stays as it is
     const bool  shared_slab = n > a.part;
-    const Item* my = a.items + ((size_t)blockIdx.y * a.bins + bin) * a.cap + (size_t)part * a.part;
+    const Item* my = a.items + ((size_t)level * a.bins + bin) * a.cap + (size_t)part * a.part;
     n = min(n - part * a.part, a.part);
 
     for (uint32_t k = lane * 4; k < kSlab * F; k += 64 * 4)     // 16-byte LDS stores
@@ -561,7 +606,7 @@ static void launch_binned(const BinnedArgs& a, uint32_t n_binned, bool ste, bool
 {
     sorted = sorted && a.bins <= kSortBins;
     const dim3 g1(div_up(a.N, 1024 * (sorted ? kSortSamplesPerThread : kBinSamplesPerThread)), n_binned),
-        g2(a.bins * div_up(a.cap, a.part), n_binned);
+        g2((uint32_t)owner_grid_size(n_binned, a.bins, a.parts, a.n_pairs));
     if (ste) {
         if (sorted) hipLaunchKernelGGL((k_bwd_bin_sorted<F, true>), g1, dim3(1024), 0, s, a);
         else hipLaunchKernelGGL((k_bwd_bin<F, true>), g1, dim3(1024), 0, s, a);
@@ -649,8 +694,12 @@ extern "C" int cnc_grid_encode_backward_binned(const float* grad, const float* i
     hipStream_t s = (hipStream_t)stream;
     uint32_t*   ws = (uint32_t*)workspace;
     if (hipMemsetAsync(ws, 0, heads * 4, s) != hipSuccess) return CNC_ERR_LAUNCH;
+    const uint32_t part = owner_part(N, bins, cap), parts = div_up((uint32_t)cap, part);
+    // pairs of levels on complementary halves of the XCD labels (owner_slab); an odd level out stays on all eight
+    const uint32_t n_pairs = (flags & CNC_FLAG_OWNER_XCD_PAIRS) ? n_binned / 2 : 0;
+    if (owner_grid_size(n_binned, bins, parts, n_pairs) > 0x7FFFFFFFull) return CNC_ERR_INVALID_VALUE;
     BinnedArgs a{grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, L - n_binned,
-                 bins, (uint32_t)cap, owner_part(N, bins, cap), ws, (Item*)((char*)workspace + heads * kHeadBytes), ste_clip_count,
+                 bins, (uint32_t)cap, part, parts, n_pairs, ws, (Item*)((char*)workspace + heads * kHeadBytes), ste_clip_count,
                  FeatLayout{grad_ld, grad_col}};
     const bool ste = (flags & CNC_FLAG_STE_BINARY) != 0;
     const bool sorted = (flags & CNC_FLAG_BIN_LANE_STORES) == 0;

@@ -7,6 +7,7 @@
 // streams and events belong to a plan object the caller creates once (no globals in the library), and one call
 // does:   fork event on `stream`  ->  finest levels in one or two groups on the plan's side streams
 //                                 ->  coarse levels on `stream`  ->  `stream` waits for the groups.
+// (one group unless CNC_BWD_GROUP_SPLIT asks for two: split_groups)
 // Everything the call touches is ordered on `stream` again when it returns.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@ struct cnc_backward_plan {
     hipEvent_t  fork;
     hipEvent_t  join[2];
     int         device;
+    int         group_split;    // CNC_BWD_GROUP_SPLIT (split_groups); 0: not set
 };
 
 namespace {
@@ -28,12 +30,17 @@ constexpr uint64_t kAlign = 256;
 
 inline uint64_t round_up(uint64_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
-// the finest levels as one group, or two halves when there are four or more (the bin pass of one next to the owner
-// pass of the other: scattered stores vs. gathers — 1.122 -> 1.083 ms in the bench)
-inline int split_groups(uint32_t n_binned, uint32_t first[2], uint32_t count[2])
+// The finest levels run as ONE group: the bin pass of all of them, then their owner pass, on one side stream.  Until
+// round 8 four or more levels went as two halves on the two side streams (the bin pass of one next to the owner pass of
+// the other: 1.122 -> 1.083 ms in the round-2 bench; at parity in round 3); with today's kernels the halves cost 2.4 %
+// of the bench frame: call 1.034 -> 1.010 ms, profiles/r09_owner_xcd_placement.md.  One group is also what
+// CNC_FLAG_OWNER_XCD_PAIRS needs: the two levels of a pair sit on complementary halves of the workgroup labels, which
+// means something only inside one launch.  Measurement switch CNC_BWD_GROUP_SPLIT=k, read when the plan is created: the
+// first k levels and the rest as two groups (an odd k cuts a pair, which costs speed only).
+inline int split_groups(uint32_t n_binned, int group_split, uint32_t first[2], uint32_t count[2])
 {
-    if (n_binned >= 4) {
-        count[0] = n_binned / 2; count[1] = n_binned - count[0];
+    if (group_split > 0 && (uint32_t)group_split < n_binned) {
+        count[0] = (uint32_t)group_split; count[1] = n_binned - count[0];
         first[0] = 0; first[1] = count[0];
         return 2;
     }
@@ -55,6 +62,8 @@ extern "C" int cnc_backward_plan_create(cnc_backward_plan** out)
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
     const char* pr = getenv("CNC_BWD_SIDE_PRIORITY");
     const int   prio = pr ? atoi(pr) : least;
+    const char* gs = getenv("CNC_BWD_GROUP_SPLIT");
+    p->group_split = gs ? atoi(gs) : 0;
     for (int i = 0; i < 2 && ok; ++i) {
         ok = hipStreamCreateWithPriority(&p->side[i], hipStreamNonBlocking, prio) == hipSuccess
              && hipEventCreateWithFlags(&p->join[i], hipEventDisableTiming) == hipSuccess;
@@ -80,11 +89,12 @@ extern "C" int cnc_backward_plan_destroy(cnc_backward_plan* p)
 
 extern "C" uint64_t cnc_grid_encode_backward_overlapped_workspace(uint32_t N, uint32_t n_binned, uint32_t level_rows)
 {
-    uint32_t first[2], count[2];
-    const int groups = split_groups(n_binned, first, count);
+    // Two groups pad their shares to 256 bytes; every split of the levels in two needs the same amount (a level's bytes
+    // do not depend on its group) and one group needs less, so this covers whatever split the call chooses.
     uint64_t total = 0;
-    for (int g = 0; g < groups; ++g)
-        total += round_up(cnc_grid_encode_backward_binned_workspace(N, count[g], level_rows));
+    if (n_binned >= 2)
+        total = round_up(cnc_grid_encode_backward_binned_workspace(N, 1, level_rows))
+                + round_up(cnc_grid_encode_backward_binned_workspace(N, n_binned - 1, level_rows));
     // the serial fallback (small N, no coarse levels) needs the whole set of bins in one piece
     const uint64_t serial = cnc_grid_encode_backward_binned_workspace(N, n_binned, level_rows);
     return total > serial ? total : serial;
@@ -110,7 +120,7 @@ extern "C" int cnc_grid_encode_backward_overlapped(cnc_backward_plan* plan, cons
     if ((uintptr_t)workspace % 16 != 0) return CNC_ERR_INVALID_VALUE;
     hipStream_t s = (hipStream_t)stream;
     uint32_t first[2], count[2];
-    const int groups = split_groups(n_binned, first, count);
+    const int groups = split_groups(n_binned, plan->group_split, first, count);
     // each group gets a share of the caller's scratch proportional to its level count (deeper bins when the caller
     // passes more than the minimum)
     if (hipEventRecord(plan->fork, s) != hipSuccess) return CNC_ERR_LAUNCH;
