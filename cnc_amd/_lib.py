@@ -197,6 +197,7 @@ CNC_FLAG_BIN_LANE_STORES = 4
 CNC_FLAG_CELL_MERGE = 8
 CNC_FLAG_CELL_CARRY = 16
 CNC_FLAG_OWNER_XCD_PAIRS = 32
+CNC_FLAG_MERGE_CONSECUTIVE = 64
 CNC_FIELD_SH_FP16 = 1
 CNC_FIELD_MFMA_F16X3 = 2
 CNC_FIELD_TWO_WAVES = 4

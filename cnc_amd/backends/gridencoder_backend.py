@@ -168,7 +168,7 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
         L = _lib.lib()
         nbytes = int(L.cnc_grid_encode_backward_binned_workspace(int(N), n_binned, level_rows))
         flags = (_lib.CNC_FLAG_STE_BINARY if ste_binary else 0) | (_lib.CNC_FLAG_BIN_LANE_STORES if _BIN_LANE_STORES else 0) \
-            | (_lib.CNC_FLAG_OWNER_XCD_PAIRS if _OWNER_XCD_PAIRS else 0)
+            | (_lib.CNC_FLAG_OWNER_XCD_PAIRS if _OWNER_XCD_PAIRS else 0) | (0 if _MERGE_TILES else _lib.CNC_FLAG_MERGE_CONSECUTIVE)
         if overlap_streams and _OVERLAP_ENABLED:
             # coarse levels on the caller's stream, the finest ones on side streams the library owns through a plan
             # object: fork, join and the split into groups live behind the C ABI (grid_encode_overlap.hip)
@@ -196,6 +196,7 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
         ptr(dy_dx), ptr(grad_inputs), ptr(binary_vxl), ptr(min_level_id),
         (_lib.CNC_FLAG_STE_BINARY if ste_binary else 0)
         | (_lib.CNC_FLAG_LEVELS_FINEST_FIRST if interleave_levels else 0)
+        | (0 if _MERGE_TILES else _lib.CNC_FLAG_MERGE_CONSECUTIVE)
         | (_lib.CNC_FLAG_CELL_MERGE if cell_merge else 0)
         | (_lib.CNC_FLAG_CELL_CARRY if cell_merge and cell_carry else 0), ptr(ste_clip_count),
         ptr(_check_sat(occ_sat, binary_vxl)), *_vb(vertex_bits, binary_vxl, 0 if min_level_id is not None else n_levels),
@@ -208,6 +209,7 @@ _PLANS = {}
 _OVERLAP_ENABLED = os.environ.get("CNC_BWD_OVERLAP", "1") != "0"   # measurement switch (profiles/)
 _BIN_LANE_STORES = os.environ.get("CNC_BWD_BIN_LANE_STORES", "0") == "1"   # measurement switch: the round-2 bin pass
 _OWNER_XCD_PAIRS = os.environ.get("CNC_BWD_OWNER_XCD_PAIRS", "0") == "1"   # measurement switch: owner waves of a level on 4 of 8 XCD labels
+_MERGE_TILES = os.environ.get("CNC_BWD_MERGE_TILES", "1") != "0"   # measurement switch: 0 = 1,024 consecutive samples per merge block
 
 
 def _plan(device, caller_stream):

@@ -51,6 +51,16 @@ __device__ __forceinline__ size_t feat_index(FeatLayout lay, uint32_t slot, uint
     return lay.ld ? (size_t)b * lay.ld + lay.col + slot * F : ((size_t)slot * N + b) * F;
 }
 
+// grid_encode.hip / grid_encode_merge.hip: the coarse call of the overlapped entry (grid_encode_overlap.hip)
+int grid_encode_backward_with_scratch(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
+                                      const int32_t* resolutions, float* grad_embeddings, uint32_t N, uint32_t D, uint32_t F,
+                                      uint32_t L, uint32_t Rb, const float* dy_dx, float* grad_inputs,
+                                      const uint8_t* binary_vxl, const int32_t* min_level_id, uint32_t flags,
+                                      const uint32_t* ste_clip_count, const int32_t* occ_sat, const uint32_t* vertex_bits,
+                                      const int32_t* vertex_bit_offsets, uint32_t grad_ld, uint32_t grad_col, void* stream,
+                                      uint16_t* tile_order);
+uint64_t merge_tile_order_bytes(uint32_t N);
+
 inline int launch_status()
 {
     return hipGetLastError() == hipSuccess ? CNC_OK : CNC_ERR_LAUNCH;

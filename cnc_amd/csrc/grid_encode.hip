@@ -791,6 +791,10 @@ struct EncArgs {
     const uint32_t* clip_count = nullptr;   // backward + STE only
     const int32_t*  sat = nullptr;          // optional summed-volume table of the occupancy grid
     FeatLayout      lay{0, 0};              // where outputs (forward) / gradients (backward) live
+    // k_grid_encode_bwd_merge (grid_encode_merge.hip): CNC_FLAG_MERGE_CONSECUTIVE, and scratch of merge_tile_order_bytes(N)
+    // for the segment order of its depth-ranked tiles (nullptr: consecutive samples)
+    bool            merge_consecutive = false;
+    uint16_t*       tile_order = nullptr;
 };
 
 template <uint32_t D, uint32_t F, bool VXL, bool STE>
@@ -808,7 +812,8 @@ bool launch_bwd_cells(const CellsArgs& a, uint32_t D, uint32_t F, bool ste, hipS
 // grid_encode_merge.hip
 void launch_bwd_merge(const float* grad, const float* inputs, const float* emb, const int32_t* offsets,
                       const int32_t* resolutions, float* grad_emb, uint32_t N, uint32_t L,
-                      const uint32_t* clip_count, FeatLayout lay, bool ste, hipStream_t s);
+                      const uint32_t* clip_count, FeatLayout lay, bool ste, bool consecutive, uint16_t* tile_order,
+                      hipStream_t s);
 
 template <uint32_t D, uint32_t F, bool VXL, bool STE>
 static void launch_bwd(const EncArgs& a)
@@ -817,7 +822,7 @@ static void launch_bwd(const EncArgs& a)
         // coarse half of a binned call: runs merged across the rays of a 1024-sample block
         if (a.lay.finest_first && !a.mli && (uint64_t)div_up(a.N, 256) * a.L < (1ull << 31)) {
             launch_bwd_merge(a.grad, a.inputs, a.emb, a.offsets, a.resolutions, a.out, a.N, a.L, a.clip_count,
-                             a.lay, STE, a.stream);
+                             a.lay, STE, a.merge_consecutive, a.tile_order, a.stream);
             return;
         }
     }
@@ -930,16 +935,18 @@ extern "C" int cnc_grid_encode_forward(const float* inputs, const float* embeddi
     return rc != CNC_OK ? rc : launch_status();
 }
 
-extern "C" int cnc_grid_encode_backward(const float* grad, const float* inputs,
-                                        const float* embeddings, const int32_t* offsets,
-                                        const int32_t* resolutions, float* grad_embeddings,
-                                        uint32_t N, uint32_t D, uint32_t F, uint32_t L,
-                                        uint32_t Rb, const float* dy_dx, float* grad_inputs,
-                                        const uint8_t* binary_vxl, const int32_t* min_level_id,
-                                        uint32_t flags, const uint32_t* ste_clip_count,
-                                        const int32_t* occ_sat, const uint32_t* vertex_bits,
-                                        const int32_t* vertex_bit_offsets, uint32_t grad_ld,
-                                        uint32_t grad_col, void* stream)
+// cnc_grid_encode_backward, plus the scratch a caller inside the library may lend the merge kernel
+// (merge_tile_order_bytes(N) bytes for the segment order of the depth-ranked tiles, or nullptr)
+int cnc::grid_encode_backward_with_scratch(const float* grad, const float* inputs,
+                                           const float* embeddings, const int32_t* offsets,
+                                           const int32_t* resolutions, float* grad_embeddings,
+                                           uint32_t N, uint32_t D, uint32_t F, uint32_t L,
+                                           uint32_t Rb, const float* dy_dx, float* grad_inputs,
+                                           const uint8_t* binary_vxl, const int32_t* min_level_id,
+                                           uint32_t flags, const uint32_t* ste_clip_count,
+                                           const int32_t* occ_sat, const uint32_t* vertex_bits,
+                                           const int32_t* vertex_bit_offsets, uint32_t grad_ld,
+                                           uint32_t grad_col, void* stream, uint16_t* tile_order)
 {
     if ((dy_dx == nullptr) != (grad_inputs == nullptr)) return CNC_ERR_INVALID_VALUE;   // both or neither
     if (N == 0 || L == 0) return CNC_OK;
@@ -950,6 +957,8 @@ extern "C" int cnc_grid_encode_backward(const float* grad, const float* inputs,
               binary_vxl ? occ_sat : nullptr,
               FeatLayout{grad_ld, grad_col, (flags & CNC_FLAG_LEVELS_FINEST_FIRST) ? 1u : 0u}};
     if (!layout_ok(a.lay, F, L)) return CNC_ERR_INVALID_VALUE;
+    a.merge_consecutive = (flags & CNC_FLAG_MERGE_CONSECUTIVE) != 0;
+    a.tile_order = tile_order;
     if (binary_vxl && vertex_bits && vertex_bit_offsets) { a.lay.vbits = vertex_bits; a.lay.vboff = vertex_bit_offsets; }
     int rc = CNC_OK;
     bool done = false;
@@ -963,6 +972,22 @@ extern "C" int cnc_grid_encode_backward(const float* grad, const float* inputs,
         rc = launch_input_backward(grad, dy_dx, grad_inputs, N, D, F, L, FeatLayout{grad_ld, grad_col},
                                    (hipStream_t)stream);
     return rc != CNC_OK ? rc : launch_status();
+}
+
+extern "C" int cnc_grid_encode_backward(const float* grad, const float* inputs,
+                                        const float* embeddings, const int32_t* offsets,
+                                        const int32_t* resolutions, float* grad_embeddings,
+                                        uint32_t N, uint32_t D, uint32_t F, uint32_t L,
+                                        uint32_t Rb, const float* dy_dx, float* grad_inputs,
+                                        const uint8_t* binary_vxl, const int32_t* min_level_id,
+                                        uint32_t flags, const uint32_t* ste_clip_count,
+                                        const int32_t* occ_sat, const uint32_t* vertex_bits,
+                                        const int32_t* vertex_bit_offsets, uint32_t grad_ld,
+                                        uint32_t grad_col, void* stream)
+{
+    return grid_encode_backward_with_scratch(grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F, L, Rb,
+                                             dy_dx, grad_inputs, binary_vxl, min_level_id, flags, ste_clip_count, occ_sat,
+                                             vertex_bits, vertex_bit_offsets, grad_ld, grad_col, stream, nullptr);
 }
 
 #define CNC_F_SWITCH(F, CALL)                         \

@@ -667,11 +667,20 @@ extern "C" int cnc_grid_encode_backward_binned(const float* grad, const float* i
     if (n_binned > L) return CNC_ERR_INVALID_VALUE;
     // what is not binned goes through the atomic kernel, with the same arguments
     if (L - n_binned > 0) {
-        const int rc = cnc_grid_encode_backward(grad, inputs, embeddings, offsets, resolutions,
-                                                grad_embeddings, N, D, F, L - n_binned, 0, nullptr,
-                                                nullptr, nullptr, nullptr,
-                                                flags | CNC_FLAG_LEVELS_FINEST_FIRST, ste_clip_count,
-                                                nullptr, nullptr, nullptr, grad_ld, grad_col, stream);
+        // scratch beyond what the bins were asked for (what cnc_grid_encode_backward_overlapped_workspace adds, when that
+        // entry hands a call on as a whole): its tail holds the segment order of the merge kernel's depth-ranked tiles
+        uint16_t*      tile_order = nullptr;
+        const uint64_t order_bytes = merge_tile_order_bytes(N);
+        const uint64_t bins_bytes = (cnc_grid_encode_backward_binned_workspace(N, n_binned, level_rows) + 255) / 256 * 256;
+        if (workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= bins_bytes + order_bytes) {
+            workspace_bytes = (workspace_bytes - order_bytes) / 256 * 256;
+            tile_order = reinterpret_cast<uint16_t*>((char*)workspace + workspace_bytes);
+        }
+        const int rc = grid_encode_backward_with_scratch(grad, inputs, embeddings, offsets, resolutions,
+                                                         grad_embeddings, N, D, F, L - n_binned, 0, nullptr,
+                                                         nullptr, nullptr, nullptr,
+                                                         flags | CNC_FLAG_LEVELS_FINEST_FIRST, ste_clip_count,
+                                                         nullptr, nullptr, nullptr, grad_ld, grad_col, stream, tile_order);
         if (rc != CNC_OK) return rc;
     }
     if (n_binned == 0) return CNC_OK;

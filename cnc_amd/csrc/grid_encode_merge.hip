@@ -7,7 +7,8 @@
 // 0.93-0.96.  This kernel takes MB = 1024 (or 512) samples per block, chains the runs of equal cells through a
 // small LDS hash table and sends ONE set of atomics per distinct cell — the coarse levels are bound by the
 // memory-side atomic units (docs/engineering_log.md §4.2b), so the number of atomic instructions is what their time was
-// made of.
+// made of.  Which 1024 samples a block takes: consecutive ones, or (levels of R >= kMergeTileMinRes, callers with scratch
+// for the order) a depth slab of ~26 neighbouring rays, which merges as 4096 consecutive samples would: k_merge_tile_order.
 //
 // How it got here (9 coarse levels of the bench grid, ms per 2^20 marched samples; k_grid_encode_bwd: 0.523):
 //   * first version, 8 stored weights per sample, block size 256 / 384 / 512 / 640 / 768 / 1024:
@@ -33,14 +34,137 @@ namespace cnc {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// window and segment of the depth-ranked tiles of the 1024-sample blocks (k_merge_tile_order), in samples
+#ifndef CNC_MERGE_TILE_WINDOW
+#define CNC_MERGE_TILE_WINDOW 8192
+#endif
+#ifndef CNC_MERGE_TILE_SEGMENT
+#define CNC_MERGE_TILE_SEGMENT 8
+#endif
+constexpr uint32_t kMergeTileWindow = CNC_MERGE_TILE_WINDOW, kMergeTileSegment = CNC_MERGE_TILE_SEGMENT;
+// Levels below this resolution keep consecutive samples.  A tile of ~32 rays x 32 samples spans a handful of their
+// cells: fewer cells than the block has waves, each a chain of hundreds of samples that ONE wave walks while the others
+// idle.  Ten copies of one level of the bench grid, middle chunk, ms consecutive -> ranked (order from
+// k_merge_tile_order): R = 18 0.224 -> 0.462, 24 0.216 -> 0.420, 32 0.227 -> 0.378, 44 0.253 -> 0.333, 60 0.340 -> 0.317,
+// 82 0.376 -> 0.322, 113 0.458 -> 0.336, 155 0.619 -> 0.400, 214 0.859 -> 0.590, 296 1.190 -> 0.884.
+#ifndef CNC_MERGE_TILE_MIN_RES
+#define CNC_MERGE_TILE_MIN_RES 52
+#endif
+constexpr uint32_t kMergeTileMinRes = CNC_MERGE_TILE_MIN_RES;
+
+// Depth-ranked sample tiles.  Two samples of one ray never share a cell beyond one run: all merging beyond runs happens
+// ACROSS rays, and 1024 consecutive samples are the full depth of only 3-4 rays.  So a block of the merge kernel need not
+// take consecutive samples.  A window of TW consecutive samples is cut into TW / TS segments of TS consecutive samples,
+// this kernel (one block per window, one segment per thread) orders the segments by depth along the rays, and each
+// block of the window takes a slab of 1024 / TS of them: the same 1024 LDS slots hold a thin depth slab of ~26
+// neighbouring rays, which merges as a 4,096-sample block would (0.57 of the distinct cells of the ten coarse levels on
+// the bench frame's middle chunk), at the same LDS, block size and occupancy.  profiles/r10_merge_tiles.md.
+//   * depth of a segment = its middle sample . axis; axis = the median-length one of three differences of neighbouring
+//     samples of the window (a pair that straddles a ray boundary does not decide).  It only has to order depth.
+//   * key = 22 bits of the depth in a monotonic integer form | segment index: a total order whatever the inputs are
+//     (ties, a zero axis, NaN and points outside the cube: one sentinel, the index decides), so the tiling is a
+//     permutation of the window's samples and a pure function of the inputs.  Segments past N rank last; they are
+//     written like any other, and the merge kernel drops their samples because their indices are >= N.
+//   * the window splits itself: the depths of consecutive segments fall once per ray boundary, so the descents count the
+//     window's rays.  The best tile is about as many rays as samples per ray, i.e. a (sub-)window of ~32 ray lengths:
+//     the window is cut into 1, 2, 4 ... TW / 1024 equal sub-windows, whichever is nearest, and ranked inside each.
+//     With TW / 1024 sub-windows a block holds exactly the samples of the consecutive tiling.
+//   * the order is a bitonic network on one key per thread (every merge ascending: first step against the mirrored
+//     partner), shuffles inside a wave and double-buffered LDS words across waves, stopped at the sub-window size.
+// order[window * TW / TS + i] = the segment (16 bits) at place i of the window's order.
+template <uint32_t TW, uint32_t TS>
+__global__ __launch_bounds__(1024) void k_merge_tile_order(const float* __restrict__ inputs, uint32_t N,
+                                                           uint16_t* __restrict__ order)
+{
+    constexpr uint32_t MB = 1024;
+    __shared__ uint32_t s_sort[2 * MB], s_cnt[MB / 64];
+    const uint32_t base = blockIdx.x * TW;
+    constexpr uint32_t kSegs = TW / TS, kTiles = TW / MB;
+    constexpr uint32_t kPastEnd = 0x3FFFFFu, kUnusable = 0x3FFFFEu;
+    static_assert(MB == 1024 && kSegs <= MB && kSegs * TS == TW && kTiles * MB == TW, "one segment per thread, 10 index bits");
+    static_assert(TS >= 1 && TS <= 16 && (TS & (TS - 1)) == 0 && (kTiles & (kTiles - 1)) == 0 && kTiles <= 16,
+                  "a tile is at least one wave of segments");
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n_in = min(N - base, TW), n_seg = div_up(n_in, TS);
+    float ax[3] = {0.0f, 0.0f, 0.0f};
+    if (n_in >= 2) {
+        float cand[3][3], len[3];
+#pragma unroll
+        for (uint32_t k = 0; k < 3; k++) {
+            const size_t a = (size_t)base + min(k * 11u, n_in - 2);
+#pragma unroll
+            for (uint32_t d = 0; d < 3; d++) cand[k][d] = inputs[(a + 1) * 3 + d] - inputs[a * 3 + d];
+            len[k] = (cand[k][0] * cand[k][0] + cand[k][1] * cand[k][1]) + cand[k][2] * cand[k][2];
+        }
+        const bool m0 = len[0] <= len[1] ? (len[1] > len[2] && len[0] > len[2]) : len[0] <= len[2];
+        const bool m2 = len[0] <= len[1] ? (len[1] > len[2] && len[0] <= len[2]) : (len[0] > len[2] && len[1] <= len[2]);
+#pragma unroll
+        for (uint32_t d = 0; d < 3; d++) ax[d] = m0 ? cand[0][d] : m2 ? cand[2][d] : cand[1][d];
+    }
+    uint32_t q = kPastEnd;
+    if (tid < n_seg) {
+        const size_t s = (size_t)base + min(tid * TS + TS / 2, n_in - 1);
+        const float  x0 = inputs[s * 3], x1 = inputs[s * 3 + 1], x2 = inputs[s * 3 + 2];
+        const float  dep = (x0 * ax[0] + x1 * ax[1]) + x2 * ax[2];
+        const bool   usable = x0 >= 0 && x0 <= 1 && x1 >= 0 && x1 <= 1 && x2 >= 0 && x2 <= 1 && dep == dep;
+        uint32_t     u = __float_as_uint(dep);
+        u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;            // monotonic in the float's value
+        q = usable ? min(u >> 10, kUnusable - 1) : kUnusable;
+    }
+    // rays of the window: descents of the depth in segment order (pairs across a wave boundary are not looked at)
+    const uint32_t qp = (uint32_t)__shfl_up((int)q, 1);
+    const uint64_t db = __ballot(lane != 0 && q < qp && qp < kUnusable);
+    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(db);
+    uint32_t key = q << 10 | tid;
+#pragma unroll
+    for (uint32_t k = 2; k <= 64; k <<= 1) {
+        uint32_t o = (uint32_t)__shfl_xor((int)key, (int)(k - 1));
+        key = (lane & (k >> 1)) == 0 ? min(key, o) : max(key, o);
+#pragma unroll
+        for (uint32_t s = k >> 2; s >= 1; s >>= 1) {
+            o = (uint32_t)__shfl_xor((int)key, (int)s);
+            key = (lane & s) == 0 ? min(key, o) : max(key, o);
+        }
+    }
+    __syncthreads();
+    uint32_t n_rays = 1;
+#pragma unroll
+    for (uint32_t w = 0; w < MB / 64; w++) n_rays += s_cnt[w];
+    // sub-windows: kSegs n_rays / (32 n_seg) of them would hold 32 ray lengths each; the nearest power of two
+    const uint32_t have = n_rays * kSegs * 5u, want = n_seg * 32u * 7u;
+    uint32_t       n_sub = have < want ? 1u : have < 2 * want ? 2u : have < 4 * want ? 4u : have < 8 * want ? 8u : 16u;
+    n_sub = min(n_sub, kTiles);
+    const uint32_t sub_segs = kSegs / n_sub;                   // >= MB / TS >= 64: block-uniform
+    uint32_t p = 0;
+    auto cross = [&](uint32_t mask, uint32_t bit) {
+        s_sort[p * MB + tid] = key;
+        __syncthreads();
+        const uint32_t o = s_sort[p * MB + (tid ^ mask)];
+        key = (tid & bit) == 0 ? min(key, o) : max(key, o);
+        p ^= 1;                                                // (the next write must not meet this step's late readers)
+    };
+    for (uint32_t k = 128; k <= sub_segs; k <<= 1) {
+        cross(k - 1, k >> 1);
+        for (uint32_t s = k >> 2; s >= 64; s >>= 1) cross(s, s);
+#pragma unroll
+        for (uint32_t s = 32; s >= 1; s >>= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)key, (int)s);
+            key = (lane & s) == 0 ? min(key, o) : max(key, o);
+        }
+    }
+    if (tid < kSegs) order[(size_t)blockIdx.x * kSegs + tid] = (uint16_t)(key & (MB - 1));
+}
+
 // MB = samples (= threads) per block, a multiple of 64: 1024 for the frames of the bench (more samples per block merge
 // more), 512 when the whole launch is only a few rounds of 1024-sample blocks — a training batch of 2^18 samples x 11
 // levels is 2.8 k such blocks on 512 block slots, and ran 4x less efficiently than the 2^20-sample chunks.
-template <bool STE, uint32_t MB>
+// TW, TS: window and segment of the depth-ranked tiles (above), TW = 0: MB consecutive samples per block.
+template <bool STE, uint32_t MB, uint32_t TW, uint32_t TS>
 __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     const float* __restrict__ grad, const float* __restrict__ inputs, const float* __restrict__ emb,
     const int32_t* __restrict__ offsets, const int32_t* __restrict__ resolutions,
-    float* __restrict__ grad_emb, uint32_t N, const uint32_t* __restrict__ clip_count, FeatLayout lay)
+    float* __restrict__ grad_emb, uint32_t N, const uint32_t* __restrict__ clip_count, FeatLayout lay,
+    const uint16_t* __restrict__ tile_order)
 {
     constexpr uint32_t kMB = MB;
     constexpr uint32_t kMW = kMB / 64;        // waves per block
@@ -68,11 +192,20 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     const uint32_t n_slots = lay.n_slots;
     const uint32_t chunk = blockIdx.x / n_slots;
     const uint32_t slot = n_slots - 1 - blockIdx.x % n_slots;
-    const uint32_t b = chunk * kMB + tid;
+    uint32_t       b = chunk * kMB + tid;
     const uint32_t off = (uint32_t)offsets[slot];
     const uint32_t hs = (uint32_t)offsets[slot + 1] - off;
     const uint32_t R = (uint32_t)resolutions[slot];
 
+    if constexpr (TW != 0) {
+        // block = (window, tile, level slot): the order of the window's segments comes from k_merge_tile_order
+        if (R >= kMergeTileMinRes) {
+            constexpr uint32_t kTiles = TW / kMB, kSegs = TW / TS;
+            const uint32_t win = chunk / kTiles, at = chunk % kTiles * (kMB / TS) + tid / TS;
+            // (a segment past N, of the last window only, gives b >= N: no sample, as in a consecutive block's tail)
+            b = win * TW + (uint32_t)tile_order[(size_t)win * kSegs + at] * TS + tid % TS;
+        }
+    }
     for (uint32_t i = tid; i < kMSlots; i += kMB) h_slot[i] = 0;
     l_head[tid] = END;
 
@@ -307,24 +440,43 @@ __global__ __launch_bounds__(256) void k_grid_encode_bwd_wide(
     }
 }
 
+// scratch for the segment order of a call's windows (k_merge_tile_order), a multiple of 256 bytes
+uint64_t merge_tile_order_bytes(uint32_t N)
+{
+    return ((uint64_t)div_up(N, kMergeTileWindow) * (kMergeTileWindow / kMergeTileSegment) * 2 + 255) / 256 * 256;
+}
+
 // grid_encode.hip launches this for the coarse half of a binned call (D = 3, F = 8)
 void launch_bwd_merge(const float* grad, const float* inputs, const float* emb, const int32_t* offsets,
                       const int32_t* resolutions, float* grad_emb, uint32_t N, uint32_t L,
-                      const uint32_t* clip_count, FeatLayout lay, bool ste, hipStream_t s)
+                      const uint32_t* clip_count, FeatLayout lay, bool ste, bool consecutive, uint16_t* tile_order,
+                      hipStream_t s)
 {
     lay.n_slots = L;
     // (round 3 measured this kernel with padded dynamic LDS — one block per CU, to leave room for the owner waves of
     // the binned levels: slower; the switch is gone, the library keeps no state between calls)
     const bool small = (uint64_t)div_up(N, 1024u) * L < 4096u;       // fewer than eight rounds of 1024-sample blocks
+#define CNC_MERGE_GO(ST, MBS, W, S)                                                                                \
+    hipLaunchKernelGGL((k_grid_encode_bwd_merge<ST, MBS, W, S>), dim3(div_up(N, MBS) * L), dim3(MBS), 0, s, grad, inputs, \
+                       emb, offsets, resolutions, grad_emb, N, clip_count, lay, tile_order)
     if (small) {
-        const dim3 grid(div_up(N, 512u) * L);
-        if (ste) hipLaunchKernelGGL((k_grid_encode_bwd_merge<true, 512>), grid, dim3(512), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
-        else hipLaunchKernelGGL((k_grid_encode_bwd_merge<false, 512>), grid, dim3(512), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
+        // training batches of unrelated short rays: consecutive samples
+        if (ste) CNC_MERGE_GO(true, 512u, 0u, 0u);
+        else CNC_MERGE_GO(false, 512u, 0u, 0u);
+    } else if (consecutive || tile_order == nullptr) {
+        // CNC_FLAG_MERGE_CONSECUTIVE (the tiling before the depth-ranked tiles, for comparisons inside one build), or a
+        // caller without scratch for the segment order
+        if (ste) CNC_MERGE_GO(true, 1024u, 0u, 0u);
+        else CNC_MERGE_GO(false, 1024u, 0u, 0u);
     } else {
-        const dim3 grid(div_up(N, 1024u) * L);
-        if (ste) hipLaunchKernelGGL((k_grid_encode_bwd_merge<true, 1024>), grid, dim3(1024), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
-        else hipLaunchKernelGGL((k_grid_encode_bwd_merge<false, 1024>), grid, dim3(1024), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
+        // same grid: block id / L = window * (tiles per window) + tile, and a tile with a sample below N exists exactly
+        // where a consecutive block does
+        hipLaunchKernelGGL((k_merge_tile_order<kMergeTileWindow, kMergeTileSegment>), dim3(div_up(N, kMergeTileWindow)),
+                           dim3(1024), 0, s, inputs, N, tile_order);
+        if (ste) CNC_MERGE_GO(true, 1024u, kMergeTileWindow, kMergeTileSegment);
+        else CNC_MERGE_GO(false, 1024u, kMergeTileWindow, kMergeTileSegment);
     }
+#undef CNC_MERGE_GO
     // (a few blocks per level slot: they leave at once unless the level is one of those, and the launch is all the call
     // pays for it.  On such a level the 4096 threads walk the samples grid-stride, 2^D F atomics each: slow for millions
     // of samples, but no encoder CNC builds has a level of R > 2^16, and the merge kernel keeps its speed)

@@ -15,6 +15,7 @@
 #include <new>
 
 #include "cnc_hip.h"
+#include "common.hpp"      // grid_encode_backward_with_scratch, merge_tile_order_bytes
 
 struct cnc_backward_plan {
     hipStream_t side[2];
@@ -97,7 +98,8 @@ extern "C" uint64_t cnc_grid_encode_backward_overlapped_workspace(uint32_t N, ui
                 + round_up(cnc_grid_encode_backward_binned_workspace(N, n_binned - 1, level_rows));
     // the serial fallback (small N, no coarse levels) needs the whole set of bins in one piece
     const uint64_t serial = cnc_grid_encode_backward_binned_workspace(N, n_binned, level_rows);
-    return total > serial ? total : serial;
+    // behind the bins: the segment order of the coarse call's depth-ranked tiles (k_merge_tile_order), 2 KB per window
+    return round_up(total > serial ? total : serial) + cnc::merge_tile_order_bytes(N);
 }
 
 extern "C" int cnc_grid_encode_backward_overlapped(cnc_backward_plan* plan, const float* grad, const float* inputs,
@@ -119,6 +121,13 @@ extern "C" int cnc_grid_encode_backward_overlapped(cnc_backward_plan* plan, cons
         return CNC_ERR_INVALID_VALUE;
     if ((uintptr_t)workspace % 16 != 0) return CNC_ERR_INVALID_VALUE;
     hipStream_t s = (hipStream_t)stream;
+    // a caller that brought all the scratch asked for lends its tail to the coarse call; with less, the bins keep all of
+    // it and the merge kernel's blocks take consecutive samples
+    uint16_t* tile_order = nullptr;
+    if (workspace_bytes >= cnc_grid_encode_backward_overlapped_workspace(N, n_binned, level_rows)) {
+        workspace_bytes = (workspace_bytes - cnc::merge_tile_order_bytes(N)) / kAlign * kAlign;
+        tile_order = reinterpret_cast<uint16_t*>((char*)workspace + workspace_bytes);
+    }
     uint32_t first[2], count[2];
     const int groups = split_groups(n_binned, plan->group_split, first, count);
     // each group gets a share of the caller's scratch proportional to its level count (deeper bins when the caller
@@ -142,9 +151,10 @@ extern "C" int cnc_grid_encode_backward_overlapped(cnc_backward_plan* plan, cons
         if (hipEventRecord(plan->join[g], plan->side[g]) != hipSuccess) return CNC_ERR_LAUNCH;
     }
     // the coarse levels fill in next to the (longer) bin + owner passes, on the caller's stream
-    const int rc0 = cnc_grid_encode_backward(grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F, coarse,
-                                             0, nullptr, nullptr, nullptr, nullptr, flags | CNC_FLAG_LEVELS_FINEST_FIRST,
-                                             ste_clip_count, nullptr, nullptr, nullptr, grad_ld, grad_col, stream);
+    const int rc0 = cnc::grid_encode_backward_with_scratch(grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F,
+                                                      coarse, 0, nullptr, nullptr, nullptr, nullptr,
+                                                      flags | CNC_FLAG_LEVELS_FINEST_FIRST, ste_clip_count, nullptr, nullptr,
+                                                      nullptr, grad_ld, grad_col, stream, tile_order);
     for (int g = 0; g < groups; ++g)
         if (hipStreamWaitEvent(s, plan->join[g], 0) != hipSuccess) return CNC_ERR_LAUNCH;
     return rc0 != CNC_OK ? rc0 : rc;

@@ -66,6 +66,16 @@ extern "C" {
                                        * (grid_encode_binned.hip, owner_slab).  Measured: the owner pass's read requests
                                        * fall by 2 %, its time not at all — off by default */
 
+#define CNC_FLAG_MERGE_CONSECUTIVE 64u /* measurement switch for cnc_grid_encode_backward_overlapped (same result to fp32
+                                       * summation order): every 1,024-sample block of k_grid_encode_bwd_merge takes
+                                       * consecutive samples, the tiling before the depth-ranked tiles
+                                       * (grid_encode_merge.hip, k_merge_tile_order).  The tiles need scratch for the segment
+                                       * order: cnc_grid_encode_backward_overlapped_workspace asks for it (and
+                                       * the serial entry that call hands small N to finds it: _binned lends the tail
+                                       * of a workspace of at least its own ask rounded up to 256 bytes plus that
+                                       * order); cnc_grid_encode_backward has none, and its blocks and those of a
+                                       * _binned call with only its own ask take consecutive samples either way */
+
 #define CNC_FLAG_CELL_MERGE 8u   /* cnc_grid_encode_backward (same result to fp32 summation order): the points of a
                                  * 1024-point block that fall into one cell of a level are summed in LDS and every
                                  * distinct (cell, corner row) goes out as ONE atomic (grid_encode_cells.hip) — with or

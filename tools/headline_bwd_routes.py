@@ -8,7 +8,10 @@ STE) through each scatter route the library has — what `profiles/<tag>_headlin
     --route carry     ... with the x-neighbour carry (a vertex shared by two cells of the block is written once)
     --levels K        only the K coarsest levels (10 = the ones the product route gives the merge kernel), not for product
     --count           no kernel: distinct cells per group of 1,024 / 2,048 / 4,096 consecutive samples, per level — what a
-                      block that carried its cell table across 2 / 4 blocks would send (an upper bound on what it saves)
+                      block that carried its cell table across 2 / 4 blocks would send (an upper bound on what it saves) —
+                      and per 1,024-sample block of the merge kernel's depth-ranked tiles (tools/merge_tiles.py, the
+                      kernel's rule in torch; --tiles W,S: another window / segment than the kernel's 8192,8)
+    --chunk WHICH     first | quarter | middle (default, bench.probe_chunk_of): which chunk of the frame
 
 One route per process so that a counter pass (rocprofv3 --pmc TCC_ATOMIC_sum) sees only that route's kernels; prints the
 time per call (HIP events, median of 20).   tools/collect_profiles.sh <tag> routes  runs all of them."""
@@ -24,13 +27,25 @@ dev = torch.device("cuda:0")
 w = bench.build_workload(dev, 0)
 box = {}
 bench.march_frame(w, box)
-xs = bench.probe_chunk_of(box["ex"]["positions"]).contiguous()
+which = sys.argv[sys.argv.index("--chunk") + 1] if "--chunk" in sys.argv else "middle"
+pos = box["ex"]["positions"]
+if which == "middle":
+    xs = bench.probe_chunk_of(pos).contiguous()
+else:
+    at = {"first": 0, "quarter": pos.shape[0] // bench.CHUNK // 4}[which] * bench.CHUNK
+    xs = pos[at:at + bench.CHUNK].contiguous()
 n = xs.shape[0]
 torch.cuda.synchronize()
 
 if "--count" in sys.argv:
+    from tools import merge_tiles
     res = synthetic.RES_16L
     x = xs.double().cpu().numpy()
+    TW, TS = (int(v) for v in sys.argv[sys.argv.index("--tiles") + 1].split(",")) if "--tiles" in sys.argv else (8192, 8)
+    blocks = merge_tiles.block_samples(xs, TW, TS)
+    subs = [merge_tiles.window_order(xs.cpu(), b, n, TW, TS)[1] for b in range(0, n, TW)]
+    print(f"chunk {which}: {n} samples, windows of {TW} by their sub-window count:",
+          json.dumps({k: subs.count(k) for k in sorted(set(subs))}), flush=True)
     rows = []
     for l, R in enumerate(res):
         # the cell of a sample as Corners::setup floors it, floor(x (R - 2) + 0.5) (in float64 here: flooring differs from
@@ -43,11 +58,15 @@ if "--count" in sys.argv:
             k = key[: n // G * G].reshape(-1, G)
             k = np.sort(k, axis=1)
             per[G] = int((np.diff(k, axis=1) != 0).sum() + k.shape[0])
+        # (levels below the kernel's kMergeTileMinRes keep consecutive blocks; --tiles-all-levels: ranked everywhere)
+        per["tiles"] = merge_tiles.cells_per_block(torch.as_tensor(key), blocks) \
+            if R >= merge_tiles.MIN_RES or "--tiles-all-levels" in sys.argv else per[1024]
         rows.append((l, R, runs, per))
         print(f"level {l:2d} R={R:5d}: runs {runs:8d} | distinct cells per 256: {per[256]:8d}  1,024: {per[1024]:8d}  "
-              f"2,048: {per[2048]:8d}  4,096: {per[4096]:8d}", flush=True)
-    tot = {G: sum(r[3][G] for r in rows[:10]) for G in (256, 1024, 2048, 4096)}
-    print("coarse ten levels, cells summed:", json.dumps(tot), "runs:", sum(r[2] for r in rows[:10]))
+              f"2,048: {per[2048]:8d}  4,096: {per[4096]:8d}  ranked tiles {TW}/{TS}: {per['tiles']:8d}", flush=True)
+    tot = {G: sum(r[3][G] for r in rows[:10]) for G in (256, 1024, 2048, 4096, "tiles")}
+    print("coarse ten levels, cells summed:", json.dumps(tot), "runs:", sum(r[2] for r in rows[:10]),
+          "ranked tiles over consecutive 1,024: %.3f" % (tot["tiles"] / tot[1024]))
     sys.exit(0)
 
 out = torch.empty((L, n, F), device=dev)
