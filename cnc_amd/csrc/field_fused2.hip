@@ -9,18 +9,24 @@
 //   * fill: thread (sample i = tid & 31, window q = tid >> 5) computes the 8 columns [8 q, 8 q + 8) of sample i's row of
 //     the current 32-column chunk — half the gather work per wave — into a double-buffered chunk tile (two half planes:
 //     x = hi + lo), one workgroup barrier per chunk;
-//   * matrix products on v_mfma_f32_16x16x32_f16, three per term as in field_fused.hip (hi hi + hi lo + lo hi).  A layer
-//     whose width is H is split by COLUMNS: wave w owns output columns [w H / 2, (w + 1) H / 2) of all 32 rows =
+//   * matrix products on v_mfma_f32_16x16x32_f16, three per term: every operand is split x = hi + lo, hi = half(x),
+//     lo = half(x - hi) (22 of fp32's 24 significand bits; the weights are scaled by 2^8 first so that their lo parts
+//     stay normal numbers) and x w ~= hi_x hi_w + hi_x lo_w + lo_x hi_w, accumulated in fp32 by the MFMA (the dropped
+//     lo_x lo_w is 2^-22 relative): ~5e-7 per term against fp32 rounding's 6e-8, two orders below north_star's 1e-4, on
+//     the real matrix pipe — v_mfma_f32_32x32x2_f32 of the exact kernel runs at the f32 VECTOR rate and does not overlap
+//     with the gather's vector work (docs/engineering_log.md, round 4);
+//   * a layer whose width is H is split by COLUMNS: wave w owns output columns [w H / 2, (w + 1) H / 2) of all 32 rows =
 //     2 row blocks x H / 32 column blocks x 4 = 40 accumulator registers at H = 160, and loads only its half of the
-//     weight fragments (the workgroup reads each fragment once, as before).  The narrow layers (H -> 1 + geo, H -> 3)
-//     are split by ROWS: wave w owns row block w and every column block;
+//     weight fragments (the workgroup reads each fragment once).  The narrow layers (H -> 1 + geo, H -> 3) are split by
+//     ROWS: wave w owns row block w and every column block;
 //   * activations go between the layers through the workgroup's LDS planes (the A operand needs all K columns of a
 //     row: both waves' halves), two barriers per layer.
 // Half the accumulators and half the weight registers per wave: three to four waves per SIMD instead of two.
 //
 // Values: the features are those of k_grid_encode_fwd_bits (bit-identical: same Corners / fmaf chain); the layers are
-// the three-product scheme of field_fused.hip with a different summation order (k in steps of 32 instead of 16).
-// The fp16 range guard (field_fused_common.hpp) covers every value that is split into halves here.
+// the three-product scheme above, k in steps of 32, checked against the op chain in tests/test_gpu_field_fused.py at 2e-5.
+// Activations are assumed below fp16's 65504: the fp16 range guard (field_fused_common.hpp) covers every value that is
+// split into halves here.
 #include "field_mma.hpp"
 
 #include <type_traits>
@@ -362,12 +368,11 @@ struct PackAllArgs {
     const float* W[5];
     const float* b[5];
     uint32_t     H[5], K[5], ldw[5];
-    uint32_t     nt32[5], nk8[5], nk16[5];      // fp32 fragments (and biases), 32x32x16 half fragments
+    uint32_t     nt32[5], nk8[5];               // fp32 fragments (and biases)
     uint32_t     ncb[5], nk32[5], k_gap[5];     // 16x16x32 half fragments
     uint32_t     tflags[5], src_off[5];
     float*       Wp[5];
     float*       Bp[5];
-    half_t*      Wp16[5];                       // nullable
     half_t*      Wq16[5];                       // nullable
     float*       row0;                          // layer 1's (base.2) row 0, padded to row0_len
     uint32_t     row0_len;
@@ -376,8 +381,8 @@ struct PackAllArgs {
     uint32_t     pack_id;
 };
 
-// All five layers in every fragment order the fused kernels read, in ONE launch (the per-layer entry points cost ten
-// launches per optimiser step).
+// All five layers in both fragment orders the fused kernels read, in ONE launch (per-layer launches cost ten per
+// optimiser step).
 __global__ __launch_bounds__(256) void k_field_pack_all(PackAllArgs a)
 {
     uint32_t l = 0;
@@ -386,7 +391,7 @@ __global__ __launch_bounds__(256) void k_field_pack_all(PackAllArgs a)
     const uint32_t idx = (blockIdx.x - a.first_block[l]) * 256 + threadIdx.x;
     const float*   W = a.W[l];
     const uint32_t H = a.H[l], K = a.K[l], ldw = a.ldw[l];
-    if (a.Wp[l]) {   // fp32 fragments, biases, row 0 (k_field_pack_layer)
+    if (a.Wp[l]) {   // fp32 fragments (float4 (kb NT + t) 64 + lane = W[32 t + (lane & 31)][8 kb + 4 (lane >> 5) + 0..3]), biases, row 0
         const uint32_t NT = a.nt32[l], total = a.nk8[l] * NT * 256;
         if (idx < total) {
             const uint32_t m = idx & 3u, lane = (idx >> 2) & 63u, q = idx >> 8;
@@ -398,53 +403,11 @@ __global__ __launch_bounds__(256) void k_field_pack_all(PackAllArgs a)
         if (l == 1 && a.row0 && idx < a.row0_len) a.row0[idx] = idx < K ? W[idx] : 0.0f;
     }
     uint32_t* const flag = a.guard ? a.guard + 1 + l : nullptr;
-    if (a.Wp16[l]) {   // 32x32x16 half fragments (k_field_pack_layer16)
-        const uint32_t NT = a.nt32[l], total = a.nk16[l] * NT * 512;
-        if (idx < total) {
-            const uint32_t e = idx & 7u, lane = (idx >> 3) & 63u, q = idx >> 9;
-            const uint32_t t = q % NT, ks = q / NT;
-            const uint32_t out = t * 32 + (lane & 31u), k = ks * 16 + 8 * (lane >> 5) + e;
-            const float    wv = (out < H && k < K) ? W[(size_t)out * ldw + k] * 256.0f : 0.0f;
-            if (flag && !(fabsf(wv) <= kHalfMax)) atomicMax(flag, a.pack_id);
-            half_t hi, lo;
-            split_half(wv, hi, lo);
-            a.Wp16[l][((size_t)q * 2 + 0) * 512 + lane * 8 + e] = hi;
-            a.Wp16[l][((size_t)q * 2 + 1) * 512 + lane * 8 + e] = lo;
-        }
-    }
     if (a.Wq16[l]) {
         const uint32_t total = a.nk32[l] * a.ncb[l] * 512;
         if (idx < total)
             pack16x32_element(W, H, K, ldw, a.ncb[l], idx, a.Wq16[l], flag, a.pack_id, a.k_gap[l], a.tflags[l], a.src_off[l]);
     }
-}
-
-template <typename Kern>
-static int resident_grid(Kern kern, size_t lds_bytes, uint32_t tiles, uint32_t cap_per_cu, uint32_t* blocks)
-{
-    // (kernel, device, LDS size) -> resident workgroups: an immutable fact of the hardware and the binary, asked once
-    // per thread and variant instead of three runtime calls per launch.  (Every instantiation has the same function
-    // type, so the kernel's address is part of the key.)
-    struct Slot { const void* kern; int dev; size_t lds; uint32_t n; };
-    static thread_local Slot cache[8] = {};
-    static thread_local uint32_t next = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return CNC_ERR_LAUNCH;
-    const void* const key = reinterpret_cast<const void*>(kern);
-    uint32_t n = 0;
-    for (auto& s : cache)
-        if (s.kern == key && s.dev == dev && s.lds == lds_bytes) n = s.n;
-    if (n == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 128, lds_bytes) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu <= 0 || cus <= 0)
-            return CNC_ERR_LAUNCH;
-        if ((uint32_t)per_cu > cap_per_cu) per_cu = (int)cap_per_cu;
-        n = (uint32_t)(per_cu * cus);
-        cache[next++ & 7u] = Slot{key, dev, lds_bytes, n};
-    }
-    *blocks = tiles < n ? tiles : n;
-    return CNC_OK;
 }
 
 // Launch of the two-wave kernels (called by cnc_field_fused_forward, field_fused.hip).  waves_per_simd: 3 or 4 (the
@@ -456,28 +419,23 @@ int launch_field_fused_w2(const FusedFieldArgs& p, bool rgb, uint32_t F, uint32_
     const uint32_t table_at = NT == 5 ? (rgb ? kUnitTableAt<5, true>() : kUnitTableAt<5, false>())
                                       : (rgb ? kUnitTableAt<2, true>() : kUnitTableAt<2, false>());
     const size_t lds_bytes = (size_t)table_at * sizeof(half_t) + kMaxUnits * sizeof(uint4);
-    uint32_t blocks = 0;
     int rc = CNC_OK;
-#define CNC_W2(FV, NTV, RGBV, WV)                                                                   \
-    do {                                                                                            \
-        rc = resident_grid(k_field_fused16w2<FV, NTV, RGBV, WV>, lds_bytes, tiles, 16, &blocks);    \
-        if (rc == CNC_OK) hipLaunchKernelGGL((k_field_fused16w2<FV, NTV, RGBV, WV>), dim3(blocks), dim3(128), lds_bytes, s, p); \
+    auto launch = [&](auto kern) {
+        uint32_t resident = 0;
+        rc = resident_grid(kern, 128, lds_bytes, 16, &resident);
+        if (rc == CNC_OK) hipLaunchKernelGGL(kern, dim3(tiles < resident ? tiles : resident), dim3(128), lds_bytes, s, p);
+    };
+#define CNC_W2_W(FV, NTV, RGBV)                                                \
+    do {                                                                       \
+        if (waves_per_simd >= 4) launch(k_field_fused16w2<FV, NTV, RGBV, 4>); \
+        else launch(k_field_fused16w2<FV, NTV, RGBV, 3>);                      \
     } while (0)
-#define CNC_W2_W(FV, NTV, RGBV)                     \
-    do {                                            \
-        if (waves_per_simd >= 4) CNC_W2(FV, NTV, RGBV, 4); \
-        else CNC_W2(FV, NTV, RGBV, 3);              \
-    } while (0)
-#define CNC_W2_RGB(FV, NTV)                 \
-    do {                                    \
-        if (p.dbg_features) {               \
-            rc = resident_grid(k_field_fused16w2<FV, NTV, false, 3, 1>, lds_bytes, tiles, 16, &blocks); \
-            if (rc == CNC_OK) hipLaunchKernelGGL((k_field_fused16w2<FV, NTV, false, 3, 1>), dim3(blocks), dim3(128), lds_bytes, s, p); \
-        } else if (p.save.feat) {           \
-            rc = resident_grid(k_field_fused16w2<FV, NTV, true, 3, 2>, lds_bytes, tiles, 16, &blocks); \
-            if (rc == CNC_OK) hipLaunchKernelGGL((k_field_fused16w2<FV, NTV, true, 3, 2>), dim3(blocks), dim3(128), lds_bytes, s, p); \
-        } else if (rgb) CNC_W2_W(FV, NTV, true); \
-        else CNC_W2_W(FV, NTV, false);      \
+#define CNC_W2_RGB(FV, NTV)                                                       \
+    do {                                                                          \
+        if (p.dbg_features) launch(k_field_fused16w2<FV, NTV, false, 3, 1>);      \
+        else if (p.save.feat) launch(k_field_fused16w2<FV, NTV, true, 3, 2>);     \
+        else if (rgb) CNC_W2_W(FV, NTV, true);                                    \
+        else CNC_W2_W(FV, NTV, false);                                            \
     } while (0)
 #define CNC_W2_NT(FV)                   \
     do {                                \
@@ -490,7 +448,6 @@ int launch_field_fused_w2(const FusedFieldArgs& p, bool rgb, uint32_t F, uint32_
 #undef CNC_W2_NT
 #undef CNC_W2_RGB
 #undef CNC_W2_W
-#undef CNC_W2
     if (rc != CNC_OK) return rc;
     return launch_status();
 }
@@ -514,20 +471,17 @@ extern "C" int cnc_field_pack_all(const cnc_field_pack_t* d, void* stream)
         } else if (!L.Wq16) {
             return CNC_ERR_INVALID_VALUE;
         }
-        if (tr && (L.Wp16 || L.ldw < L.src_off + L.H - ((L.flags & CNC_PACK_ZERO_FIRST) ? 1u : 0u))) return CNC_ERR_INVALID_VALUE;
-        if (L.Wp16 && (L.n_ksteps16 == 0 || L.K > L.n_ksteps16 * 16)) return CNC_ERR_INVALID_VALUE;
+        if (tr && L.ldw < L.src_off + L.H - ((L.flags & CNC_PACK_ZERO_FIRST) ? 1u : 0u)) return CNC_ERR_INVALID_VALUE;
         if (L.Wq16 && (L.n_colblocks == 0 || L.n_ksteps32 == 0 || L.H > L.n_colblocks * 16 ||
                        L.K + (L.k_gap ? 1u : 0u) > L.n_ksteps32 * 32 || L.k_gap >= L.K))
             return CNC_ERR_INVALID_VALUE;
         a.W[l] = L.W; a.b[l] = L.b; a.H[l] = L.H; a.K[l] = L.K; a.ldw[l] = L.ldw;
-        a.nt32[l] = L.n_tiles; a.nk8[l] = L.n_ksteps; a.nk16[l] = L.n_ksteps16;
+        a.nt32[l] = L.n_tiles; a.nk8[l] = L.n_ksteps;
         a.ncb[l] = L.n_colblocks; a.nk32[l] = L.n_ksteps32; a.k_gap[l] = L.k_gap;
         a.tflags[l] = L.flags; a.src_off[l] = L.src_off;
         a.Wp[l] = L.Wp; a.Bp[l] = L.Bp;
-        a.Wp16[l] = reinterpret_cast<half_t*>(L.Wp16);
         a.Wq16[l] = reinterpret_cast<half_t*>(L.Wq16);
         uint32_t total = L.Wp ? L.n_ksteps * L.n_tiles * 256 : 0u;
-        if (L.Wp16 && L.n_ksteps16 * L.n_tiles * 512 > total) total = L.n_ksteps16 * L.n_tiles * 512;
         if (L.Wq16 && L.n_ksteps32 * L.n_colblocks * 512 > total) total = L.n_ksteps32 * L.n_colblocks * 512;
         if (l == 1 && d->row0 && d->row0_len > total) total = d->row0_len;
         a.first_block[l] = blocks;

@@ -1,6 +1,6 @@
-// field_fused_common.hpp — what the fused-field translation units (field_fused.hip: one wave per 32 samples;
-// field_fused2.hip: two cooperating waves per 32 samples) share: the kernel arguments, the weight stream through a
-// buffer resource, the per-unit gather, the chunk-tile rows and the window fill.
+// field_fused_common.hpp — what the fused-field translation units (field_fused.hip: one wave per 32 samples, exact fp32;
+// field_fused2.hip: two cooperating waves per 32 samples, fp16) share: the kernel arguments, the weight stream through a
+// buffer resource, the per-unit gather, the chunk-tile rows, the window fill and the resident-grid query.
 #pragma once
 #include "common.hpp"
 #include <cstdlib>
@@ -51,7 +51,7 @@ struct FusedFieldArgs {
     uint32_t     n_freqs;
     uint32_t     n_units;         // (encoder, level) units = sum of n_levels
     uint32_t     nkb1;            // K-steps of 8 of layer 1 (a multiple of 4: K padded to whole 32-column chunks)
-    const float* Wp[5];           // packed weights (cnc_field_pack_layer)
+    const float* Wp[5];           // packed weights (cnc_field_pack_all: Wp)
     const float* Bp[5];           // padded biases
     const float* w2row;           // density only: W2[0, :] padded to NT * 32
     uint32_t     geo;
@@ -60,12 +60,11 @@ struct FusedFieldArgs {
     float*       rgb;
     uint32_t     sh_fp16;
     const uint4* units;           // per unit {first row, rows, resolution, encoder} of its level (cnc_fused_field_t.units)
-    const half_t_* Wp16[5];       // fp16 hi / lo fragments (cnc_field_pack_layer16), k_field_fused16
-    uint32_t       nk16_1;        // K-steps of 16 of layer 1 (a multiple of 2)
-    uint32_t       nk16_h;        // K-steps of 16 of the head's first layer: roundup16(16 + geo) / 16
+    uint32_t       nk16_1;        // K-steps of 16 of layer 1 = nkb1 / 2 (a multiple of 2): k_field_fused16w2 counts its
+                                  // 32-column chunks from it, and that kernel's code is kept as it was
     // fp16 range guard (cnc_fused_field_t.guard): word 0 = id of the last call in which a value left fp16's range
     // (written by the fp16 kernels, read by the exact-fp32 kernel launched behind them: it runs only then), words
-    // 1..5 = "layer l has a weight with |256 w| > 65504" (cnc_field_pack_layer16*)
+    // 1..5 = "layer l has a weight with |256 w| > 65504" (cnc_field_pack_all)
     uint32_t*      guard;
     uint32_t       call_id;
     uint32_t       pack_id;       // id of the cnc_field_pack_all that produced the fragments in use (> 0)
@@ -311,7 +310,7 @@ __device__ __forceinline__ void guard_raise(const FusedFieldArgs& p, float mx)
 
 // Where a sample's row of the 32 x 32 chunk tile lives.  Float tile: the A operand of the fp32 MFMA.  Half tile: two
 // planes, x = hi + lo with hi = half(x), lo = half(x - hi) — 22 bits of x — the A operands of the three-product
-// fp16 MFMA scheme (see k_field_fused16).
+// fp16 MFMA scheme (see k_field_fused16w2, field_fused2.hip).
 struct RowF32 {
     static constexpr bool kFastSin = false;
     static __device__ __forceinline__ float clamp_raw(float v) { return v; }
@@ -617,6 +616,35 @@ __device__ __forceinline__ void fill_units(const FusedFieldArgs& p, const UnitTa
         window_unit_issue<F, D>(p, units, xu, (w0 + s * F) / F, st, bits_uniform);
         window_unit_finish<F, D, Row>(st, w0 + s * F, trow);
     }
+}
+
+// The grid of a persistent kernel is what is RESIDENT at once (the workgroups loop over the tiles): workgroups of `block`
+// threads and `lds_bytes` of LDS per CU, at most `cap_per_cu`, times the CUs.  (kernel, device, LDS size) -> resident
+// workgroups is an immutable fact of the hardware and the binary: asked once per thread and variant instead of three
+// runtime calls per launch.  (Every instantiation has the same function type, so the kernel's address is part of the key.)
+template <typename Kern>
+static int resident_grid(Kern kern, uint32_t block, size_t lds_bytes, uint32_t cap_per_cu, uint32_t* resident)
+{
+    struct Slot { const void* kern; int dev; size_t lds; uint32_t n; };
+    static thread_local Slot cache[8] = {};
+    static thread_local uint32_t next = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return CNC_ERR_LAUNCH;
+    const void* const key = reinterpret_cast<const void*>(kern);
+    uint32_t n = 0;
+    for (auto& s : cache)
+        if (s.kern == key && s.dev == dev && s.lds == lds_bytes) n = s.n;
+    if (n == 0) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)block, lds_bytes) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu <= 0 || cus <= 0)
+            return CNC_ERR_LAUNCH;
+        if ((uint32_t)per_cu > cap_per_cu) per_cu = (int)cap_per_cu;
+        n = (uint32_t)(per_cu * cus);
+        cache[next++ & 7u] = Slot{key, dev, lds_bytes, n};
+    }
+    *resident = n;
+    return CNC_OK;
 }
 
 // field_fused2.hip: the two-waves-per-tile kernels

@@ -1177,4 +1177,4 @@ extern "C" const char* cnc_error_string(int code)
     }
 }
 
-extern "C" int cnc_abi_version(void) { return 32; }
+extern "C" int cnc_abi_version(void) { return 33; }

@@ -373,8 +373,8 @@ class FusedFieldForward:
         return [f.mlp_base.network[0], f.mlp_base.network[2], f.mlp_head[0], f.mlp_head[2], f.mlp_head[4]]
 
     def _pack(self, dev):
-        """The five layers in every fragment order the kernels read — fp32 (exact form and the range guard's fallback),
-        fp16 hi / lo for the one-wave and for the two-wave kernels — in ONE launch (cnc_field_pack_all)."""
+        """The five layers in both fragment orders the kernels read — fp32 (exact form and the range guard's fallback),
+        fp16 hi / lo for the two-wave kernels — in ONE launch (cnc_field_pack_all)."""
         from . import _lib
         layers = self._layers()
         key = tuple((l.weight.data_ptr(), l.weight._version, l.bias.data_ptr(), l.bias._version) for l in layers) + (str(dev),)
@@ -385,19 +385,18 @@ class FusedFieldForward:
         T, T2 = H // 32, (3 if H == 160 else 2)
         K0 = layers[0].in_features
         r32 = lambda k: (k + 31) // 32
-        # per layer: (32-column tiles, K-steps of 8 [fp32 MFMA], K-steps of 16 [32x32x16 halves],
-        #             16-column blocks, K-steps of 32 [16x16x32 halves: the two-wave kernels])
-        shapes = [(T, r32(K0) * 4, r32(K0) * 2, H // 16, r32(K0)),
-                  (T2, H // 8, H // 16, 5 if H == 160 else 4, H // 32),
-                  (T, (16 + geo + 7) // 8, (16 + geo + 15) // 16, H // 16, r32(17 + geo)),     # Wq16: a zero column at k = 16
-                  (T, H // 8, H // 16, H // 16, H // 32),
-                  (1, H // 8, H // 16, 1, H // 32)]
+        # per layer: (32-column tiles, K-steps of 8 [fp32 MFMA], 16-column blocks, K-steps of 32 [16x16x32 halves: the
+        #             two-wave kernels])
+        shapes = [(T, r32(K0) * 4, H // 16, r32(K0)),
+                  (T2, H // 8, 5 if H == 160 else 4, H // 32),
+                  (T, (16 + geo + 7) // 8, H // 16, r32(17 + geo)),     # Wq16: a zero column at k = 16
+                  (T, H // 8, H // 16, H // 32),
+                  (1, H // 8, 1, H // 32)]
         if self._buffers is None or self._buffers["dev"] != str(dev):
             self._buffers = {"dev": str(dev),
-                             "w": [torch.empty(nk * nt * 256, dtype=torch.float32, device=dev) for nt, nk, _, _, _ in shapes],
-                             "w16": [torch.empty(nk16 * nt * 1024, dtype=torch.float16, device=dev) for nt, _, nk16, _, _ in shapes],
-                             "wq16": [torch.empty(nk32 * ncb * 1024, dtype=torch.float16, device=dev) for _, _, _, ncb, nk32 in shapes],
-                             "b": [torch.empty(nt * 32, dtype=torch.float32, device=dev) for nt, _, _, _, _ in shapes],
+                             "w": [torch.empty(nk * nt * 256, dtype=torch.float32, device=dev) for nt, nk, _, _ in shapes],
+                             "wq16": [torch.empty(nk32 * ncb * 1024, dtype=torch.float16, device=dev) for _, _, ncb, nk32 in shapes],
+                             "b": [torch.empty(nt * 32, dtype=torch.float32, device=dev) for nt, _, _, _ in shapes],
                              "row0": torch.empty(H, dtype=torch.float32, device=dev),
                              # the fp16 range guard's words (cnc_hip.h): zero once, stamped with ids afterwards
                              # (64 words: a -DCNC_W2_PROF build adds its phase clocks behind the guard's eight)
@@ -406,16 +405,15 @@ class FusedFieldForward:
         self._pack_id += 1
         d = _lib.FieldPack()
         keep = []
-        for k, (l, (nt, nk, nk16, ncb, nk32)) in enumerate(zip(layers, shapes)):
+        for k, (l, (nt, nk, ncb, nk32)) in enumerate(zip(layers, shapes)):
             w, b = l.weight.detach(), l.bias.detach()
             if not w.is_contiguous():
                 w = w.contiguous()
             keep += [w, b]
             L = d.layer[k]
             L.W, L.b, L.H, L.K, L.ldw = w.data_ptr(), b.data_ptr(), w.shape[0], w.shape[1], w.stride(0)
-            L.n_tiles, L.n_ksteps, L.n_ksteps16, L.n_colblocks, L.n_ksteps32 = nt, nk, nk16, ncb, nk32
-            L.Wp, L.Bp = buf["w"][k].data_ptr(), buf["b"][k].data_ptr()
-            L.Wp16, L.Wq16 = buf["w16"][k].data_ptr(), buf["wq16"][k].data_ptr()
+            L.n_tiles, L.n_ksteps, L.n_colblocks, L.n_ksteps32 = nt, nk, ncb, nk32
+            L.Wp, L.Bp, L.Wq16 = buf["w"][k].data_ptr(), buf["b"][k].data_ptr(), buf["wq16"][k].data_ptr()
             L.k_gap = 16 if k == 2 else 0          # head.0: [SH4 | raw density (zero weights) | geo], field_fused2.hip
         d.row0, d.row0_len = buf["row0"].data_ptr(), H
         d.guard, d.pack_id = buf["guard"].data_ptr(), self._pack_id
@@ -447,7 +445,6 @@ class FusedFieldForward:
         st.freqs, st.n_freqs = mb._freqs.data_ptr(), mb._freqs.numel()
         for k in range(5):
             st.packed_weights[k], st.packed_biases[k] = buf["w"][k].data_ptr(), buf["b"][k].data_ptr()
-            st.packed_weights16[k] = buf["w16"][k].data_ptr()
             st.packed_weights16q[k] = buf["wq16"][k].data_ptr()
         st.w2_row0 = buf["row0"].data_ptr()
         if self._units is None or self._units.device != dev:
@@ -461,13 +458,11 @@ class FusedFieldForward:
         st.n_features, st.n_neurons, st.geo_feat_dim = mb.encoding_xyz.n_features, mb.network[0].out_features, f.geo_feat_dim
         flags = _lib.CNC_FIELD_SH_FP16 if f.sh_fp16_round else 0
         if f.fused_field_precision == "f16x3":
+            # two cooperating waves per tile; the density-only kernel fits four waves per SIMD, the colour kernel three
             flags |= _lib.CNC_FIELD_MFMA_F16X3
-            if f.fused_field_kernel == "w2":
-                # two cooperating waves per tile; the density-only kernel fits four waves per SIMD, the colour kernel three
-                flags |= _lib.CNC_FIELD_TWO_WAVES
-                waves = f.fused_field_waves or (3 if want_rgb else 4)
-                if waves >= 4:
-                    flags |= _lib.CNC_FIELD_WAVES4
+            waves = f.fused_field_waves or (3 if want_rgb else 4)
+            if waves >= 4:
+                flags |= _lib.CNC_FIELD_WAVES4
         st.flags = flags
         self._call_id = self._call_id % 0xFFFFFFF0 + 1
         st.guard, st.call_id, st.pack_id = buf["guard"].data_ptr(), self._call_id, self._pack_id
@@ -509,11 +504,11 @@ class FusedFieldForward:
         """The gradient pass's forward (cnc_field_save_t): rgb [rows, 3], density [rows, 1] of the N <= `rows` world
         positions — rows behind them are evaluated as points outside the box — and, in a dict, everything the backward
         reads, written by the same kernel: feat, h1, h3, h4, head_in, raw, selector, xyz / xy / xz / yz, + the encoders'
-        clip counts.  Needs the two-wave three-product kernel (the default)."""
+        clip counts.  Needs the fp16 three-product kernel (the default)."""
         from . import _lib
         f = self.field
-        if f.fused_field_precision != "f16x3" or f.fused_field_kernel != "w2":
-            raise RuntimeError("save_forward: the two-wave fp16 kernel only")
+        if f.fused_field_precision != "f16x3":
+            raise RuntimeError("save_forward: the fp16 kernel only")
         x = positions.reshape(-1, 3).contiguous()
         d = directions.reshape(-1, 3).contiguous()
         if x.dtype != torch.float32 or d.dtype != torch.float32 or not x.is_cuda or x.shape != d.shape:
@@ -735,14 +730,15 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         # chain of encoder launches, library GEMMs and glue kernels that the gradient path uses)
         self.fused_field = fused_features and os.environ.get("CNC_FUSED_FIELD", "1") == "1"
         # "f16x3" (default): the layers on the fp16 matrix pipe, three products per term (~5e-7 per term, against
-        # fp32's 6e-8); "f32": v_mfma_f32_32x32x2_f32, an exact fmaf chain per output — 2x the time
+        # fp32's 6e-8), two cooperating waves per 32-sample tile (csrc/field_fused2.hip); "f32": one wave per tile on
+        # v_mfma_f32_32x32x2_f32, an exact fmaf chain per output — 2x the time
         self.fused_field_precision = os.environ.get("CNC_FUSED_FIELD_MFMA", "f16x3")
         if self.fused_field_precision not in ("f16x3", "f32"):
             raise ValueError("CNC_FUSED_FIELD_MFMA must be f16x3 or f32")
-        # "w2" (default): two cooperating waves per 32-sample tile (csrc/field_fused2.hip); "w1": one wave per tile
-        self.fused_field_kernel = os.environ.get("CNC_FUSED_FIELD_KERNEL", "w2")
-        if self.fused_field_kernel not in ("w1", "w2"):
-            raise ValueError("CNC_FUSED_FIELD_KERNEL must be w1 or w2")
+        # The name of the fp16 kernel, for reports only: nothing in the package branches on it.  It used to choose between
+        # the two-wave kernel and a one-wave fp16 predecessor; that one is gone, "w2" is the only fp16 form.  It stays a plain
+        # attribute because the benchmark's field report prints it and tests assign it next to the precision.
+        self.fused_field_kernel = "w2"
         self.fused_field_waves = int(os.environ.get("CNC_FUSED_FIELD_WAVES", "0"))     # 0: per kernel (4 density, 3 colour)
         self._field_fused = None
         # the gradient pass's input-gradient chain as one kernel (`_FieldChain`; CNC_FUSED_CHAIN=0: layer by layer)
@@ -828,7 +824,7 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         """The gradient pass as the saving fused kernel + the gradient chain (`_FieldTrain`) applies."""
         if not (self.fused_train and self.fused_field and torch.is_grad_enabled() and positions.is_cuda
                 and positions.dtype == torch.float32 and not positions.requires_grad and not directions.requires_grad
-                and self.fused_field_precision == "f16x3" and self.fused_field_kernel == "w2" and self._glue_ok(positions)):
+                and self.fused_field_precision == "f16x3" and self._glue_ok(positions)):
             return False
         if not self._chain_ok(positions.reshape(-1, 3)):
             return False

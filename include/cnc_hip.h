@@ -810,7 +810,7 @@ int cnc_field_post(const float* base_out, uint32_t ld_base, uint32_t geo_feat_di
  * chain in k order (v_mfma_f32_32x32x2_f32), i.e. equal to the op chain up to the summation order of a GEMM.
  * ---------------------------------------------------------------------------------------- */
 /* (ABI v27) The forward of the GRADIENT pass as the same one kernel: with `save.feat` set, cnc_field_fused_forward
- * (CNC_FIELD_TWO_WAVES, rgb != NULL) also writes everything the backward reads — what the op chain's autograd would have
+ * (CNC_FIELD_MFMA_F16X3, rgb != NULL) also writes everything the backward reads — what the op chain's autograd would have
  * kept (ngp.py:506-547: the MLPs' inputs and ReLU outputs) plus the inputs of the four encoders' backward — so that a
  * training step's render pass is: this kernel, cnc_field_backward_chain, cnc_field_weight_grads, the encoders' backward.
  * All matrices row-major float32 with N rows, N = the call's N (the caller's bucketed row count); positions / dirs are
@@ -842,10 +842,9 @@ typedef struct {
     const int32_t* offsets[4];         /* per encoder: level offsets [n_levels + 1]                               */
     const int32_t* resolutions[4];     /* per encoder: resolutions [n_levels]                                     */
     const float*   freqs;              /* [n_freqs] on the device: the Embedder's frequency bands (ngp.py:583-599) */
-    const float*   packed_weights[5];  /* cnc_field_pack_layer of: base.0, base.2, head.0, head.2, head.4          */
+    const float*   packed_weights[5];  /* cnc_field_pack_all's Wp of: base.0, base.2, head.0, head.2, head.4       */
     const float*   packed_biases[5];   /*   (entries 2..4 may be NULL for density-only calls)                      */
     const float*   w2_row0;            /* base.2.weight[0, :] padded to n_neurons (density-only calls)             */
-    const void*    packed_weights16[5];/* cnc_field_pack_layer16 of the same five layers (CNC_FIELD_MFMA_F16X3)     */
     const uint32_t* units;             /* [sum n_levels][4] on the device, in feature-row order (xyz levels, then the
                                           xy, xz, yz planes' levels): {offsets[l], offsets[l+1] - offsets[l],
                                           resolutions[l], encoder 0..3} — the level tables as one record per unit   */
@@ -854,9 +853,9 @@ typedef struct {
     uint32_t       n_freqs;            /* > 0 (the reference always embeds, ngp.py:433)                           */
     uint32_t       n_neurons;          /* H: 64 or 160                                                            */
     uint32_t       geo_feat_dim;       /* 1 + geo <= 64 (H = 64) / 96 (H = 160) and roundup8(16 + geo) <= H        */
-    uint32_t       flags;              /* CNC_FIELD_SH_FP16 | CNC_FIELD_MFMA_F16X3 | CNC_FIELD_TWO_WAVES | ...      */
+    uint32_t       flags;              /* CNC_FIELD_SH_FP16 | CNC_FIELD_MFMA_F16X3 | CNC_FIELD_WAVES4               */
     /* ---- ABI v26 ---- */
-    const void*    packed_weights16q[5];/* cnc_field_pack_all's 16x16x32 fragments (CNC_FIELD_TWO_WAVES)              */
+    const void*    packed_weights16q[5];/* cnc_field_pack_all's Wq16 of the same five layers (CNC_FIELD_MFMA_F16X3)  */
     uint32_t*      guard;              /* 8 zero-initialised words on the device, owned by the caller for the life of
                                           the field: the fp16 range guard (below).  Required with CNC_FIELD_MFMA_F16X3 */
     uint32_t       call_id;            /* a number the caller increases with every call (> 0)                      */
@@ -864,7 +863,7 @@ typedef struct {
     float*         debug_features;     /* test hook (nullable): [N, debug_ld] floats receive the first layer's INPUT row of
                                           every sample exactly as the kernel computed it — the four encoders' features,
                                           the raw coordinates, the sinusoids, zero padding to a multiple of 32 — before
-                                          it is split into halves.  CNC_FIELD_TWO_WAVES density-only calls only.        */
+                                          it is split into halves.  CNC_FIELD_MFMA_F16X3 density-only calls only.       */
     uint32_t       debug_ld;           /* >= roundup32(K0)                                                         */
     /* ---- ABI v27 ---- */
     cnc_field_save_t save;             /* save.feat != NULL: the gradient pass's forward (above)                   */
@@ -874,16 +873,17 @@ typedef struct {
                                           and must not wait for the number (the front-to-back sampler's depth windows)     */
 } cnc_fused_field_t;
 
-/* The layers' products on the fp16 matrix pipe, three per term: every operand split x = hi + lo into two halves
- * (22 significand bits), x w ~= hi hi + hi lo + lo hi accumulated in fp32 (v_mfma_f32_32x32x16_f16): ~5e-7 relative
- * per term against fp32's 6e-8, at 1/5 of the matrix cycles of the exact fp32 form and on a pipe that overlaps with the
- * gather's vector work.  Without the flag: v_mfma_f32_32x32x2_f32, an exact fp32 fmaf chain per output.        */
+/* The fp16 form.  The layers' products on the fp16 matrix pipe, three per term: every operand split x = hi + lo into
+ * two halves (22 significand bits), x w ~= hi hi + hi lo + lo hi accumulated in fp32 (v_mfma_f32_16x16x32_f16): ~5e-7
+ * relative per term against fp32's 6e-8, at a fraction of the matrix cycles of the exact fp32 form and on a pipe that
+ * overlaps with the gather's vector work.  Two cooperating waves per 32-sample tile (csrc/field_fused2.hip): each owns
+ * half the output columns of a layer — half the accumulators and weight registers of a one-wave kernel, so 3-4 waves per
+ * SIMD hide the latency of the feature gathers.  Needs packed_weights16q and the guard.  Without the flag:
+ * v_mfma_f32_32x32x2_f32, an exact fp32 fmaf chain per output, one wave per tile (csrc/field_fused.hip).
+ * (ABI v33: the flag selected a one-wave fp16 kernel with fragments of its own until v32, and the two-wave kernel had
+ * a flag, value 4; that kernel, its fragments and the flag are gone.)                                            */
 #define CNC_FIELD_MFMA_F16X3 2u
-/* (ABI v26) Two cooperating waves per 32-sample tile (csrc/field_fused2.hip): each owns half the output columns of a
- * layer — half the accumulators and weight registers of the one-wave kernel, so 3-4 waves per SIMD hide the latency of
- * the feature gathers.  Implies the three-product fp16 scheme; needs packed_weights16q.  CNC_FIELD_WAVES4 selects the
- * variant compiled for four waves per SIMD (128 registers) instead of three (168).                                */
-#define CNC_FIELD_TWO_WAVES 4u
+/* With CNC_FIELD_MFMA_F16X3: the variant compiled for four waves per SIMD (128 registers) instead of three (168).  */
 #define CNC_FIELD_WAVES4 8u
 /* The fp16 range guard.  The three-product kernels split every operand into two halves; a hidden activation above
  * fp16's 65504, or a weight with |2^8 w| above it, would become inf / NaN silently.  Both are detected exactly, on the
@@ -891,46 +891,35 @@ typedef struct {
  * and cnc_field_fused_forward enqueues the exact-fp32 kernel behind every fp16 launch — it returns at once unless
  * guard[0] == call_id, and recomputes the call otherwise.  No host synchronisation; the cost is one empty launch.   */
 
-/* W [H, K] row-major (row stride ldw), b [H]  ->  Wp: n_ksteps * n_tiles * 256 floats in MFMA fragment order (float4
- * (kb * n_tiles + t) * 64 + lane = W[32 t + (lane & 31)][8 kb + 4 (lane >> 5) + 0..3], zero outside [H, K]);
- * Bp: n_tiles * 32 floats; row0 (nullable): W[0, :] zero-padded to row0_len floats.
- * Layer shapes for cnc_field_fused_forward (H = n_neurons, T = H / 32, T2 = 3 if H == 160 else 2, K0 = feature width):
- *   base.0: n_tiles T,  n_ksteps roundup32(K0) / 8        base.2: n_tiles T2, n_ksteps H / 8  (+ row0, row0_len H)
+/* (ABI v26) All five layers (base.0, base.2, head.0, head.2, head.4) into both fragment orders the fused kernels read,
+ * in ONE launch.  Per layer: W [H, K] row-major (row stride ldw), b [H].
+ * Wp (the exact fp32 kernel): n_ksteps * n_tiles * 256 floats in MFMA fragment order — float4 (kb * n_tiles + t) * 64 +
+ * lane = W[32 t + (lane & 31)][8 kb + 4 (lane >> 5) + 0..3], zero outside [H, K]; Bp: n_tiles * 32 floats, b zero-padded.
+ * Shapes for cnc_field_fused_forward (H = n_neurons, T = H / 32, T2 = 3 if H == 160 else 2, K0 = feature width):
+ *   base.0: n_tiles T,  n_ksteps roundup32(K0) / 8        base.2: n_tiles T2, n_ksteps H / 8
  *   head.0: n_tiles T,  n_ksteps roundup8(16 + geo) / 8    head.2: n_tiles T,  n_ksteps H / 8
- *   head.4: n_tiles 1,  n_ksteps H / 8                                                                          */
-int cnc_field_pack_layer(const float* W, const float* b, uint32_t H, uint32_t K, uint32_t ldw, uint32_t n_tiles,
-                         uint32_t n_ksteps, float* Wp, float* Bp, float* row0, uint32_t row0_len, void* stream);
-
-/* The same layer for CNC_FIELD_MFMA_F16X3: Wp16 = n_ksteps16 * n_tiles * 1024 halves (per (K-step of 16, tile): 64 x 8
- * halves hi, 64 x 8 halves lo of 2^8 W[32 t + (lane & 31)][16 ks + 8 (lane >> 5) + 0..7]).  n_ksteps16: base.0
- * roundup32(K0) / 16, base.2 / head.2 / head.4 H / 16, head.0 roundup16(16 + geo) / 16 (<= H / 16).  Biases: those of
- * cnc_field_pack_layer.                                                                                        */
-int cnc_field_pack_layer16(const float* W, uint32_t H, uint32_t K, uint32_t ldw, uint32_t n_tiles, uint32_t n_ksteps16,
-                           void* Wp16, void* stream);
-
-/* (ABI v26) All five layers (base.0, base.2, head.0, head.2, head.4) into every fragment order the fused kernels read,
- * in ONE launch.  Per layer: W [H, K] (row stride ldw), b [H]; Wp / Bp as cnc_field_pack_layer (n_tiles, n_ksteps);
- * Wp16 (nullable) as cnc_field_pack_layer16 (n_ksteps16); Wq16 (nullable): n_ksteps32 * n_colblocks * 1024 halves — per
- * (K-step of 32, column block of 16): 64 x 8 halves hi, then lo, of 2^8 W[16 cb + (lane & 15)][32 ks + 8 (lane >> 4)
- * + 0..7].  Column blocks for CNC_FIELD_TWO_WAVES: base.0 / head.0 / head.2: H / 16; base.2: 5 (H = 160) or 4 (H = 64);
- * head.4: 1.  K-steps of 32: roundup32(K) / 32 (head.0: roundup32(K + 1) / 32 with k_gap = 16).  row0 / row0_len: base.2's row 0 as
- * in cnc_field_pack_layer.
- * guard / pack_id: a layer holding a weight with |2^8 w| > 65504 gets guard[1 + layer] = pack_id (see the guard). */
+ *   head.4: n_tiles 1,  n_ksteps H / 8
+ * Wq16 (nullable; the fp16 kernels): n_ksteps32 * n_colblocks * 1024 halves — per (K-step of 32, column block of 16):
+ * 64 x 8 halves hi, then lo, of 2^8 W[16 cb + (lane & 15)][32 ks + 8 (lane >> 4) + 0..7].  Column blocks for
+ * CNC_FIELD_MFMA_F16X3: base.0 / head.0 / head.2: H / 16; base.2: 5 (H = 160) or 4 (H = 64); head.4: 1.  K-steps of 32:
+ * roundup32(K) / 32 (head.0: roundup32(K + 1) / 32 with k_gap = 16).
+ * row0 (nullable) / row0_len: base.2's W[0, :] zero-padded to row0_len >= K floats (cnc_fused_field_t.w2_row0).
+ * guard / pack_id: a layer holding a weight with |2^8 w| > 65504 gets guard[1 + layer] = pack_id (see the guard).
+ * (Until ABI v32 two per-layer entry points packed Wp and a third, 32x32x16 fragment order one layer at a time.)    */
 typedef struct {
     const float* W;
     const float* b;
     uint32_t     H, K, ldw;
-    uint32_t     n_tiles, n_ksteps, n_ksteps16, n_colblocks, n_ksteps32;
+    uint32_t     n_tiles, n_ksteps, n_colblocks, n_ksteps32;
     float*       Wp;
     float*       Bp;
-    void*        Wp16;
     void*        Wq16;
     uint32_t     k_gap;     /* Wq16 only: != 0 inserts a zero column at packed k = k_gap (the source columns from k_gap on
                                move one to the right).  head.0 takes 16: the two-wave kernel lays the head's input out as
                                [SH4 (16) | base output c at column 16 + c], and output 0 is the raw density            */
     uint32_t     flags;     /* Wq16 only.  CNC_PACK_TRANSPOSE: packed W'[out][k] = W[k][src_off + out] (W: K rows of ldw
                                floats) — the layers of the gradient chain (cnc_field_backward_chain) are the forward's
-                               transposed; Wp / Bp / Wp16 / b must be NULL then (Wp == NULL skips the fp32 fragments for
+                               transposed; Wp / Bp / b must be NULL then (Wp == NULL skips the fp32 fragments for
                                any layer).  CNC_PACK_ZERO_FIRST: packed output 0 is all zero and output o >= 1 reads source
                                src_off + o - 1 (the raw density's slot in front of the geo features)                 */
     uint32_t     src_off;

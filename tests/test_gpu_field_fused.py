@@ -58,14 +58,14 @@ def _close(got, want, tol, what):
 
 
 # "f32": each layer an exact fp32 fmaf chain (v_mfma_f32_32x32x2_f32); "f16x3" (the default): three fp16 products per
-# term — the bound below is the SAME 1e-4 for both, and the fp16 form is additionally held to 2e-5.  "w2" (the default):
-# two cooperating waves per 32-sample tile (field_fused2.hip, v_mfma_f32_16x16x32_f16); "w1": one wave per tile.
-PRECISIONS = pytest.mark.parametrize("precision", ["f16x3-w2", "f16x3-w1", "f32"])
+# term — the bound below is the SAME 1e-4 for both, and the fp16 form is additionally held to 2e-5.  The fp16 form is the
+# "w2" kernel: two cooperating waves per 32-sample tile (field_fused2.hip, v_mfma_f32_16x16x32_f16); the exact form runs
+# one wave per tile (field_fused.hip).
+PRECISIONS = pytest.mark.parametrize("precision", ["f16x3-w2", "f32"])
 
 
 def _select(f, precision):
     f.fused_field_precision = precision.split("-")[0]
-    f.fused_field_kernel = precision.split("-")[1] if "-" in precision else "w1"
 
 
 @PRECISIONS
@@ -161,7 +161,7 @@ def test_sh_half_rounding_reaches_the_fused_kernel(cuda):
     assert float((out["half", True] - out["float", True]).abs().max()) > 1e-6
 
 
-@pytest.mark.parametrize("kernel", ["w2", "w1"])
+@pytest.mark.parametrize("kernel", ["w2"])
 @pytest.mark.parametrize("cfg", ["f8_full", "f2_toy"])
 def test_fp16_range_guard(cuda, cfg, kernel):
     """The three-product kernels split operands into two halves: above fp16's 65504 that would be inf / NaN.  The guard
@@ -228,7 +228,7 @@ def test_fp16_range_guard(cuda, cfg, kernel):
         _close(a[keep], b[keep], 2e-5, what)
 
 
-@pytest.mark.parametrize("kernel", ["w2", "w1"])
+@pytest.mark.parametrize("kernel", ["w2"])
 def test_fused_field_is_repeatable(cuda, kernel):
     """The kernels have no atomics and a fixed summation order: the same call returns the same bits.  (A race between
     the two waves of a tile shows up here as a handful of rows of one tile differing in one call out of a few — that is
@@ -323,12 +323,12 @@ def test_fused_field_rgb_against_float64_at_full_size(cuda):
     assert rgb64.std() > 0.01
 
 
-@pytest.mark.parametrize("kernel", ["w2", "w1"])
+@pytest.mark.parametrize("kernel", ["w2"])
 @pytest.mark.parametrize("cfg", ["f8_full", "f2_toy"])
 def test_fused_field_with_a_row_count_on_the_device(cuda, cfg, kernel):
     """cnc_fused_field_t.n_rows_dev: the call works on min(N, count) rows, the count read on the device — the rows in front of
     it get the values of an exactly sized call bit for bit, nothing behind it is touched (positions there may be garbage), a
-    count beyond the capacity is the capacity, a count of zero does nothing.  Density-only and colour calls, both kernels,
+    count beyond the capacity is the capacity, a count of zero does nothing.  Density-only and colour calls, the fp16 kernel
     and the exact-fp32 form."""
     from cnc_amd import _lib
     f = _field(cuda, CONFIGS[cfg], seed=6)

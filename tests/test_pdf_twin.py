@@ -230,7 +230,7 @@ def test_pdf_rows_mirror_has_the_header_layout(tmp_path):
         assert int(out[n]) == getattr(_lib.PdfRows, n).offset, n
     for n in seg:
         assert int(out["seg." + n]) == _lib.PdfRows.seg.offset + getattr(_lib.RaySegments, n).offset, n
-    assert _lib.ABI_VERSION == 32
+    assert _lib.ABI_VERSION == 33       # the rows struct arrived with v32; v33 removed fused-field members only
 
 
 def test_proposal_api_refuses_cpu_tensors():
