@@ -1,6 +1,10 @@
 """HIP marcher + scans (through the `nerfacc.cuda` mirror) vs the CPU oracle.  Counts, masks,
 indices and t-values are bit-exact; the scans keep the reference's 32-wide tile association, so
-they are bit-exact too."""
+they are bit-exact too.
+
+The cases here that run at full size (640 k rays) hold properties and compare the GPU with
+itself; the marcher against the oracle at frame and batch size — every launch path, on poisoned
+buffers — is tests/test_gpu_march_matrix.py."""
 import numpy as np
 import pytest
 import torch
@@ -197,8 +201,9 @@ def test_scan_docstring_examples(cuda):
 
 
 def test_march_full_frame_properties(cuda):
-    """BASELINE size: 800x800 rays through the 128^3 ball occupancy (step 5e-3) — properties that
-    need no oracle: count pass == fill pass, samples ordered by (ray, t), every sample inside its
+    """BASELINE size: 800x800 rays through the 128^3 ball occupancy (step 5e-3) — properties,
+    checked without the oracle (tests/test_gpu_march_matrix.py holds the same frame against it):
+    count pass == fill pass, samples ordered by (ray, t), every sample inside its
     ray's box interval and inside an occupied cell, interval masks consistent."""
     from cnc_amd import synthetic
     from cnc_amd.nerfacc.grid import ray_aabb_intersect, traverse_grids
@@ -372,8 +377,8 @@ def test_march_positions_equal_the_separate_pass_on_the_bench_frame(cuda):
 
 
 def test_march_samples_resume_equals_whole_ray_march_on_the_bench_frame(cuda, monkeypatch):
-    """Full size, no oracle (the small cases above pin both forms to it): bench.py's own 800x800 frame, 640 k rays and
-    ~68 M samples.  The fill pass that resumes at each ray's first sample and stops at its last (constant-step kernels,
+    """Full size, GPU against GPU (tests/test_gpu_march_matrix.py::test_frame pins both forms to the
+    oracle at this size): bench.py's own 800x800 frame, 640 k rays and ~68 M samples.  The fill pass that resumes at each ray's first sample and stops at its last (constant-step kernels,
     16-entry staging) must write exactly what the fill pass that marches every ray end to end writes."""
     import bench
     from cnc_amd.backends import nerfacc_cuda as C
