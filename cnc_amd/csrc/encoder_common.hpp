@@ -236,11 +236,33 @@ struct UnitFast {
     float    wn;          // sum of m in corner order
 };
 
-template <uint32_t D, uint32_t F>
+// Width in bytes of the aligned word that serves both x-neighbours of a corner pair on the paired path (PAIR = true
+// below): 4, 8 or 16.  8 is what tools/gather_width_probe.hip and the per-level table favour
+// (profiles/r13_forward_pair_gather.md).
+#ifndef CNC_FWD_PAIR_BYTES
+#define CNC_FWD_PAIR_BYTES 8
+#endif
+
+// Byte `at` (0 .. W-1) of a W-byte word held as W/4 dwords, in bits 0..7 of the result: one v_perm_b32 (W = 16: two
+// selects first).  Bits 8..31 hold copies of the word's byte 0: the callers' consumers read bits 0..7 only.
+template <uint32_t W>
+__device__ __forceinline__ uint32_t pair_word_byte(const uint32_t (&w)[W / 4], uint32_t at)
+{
+    static_assert(W == 4 || W == 8 || W == 16, "one dword, dwordx2 or dwordx4 load");
+    if constexpr (W == 4) return __builtin_amdgcn_perm(w[0], w[0], at);
+    else if constexpr (W == 8) return __builtin_amdgcn_perm(w[1], w[0], at);
+    else return __builtin_amdgcn_perm((at & 8u) ? w[3] : w[1], (at & 8u) ? w[2] : w[0], at & 7u);
+}
+
+// PAIR (F = 8, a hashed power-of-two level of hs >= W rows, off % W == 0, `bits` W-aligned: the caller checks, per
+// wave): the gathers of the two x-neighbours of a corner pair become ONE aligned W-byte load where both bytes lie in
+// the same word; see the comment at the loads.  PAIR = false is the instruction stream every other caller keeps.
+template <uint32_t D, uint32_t F, bool PAIR = false>
 __device__ __forceinline__ void unit_issue_fast(const float (&x_)[D], bool inside, const uint8_t* __restrict__ bits,
                                                 const UnitRec& r, UnitFast& u)
 {
     static_assert(D == 2 || D == 3, "planes and volumes");
+    static_assert(!PAIR || F == 8, "the paired gathers take one byte per row");
     constexpr uint32_t C = 1u << D;
     float (&m)[8] = u.m;
     uint32_t (&rb)[8] = u.rb;
@@ -303,12 +325,57 @@ __device__ __forceinline__ void unit_issue_fast(const float (&x_)[D], bool insid
         m[i] = (!border && inside) ? wi : 0.0f;
         wn += m[i];
     }
-    // (Serving the two x-neighbours of a corner pair with ONE 16-bit load — adjacent bytes on a dense level, an aligned
-    // byte pair on a hashed level when the cell's x is even — was built and measured: level-major forward 0.218 -> 0.255 ms
-    // per 2^20 marched samples, fused field unchanged at 0.855 ms on uniform points; the selects and the second,
-    // conditional load cost more than the lookups saved.  One byte gather per corner it stays.)
+    // One byte gather per corner, or (PAIR) one word per x-neighbour pair.  Round 5 served a pair with one 16-bit load
+    // on EVERY level (adjacent bytes on a dense level, an aligned byte pair on a hashed one when the cell's x is even:
+    // 50 %) while the kernel was bound by vector issue: level-major forward 0.218 -> 0.255 ms per 2^20 marched samples.
+    // Since the sign table the hashed levels are bound by their gathers, and an aligned 8-byte word (7 cells of 8; a
+    // wider load costs the address path nothing, tools/gather_width_probe.hip) measures, per level of the bench table:
+    // R = 82 .. 563 faster (0.0113 .. 0.0158 -> 0.0106 .. 0.0145 ms, bound by L1 accesses, which fall 9.2 M -> 3.7 .. 5.6 M),
+    // R = 778 .. 2049 SLOWER (bound by L2 -> L1 line fills: the i1 byte gather hit the line i0 had just fetched, so there
+    // was nothing to save, and the paired path fetches 9 .. 37 % more lines).  Hence a per-level choice by the caller
+    // (k_grid_encode_fwd_bits: kFwdPairMinRes / kFwdPairMaxRes); whole call 0.196 -> 0.180 ms in the bench
+    // (profiles/r13_forward_pair_gather.md).
+    if constexpr (PAIR) {
+        // Hashed level, primes[0] == 1: the x-neighbours' rows are i0 = (g ^ h) & mask and i1 = ((g + 1) ^ h) & mask,
+        // so i0 ^ i1 = (g ^ (g + 1)) & mask = 2^(t+1) - 1 with t the trailing one bits of g: both bytes lie in one
+        // aligned W-byte word whenever that is < W (W = 8: g % 8 != 7, 7 lanes of 8) — tested on the indices
+        // themselves, not on g, so it holds whatever q1 is.  The word starts at (off + i0) & ~(W - 1) >= off (off is a
+        // multiple of W) and ends at or before off + hs (i0 < hs, hs a power of two >= W, hence a multiple of W): it
+        // never leaves the level's plane.  The remaining lanes fetch their i1 bytes as before, in one branch for
+        // all pairs.  pair_word_byte leaves junk above bit 7 of rb: unit_finish_fast shifts bit k < 8 up to bit 31 and
+        // unit_finish_lut takes the two low nibbles, so nothing masks it off.
+        constexpr uint32_t W = CNC_FWD_PAIR_BYTES;
+        uint32_t word[C / 2][W / 4];
+        bool     far = false;
 #pragma unroll
-    for (uint32_t i = 0; i < C; i++) rb[i] = load_row_bits<F>(bits, (uint64_t)(uint32_t)(r.off + index[i]));
+        for (uint32_t p = 0; p < C / 2; p++) {
+            const uint32_t a0 = r.off + index[2 * p];
+            const uint8_t* at = bits + (a0 & ~(W - 1u));
+            if constexpr (W == 4) word[p][0] = *reinterpret_cast<const uint32_t*>(at);
+            else if constexpr (W == 8) {
+                const uint2 v = *reinterpret_cast<const uint2*>(at);
+                word[p][0] = v.x, word[p][1] = v.y;
+            } else {
+                const uint4 v = *reinterpret_cast<const uint4*>(at);
+                word[p][0] = v.x, word[p][1] = v.y, word[p][2] = v.z, word[p][3] = v.w;
+            }
+            far = far | ((index[2 * p] ^ index[2 * p + 1]) >= W);
+        }
+        uint32_t lone[C / 2] = {};
+        if (far) {
+#pragma unroll
+            for (uint32_t p = 0; p < C / 2; p++) lone[p] = bits[r.off + index[2 * p + 1]];
+        }
+#pragma unroll
+        for (uint32_t p = 0; p < C / 2; p++) {
+            rb[2 * p] = pair_word_byte<W>(word[p], (r.off + index[2 * p]) & (W - 1u));
+            const uint32_t near = pair_word_byte<W>(word[p], (r.off + index[2 * p + 1]) & (W - 1u));
+            rb[2 * p + 1] = far ? lone[p] : near;
+        }
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < C; i++) rb[i] = load_row_bits<F>(bits, (uint64_t)(uint32_t)(r.off + index[i]));
+    }
     u.wn = wn;
 }
 

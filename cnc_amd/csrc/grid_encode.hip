@@ -137,6 +137,14 @@ __global__ __launch_bounds__(256) void k_pack_sign_bits(const float* __restrict_
 // ds_write_b128 / ds_read_b128), after which lane i of store s holds the 16-byte chunk s*64 + i of the tile in memory
 // order: level-major a wave's instruction writes 1 KB contiguous, point-major every instruction writes whole lines
 // (64 / Cp points x Cp*16 bytes).  The arithmetic is untouched (same corner order, same fmaf chain).
+//
+// Paired gathers (unit_issue_fast<.., PAIR>): the hashed levels in this window of resolutions take them.  There the
+// lanes of a wave still share lines and the level is bound by the number of L1 accesses, which the pairs nearly halve;
+// above it every lane is on lines of its own, the bound is the L2 -> L1 line fills, which the pairs leave as they are,
+// and the paired path measured slower (per-level table in profiles/r13_forward_pair_gather.md: R = 82 .. 563 gain,
+// R = 778 .. 2049 lose).
+constexpr uint32_t kFwdPairMinRes = 80, kFwdPairMaxRes = 660;
+
 template <uint32_t D, uint32_t F, bool VXL, bool TR>
 #ifndef CNC_FWD_BITS_BOUNDS
 #define CNC_FWD_BITS_BOUNDS __launch_bounds__(256)
@@ -146,7 +154,7 @@ __global__ CNC_FWD_BITS_BOUNDS void k_grid_encode_fwd_bits(
     const int32_t* __restrict__ offsets, const int32_t* __restrict__ resolutions,
     float* __restrict__ out, uint32_t N, uint32_t L, uint32_t P, uint32_t cp_log2, uint32_t Rb,
     const uint8_t* __restrict__ vxl, const int32_t* __restrict__ min_level_id, const int32_t* __restrict__ sat,
-    FeatLayout lay, uint32_t lut_mode)
+    FeatLayout lay, uint32_t lut_mode, uint32_t pair_mode)
 {
     constexpr uint32_t C = 1u << D;
     constexpr uint32_t V = F < 4 ? F : 4;
@@ -175,10 +183,11 @@ __global__ CNC_FWD_BITS_BOUNDS void k_grid_encode_fwd_bits(
         float  acc[F];
 #pragma unroll
         for (uint32_t k = 0; k < F; k++) acc[k] = 0;
-        // The lean evaluator (encoder_common.hpp, unit_features_fast: per-axis index parts, no per-corner branch, x-pair
-        // 16-bit gathers, shift + bfi signs — the same values bit for bit) whenever the level is the same for the whole
-        // grid row (no per-point windows) and is what a GridEncoder makes: dense (R^D rows fit) or hashed into a
-        // power-of-two table.  Anything else — odd caller-made tables, the occupancy mask — takes the general path below.
+        // The lean evaluator (encoder_common.hpp, unit_issue_fast + unit_finish_*: per-axis index parts, no per-corner
+        // branch, byte or paired-word gathers, sign table or shift + bfi — the same values bit for bit) whenever the
+        // level is the same for the whole grid row (no per-point windows) and is what a GridEncoder makes: dense (R^D
+        // rows fit) or hashed into a power-of-two table.  Anything else — odd caller-made tables, the occupancy mask —
+        // takes the general path below.
         bool done = false;
         if constexpr (!VXL && (D == 2 || D == 3)) {
             if (min_level_id == nullptr) {
@@ -191,8 +200,17 @@ __global__ CNC_FWD_BITS_BOUNDS void k_grid_encode_fwd_bits(
                 const bool dense = rd <= hs, pow2 = (hs & (hs - 1u)) == 0u;
                 if ((dense || pow2) && (off & 7u) == 0u) {
                     // the sign table (lut_mode 1: every level, 2: dense levels only) or shift + bfi
+                    // the paired gathers (pair_mode 1: hashed levels of kFwdPairMinRes <= R < kFwdPairMaxRes; 2: every
+                    // hashed level that qualifies; the host passes 0 for a misaligned plane)
                     UnitFast u;
-                    unit_issue_fast<D, F>(x, inside, bits, UnitRec{off, hs, R, 0u}, u);
+                    bool pair = false;
+                    if constexpr (F == 8) {
+                        constexpr uint32_t W = CNC_FWD_PAIR_BYTES;
+                        pair = !dense && hs >= W && (off & (W - 1u)) == 0u &&
+                               (pair_mode == 2 || (pair_mode == 1 && R >= kFwdPairMinRes && R < kFwdPairMaxRes));
+                        if (pair) unit_issue_fast<D, F, true>(x, inside, bits, UnitRec{off, hs, R, 0u}, u);
+                    }
+                    if (!pair) unit_issue_fast<D, F>(x, inside, bits, UnitRec{off, hs, R, 0u}, u);
                     bool lut = false;
                     if constexpr (LUT) {
                         lut = lut_mode == 1 || (lut_mode == 2 && dense);
@@ -1071,11 +1089,15 @@ static void launch_fwd_bits(const float* inputs, const uint8_t* bits, const int3
     lay.nt = (nt_mode == 1 && lay.ld == 0) || (nt_mode == 2 && tr) ? 1u : 0u;
     // sign table of the lean evaluator (CNC_FWD_LUT: 0 shift + bfi, 1 every level, 2 dense levels only)
     const uint32_t lut_mode = getenv("CNC_FWD_LUT") ? (uint32_t)atoi(getenv("CNC_FWD_LUT")) : 1u;
+    // paired x-neighbour gathers of the lean evaluator (CNC_FWD_PAIR: 0 off, 1 hashed levels inside the kFwdPair*Res
+    // window, 2 every hashed level that qualifies: measurement switch); the words are aligned loads, so the plane has to be
+    uint32_t pair_mode = getenv("CNC_FWD_PAIR") ? (uint32_t)atoi(getenv("CNC_FWD_PAIR")) : 1u;
+    if (reinterpret_cast<uintptr_t>(bits) & (CNC_FWD_PAIR_BYTES - 1u)) pair_mode = 0;
     const dim3 grid(div_up(N, 256), div_up(L, P), 1);
     const size_t lds = tr ? (size_t)256 * W * sizeof(float) : 0;
 #define CNC_FWD_BITS(VX, TRV)                                                                                        \
     hipLaunchKernelGGL((k_grid_encode_fwd_bits<D, F, VX, TRV>), grid, dim3(256), TRV ? lds : 0, s, inputs, bits, offsets, \
-                       resolutions, outputs, N, L, P, cp_log2, Rb, vxl, mli, VX ? sat : nullptr, lay, lut_mode)
+                       resolutions, outputs, N, L, P, cp_log2, Rb, vxl, mli, VX ? sat : nullptr, lay, lut_mode, pair_mode)
     if (vxl) { if (tr) CNC_FWD_BITS(true, true); else CNC_FWD_BITS(true, false); }
     else     { if (tr) CNC_FWD_BITS(false, true); else CNC_FWD_BITS(false, false); }
 #undef CNC_FWD_BITS

@@ -2,9 +2,11 @@
 800x800 frame), 16L x 2^19 x F8, the sign bit plane of the bench's table.  Times the whole call (L = 16, level-major
 [L, N, F]) and each level alone as an L = 1 call on that level's offsets and resolution views, under each sign-table
 mode (CNC_FWD_LUT, read per launch: 0 shift + bfi, 1 table on every level, 2 on the dense levels).  One JSON line per
-row.
+row.  --pair: the same rows under the paired-gather modes instead (CNC_FWD_PAIR, read per launch: 0 byte gathers, 1 the
+default policy, 2 every hashed level), sign table as shipped, the modes alternating twice per row.
 
     python tools/fwd_levels.py                    # the table
+    python tools/fwd_levels.py --pair 0,2         # per level: byte gathers against paired gathers
     python tools/fwd_levels.py --only 15,3,all --reps 3   # just these calls in this order, `reps` each: for a
                                                           # counter run (rocprofv3 --pmc ... --); 'all' = the L = 16 call
 """
@@ -39,6 +41,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None, help="comma-separated level indices, 'all' for the L = 16 call")
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--pair", default=None, help="comma-separated CNC_FWD_PAIR modes to compare per row")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     w = bench.build_workload(dev, 0)
@@ -62,6 +65,27 @@ def main():
             for _ in range(args.reps):
                 fn()
             torch.cuda.synchronize()
+        return
+    if args.pair is not None:
+        os.environ.pop("CNC_FWD_LUT", None)
+        pairs = args.pair.split(",")
+        total = dict.fromkeys(pairs, 0.0)
+        for l in [None] + list(range(L)):
+            row = {"levels": "all", "N": N} if l is None else {
+                "level": l, "R": int(bench.synthetic.RES_16L[l]), "rows": int(w["offsets_host"][l + 1] - w["offsets_host"][l])}
+            ms = {m: [] for m in pairs}
+            for _ in range(2):
+                for m in pairs:
+                    os.environ["CNC_FWD_PAIR"] = m
+                    ms[m].append(round(timeit(call(l), args.reps), 4))
+            for m in pairs:
+                row["ms_pair%s" % m] = ms[m]
+                if l is not None:
+                    total[m] += min(ms[m])
+            print(json.dumps(row), flush=True)
+        print(json.dumps({"levels": "sum of the L = 1 calls (min of the two passes)",
+                          **{"ms_pair" + k: round(v, 4) for k, v in total.items()}}))
+        del os.environ["CNC_FWD_PAIR"]
         return
     modes = ("0", "1", "2")
     for lut in modes:
