@@ -11,6 +11,15 @@ import sys
 __version__ = "0.1.0"
 
 
+def __getattr__(name):
+    # `cnc_amd.ordered_backward`: the process-wide switch of the ordered (bit-reproducible) encoder backward, resolved
+    # on first use so that importing the package does not import torch
+    if name == "ordered_backward":
+        from .backends.gridencoder_backend import ordered_backward
+        return ordered_backward
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def install_dropins(force: bool = False) -> None:
     """Register the host mirrors under the reference's import names, so that the reference's own Python
     (`import _gridencoder as _backend` ngp.py:10, `import pack_and_align`, `import torchac` utils_bpp_acc.py:4-8,

@@ -102,6 +102,9 @@ SIGNATURES = {
     "cnc_grid_encode_backward_overlapped_workspace": [_u32, _u32, _u32],
     "cnc_grid_encode_backward_overlapped": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _u32,
                                             _u32, _u32, _vp, C.c_uint64, _vp],
+    "cnc_grid_encode_backward_ordered_workspace": [_u32, _u32, C.c_uint64],
+    "cnc_grid_encode_backward_ordered": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp,
+                                         _vp, _vp, _u32, _u32, _vp, C.c_uint64, _vp],
     "cnc_pack_sign_bits": [_vp, _vp, C.c_uint64, _u32, _vp, _vp],
     "cnc_grid_encode_forward_bits": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp],
     "cnc_mlp_forward32": [_vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp],
@@ -186,7 +189,8 @@ SIGNATURES = {
 
 # entry points that return something other than a status code
 RESTYPES = {"cnc_grid_encode_backward_binned_workspace": C.c_uint64,
-            "cnc_grid_encode_backward_overlapped_workspace": C.c_uint64, "cnc_bernoulli_bits_partials": C.c_uint32,
+            "cnc_grid_encode_backward_overlapped_workspace": C.c_uint64,
+            "cnc_grid_encode_backward_ordered_workspace": C.c_uint64, "cnc_bernoulli_bits_partials": C.c_uint32,
             "cnc_relu_backward_bias_partials": C.c_uint32, "cnc_occupancy_coarse_words": C.c_uint32}
 
 CNC_FLAG_STE_BINARY = 1
@@ -196,6 +200,7 @@ CNC_FLAG_CELL_MERGE = 8
 CNC_FLAG_CELL_CARRY = 16
 CNC_FLAG_OWNER_XCD_PAIRS = 32
 CNC_FLAG_MERGE_CONSECUTIVE = 64
+CNC_ORDERED_KEY_BITS_SHIFT = 24
 CNC_FIELD_SH_FP16 = 1
 CNC_FIELD_MFMA_F16X3 = 2
 CNC_FIELD_WAVES4 = 8

@@ -137,13 +137,18 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
                          N, num_dim, n_features, n_levels, max_level, Rb, dy_dx=None,
                          grad_inputs=None, binary_vxl=None, min_level_id=None, *, ste_binary=False,
                          ste_clip_count=None, occ_sat=None, grad_ld=0, grad_col=0, binned=None,
-                         interleave_levels=False, overlap_streams=True, vertex_bits=None, cell_merge=False, cell_carry=False):
+                         interleave_levels=False, overlap_streams=True, vertex_bits=None, cell_merge=False, cell_carry=False,
+                         ordered=None):
     """gridencoder.h:24-36.  `binned` (extension) = (n_binned, level_rows) from `plan_binned_levels`:
     take that many finest levels off the global-atomic path (cnc_grid_encode_backward_binned).
     `interleave_levels` (extension, same result): CNC_FLAG_LEVELS_FINEST_FIRST for the plain entry —
     for calls whose tables are small enough to stay cached while all levels are in flight.
     `cell_merge` / `cell_carry` (extension, same result to fp32 summation order): CNC_FLAG_CELL_MERGE / _CARRY — the
-    masked / per-point-level calls of a training step's context pass (grid_encode_cells.hip)."""
+    masked / per-point-level calls of a training step's context pass (grid_encode_cells.hip).
+    `ordered` (extension): True = cnc_grid_encode_backward_ordered, the gradient bit-equal to the serial oracle's sum in
+    (level slot, point, corner) order and so the same from run to run; the route arguments above are then ignored.
+    False = the routes above.  None = `ordered_backward_enabled()`: the process-wide mode, CNC_ORDERED_BACKWARD=1,
+    torch.are_deterministic_algorithms_enabled()."""
     _common_checks([("grad", grad), ("inputs", inputs), ("embeddings", embeddings),
                     ("offsets_list", offsets_list), ("resolutions_list", resolutions_list),
                     ("grad_embeddings", grad_embeddings)])
@@ -162,6 +167,24 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
         raise RuntimeError("GridEncoding: num_dim must be 1, 2, 3.")
     if binary_vxl is not None:
         binary_vxl = binary_vxl.contiguous()
+    if ordered_backward_enabled() if ordered is None else ordered:
+        L = _lib.lib()
+        rows_total = int(embeddings.shape[0])
+        nbytes = int(L.cnc_grid_encode_backward_ordered_workspace(int(N), int(num_dim), rows_total))
+        st = stream(grad.device)
+        ws = _workspace(grad.device, nbytes, (st, "ordered"))      # a key of its own per (device, stream)
+        ROUTE_CALLS["ordered"] += 1
+        rc = L.cnc_grid_encode_backward_ordered(
+            ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets_list), ptr(resolutions_list),
+            ptr(grad_embeddings), int(N), int(num_dim), int(n_features), int(n_levels), int(Rb),
+            ptr(dy_dx), ptr(grad_inputs), ptr(binary_vxl), ptr(min_level_id),
+            (_lib.CNC_FLAG_STE_BINARY if ste_binary else 0)
+            | (max(rows_total.bit_length(), 1) << _lib.CNC_ORDERED_KEY_BITS_SHIFT), ptr(ste_clip_count),
+            ptr(_check_sat(occ_sat, binary_vxl)), *_vb(vertex_bits, binary_vxl, 0 if min_level_id is not None else n_levels),
+            int(grad_ld), int(grad_col), ptr(ws), nbytes, st)
+        check(rc, "grid_encode_backward_ordered")
+        return
+    ROUTE_CALLS["default"] += 1
     if binned is not None and binned[0] > 0 and binary_vxl is None and min_level_id is None \
             and dy_dx is None and grad_inputs is None:
         n_binned, level_rows = int(binned[0]), int(binned[1])
@@ -206,6 +229,38 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
 
 _WORKSPACES = {}
 _PLANS = {}
+ROUTE_CALLS = {"ordered": 0, "default": 0}     # grid_encode_backward calls per route, for tests and tools to read
+_ORDERED_MODE = None                             # process-wide: None = not set, else bool (`ordered_backward`)
+
+
+class ordered_backward:
+    """Process-wide switch of the ordered encoder backward (`grid_encode_backward(..., ordered=None)`), as a plain
+    setter — `ordered_backward(True)` — or a context manager that restores the previous state on exit.  Process-wide
+    and not thread-local on purpose: the encoder's backward runs on autograd's device thread and the entropy pass on a
+    host thread of its own, and both must follow the mode the caller's thread set."""
+
+    def __init__(self, enabled=True):
+        global _ORDERED_MODE
+        self._prev = _ORDERED_MODE
+        _ORDERED_MODE = None if enabled is None else bool(enabled)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _ORDERED_MODE
+        _ORDERED_MODE = self._prev
+        return False
+
+
+def ordered_backward_enabled():
+    """What `ordered=None` resolves to: the process-wide mode if set, else CNC_ORDERED_BACKWARD=1 (read per call), else
+    torch's deterministic-algorithms switch."""
+    if _ORDERED_MODE is not None:
+        return _ORDERED_MODE
+    if os.environ.get("CNC_ORDERED_BACKWARD") == "1":
+        return True
+    return torch.are_deterministic_algorithms_enabled()
 _OVERLAP_ENABLED = os.environ.get("CNC_BWD_OVERLAP", "1") != "0"   # measurement switch (profiles/)
 _BIN_LANE_STORES = os.environ.get("CNC_BWD_BIN_LANE_STORES", "0") == "1"   # measurement switch: the round-2 bin pass
 _OWNER_XCD_PAIRS = os.environ.get("CNC_BWD_OWNER_XCD_PAIRS", "0") == "1"   # measurement switch: owner waves of a level on 4 of 8 XCD labels

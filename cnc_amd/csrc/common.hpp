@@ -51,6 +51,14 @@ __device__ __forceinline__ size_t feat_index(FeatLayout lay, uint32_t slot, uint
     return lay.ld ? (size_t)b * lay.ld + lay.col + slot * F : ((size_t)slot * N + b) * F;
 }
 
+// point-major layout: rows must hold the encoder's block and keep the vector accesses aligned
+inline bool layout_ok(FeatLayout lay, uint32_t F, uint32_t L)
+{
+    if (lay.ld == 0) return lay.col == 0;
+    const uint32_t V = F < 4 ? F : 4;
+    return lay.col + L * F <= lay.ld && lay.ld % V == 0 && lay.col % V == 0;
+}
+
 // grid_encode.hip / grid_encode_merge.hip: the coarse call of the overlapped entry (grid_encode_overlap.hip)
 int grid_encode_backward_with_scratch(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
                                       const int32_t* resolutions, float* grad_embeddings, uint32_t N, uint32_t D, uint32_t F,

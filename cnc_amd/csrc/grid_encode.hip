@@ -910,14 +910,6 @@ static int dispatch_D(const EncArgs& a, uint32_t D, uint32_t F, bool ste)
     }
 }
 
-// point-major layout: rows must hold the encoder's block and keep the vector accesses aligned
-static bool layout_ok(FeatLayout lay, uint32_t F, uint32_t L)
-{
-    if (lay.ld == 0) return lay.col == 0;
-    const uint32_t V = F < 4 ? F : 4;
-    return lay.col + L * F <= lay.ld && lay.ld % V == 0 && lay.col % V == 0;
-}
-
 // grid_input_grad.hip
 int launch_dy_dx(const float* inputs, const float* emb, const int32_t* offsets, const int32_t* resolutions,
                  float* dy_dx, uint32_t N, uint32_t D, uint32_t F, uint32_t L, const int32_t* mli, bool ste,

@@ -83,7 +83,7 @@ class _grid_encode(Function):
     @staticmethod
     def forward(ctx, inputs, embeddings, offsets_list, resolutions_list, calc_grad_inputs=False,
                 min_level_id=None, n_levels_calc=1, binary_vxl=None, PV=0, ste=False, bits=None,
-                clip_count=None, occ_sat=None, binned=None, vertex_bits=None):
+                clip_count=None, occ_sat=None, binned=None, vertex_bits=None, ordered=None):
         inputs = inputs.contiguous()
         if calc_grad_inputs:
             # dead in the reference too (ngp.py:58-60)
@@ -129,6 +129,7 @@ class _grid_encode(Function):
         # the caller thread's gradient sink (cnc_amd._gradsink), taken HERE: the backward below runs on autograd's
         # device thread, where the caller's thread-local is not visible
         ctx.sink = _gradsink.current()
+        ctx.ordered = ordered      # the module's override of the ordered-backward mode (None: the process-wide one)
         return outputs
 
     @staticmethod
@@ -153,8 +154,9 @@ class _grid_encode(Function):
                                       occ_sat=occ_sat, binned=ctx.binned,
                                       grad_ld=n_levels_calc * n_features, grad_col=0,
                                       vertex_bits=None if vb_words is None else (vb_words, vb_offs),
-                                      cell_merge=cells, cell_carry=cells and (mli is not None or n_levels_calc == 1))
-        return (None, grad_embeddings if sunk is None else None) + (None,) * 13
+                                      cell_merge=cells, cell_carry=cells and (mli is not None or n_levels_calc == 1),
+                                      ordered=ctx.ordered)
+        return (None, grad_embeddings if sunk is None else None) + (None,) * 14
 
 
 _CELL_MERGE = os.environ.get("CNC_CELL_MERGE", "1") != "0"      # measurement switch (tools/ab_train.py)
@@ -166,7 +168,7 @@ class GridEncoder(nn.Module):
     def __init__(self, num_dim=3, n_features=2,
                  resolutions_list=(16, 23, 32, 46, 64, 92, 128, 184, 256, 368, 512, 736),
                  log2_hashmap_size=19, ste_binary=False, ste_multistep=False, add_noise=False, Q=1,
-                 fused_ste=True, bitplane=True):
+                 fused_ste=True, bitplane=True, ordered_backward=None):
         super().__init__()
         resolutions_list = torch.as_tensor(np.asarray(resolutions_list)).to(torch.int)
         n_levels = resolutions_list.numel()
@@ -180,6 +182,9 @@ class GridEncoder(nn.Module):
         self.add_noise = add_noise
         self.Q = Q
         self.fused_ste = fused_ste
+        # table gradient bit-equal to the serial oracle's sum (gridencoder_backend.grid_encode_backward, `ordered`):
+        # True / False override the process-wide mode (cnc_amd.ordered_backward) for this module, None follows it
+        self.ordered_backward = ordered_backward
         # bit-plane gather for binarised tables (needs the fused STE path); the packed plane is
         # cached until the table is modified in place (optimizer step bumps Tensor._version)
         self.bitplane = bitplane and fused_ste
@@ -315,7 +320,7 @@ class GridEncoder(nn.Module):
                               min_level_id, n_levels_calc, binary_vxl, PV, ste, bits, clip,
                               self._occ_sat(binary_vxl),
                               self._binned_plan(inputs.shape[0], min_level_id, max_level_id, binary_vxl),
-                              self._occ_vertex_bits(binary_vxl))
+                              self._occ_vertex_bits(binary_vxl), self.ordered_backward)
         return outputs.view(prefix_shape + [n_levels_calc * self.n_features])
 
     def forward_diff_levels(self, inputs, min_level_id_list=None, n_levels_calc=1, test_phase=False,
@@ -328,7 +333,7 @@ class GridEncoder(nn.Module):
         bits, clip = self._bit_plane(params) if (ste and self.bitplane) else (None, None)
         outputs = grid_encode(inputs, embeddings, self.offsets_list, self.resolutions_list, False,
                               min_level_id_list.contiguous(), n_levels_calc, binary_vxl, PV, ste, bits, clip,
-                              self._occ_sat(binary_vxl), None, self._occ_vertex_bits(binary_vxl))
+                              self._occ_sat(binary_vxl), None, self._occ_vertex_bits(binary_vxl), self.ordered_backward)
         return outputs.view(prefix_shape + [n_levels_calc * self.n_features])
 
     def forward_given_params(self, inputs, offsets_list, resolutions_list, outspace_params=None,
@@ -338,5 +343,5 @@ class GridEncoder(nn.Module):
         prefix_shape = list(inputs.shape[:-1])
         inputs = inputs.view(-1, 2)
         outputs = grid_encode(inputs, outspace_params, offsets_list, resolutions_list, False, 0, 1,
-                              binary_vxl, PV, False, None, None, self._occ_sat(binary_vxl))
+                              binary_vxl, PV, False, None, None, self._occ_sat(binary_vxl), None, None, self.ordered_backward)
         return outputs.view(prefix_shape + [self.n_features])

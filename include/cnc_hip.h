@@ -223,6 +223,54 @@ int cnc_grid_encode_backward_overlapped(cnc_backward_plan* plan, const float* gr
                                         uint32_t n_binned, uint32_t level_rows,
                                         void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* ---- Ordered backward: gradients bit-equal to the serial oracle (no counterpart in the reference) ----
+ * Every entry above adds in whatever order its atomics, bin reservations and LDS tickets fall ("same result to fp32
+ * summation order").  This one takes the inputs of cnc_grid_encode_backward, same meaning, and leaves every element
+ * (row, ch) of grad_embeddings equal to this fp32 computation, the serial sum of oracle/cnc_oracle.c (orc_bwd_point):
+ *
+ *     acc = grad_embeddings[row][ch] as it was when the call began
+ *     for k in 0 .. L-1:                    level slot; level = (min_level_id ? min_level_id[b] : 0) + k
+ *       for b in 0 .. N-1:                  points outside [0,1]^D contribute nothing
+ *         for c in 0 .. 2^D-1:              corner order of the forward (bit d of c = upper vertex along axis d)
+ *           if corner c of (b, level) is valid (not border, passes the occupancy mask) and lands on `row`:
+ *             if CNC_FLAG_STE_BINARY and not (-1 <= embeddings[row][ch] <= 1): continue
+ *             t   = w[c] * wn_re            one rounded fp32 multiply
+ *             acc = acc + t * grad[k][b][ch]   one rounded multiply, one rounded add, never an fma
+ *
+ * so the result is identical from run to run, stream to stream and rank to rank.  Per slot: every (point, corner) is
+ * written to a fixed place with its row as key, a stable radix sort orders the items by (row, point, corner), and
+ * one lane per row and channel carries the sum from start to end (cnc_amd/csrc/grid_encode_ordered.hip).  No atomics,
+ * no host synchronisation, no allocation: everything is ordered on `stream` and can sit in a captured graph.  A mode
+ * for reproducibility, debugging and exact regression tests: several times slower than the routes above
+ * (profiles/ordered_backward.md), which stay the default.
+ *   Serves D in {1,2,3}, F in {1,2,4,8,16,32}, binary_vxl with or without occ_sat / vertex_bits, min_level_id,
+ *   CNC_FLAG_STE_BINARY with or without ste_clip_count, grad_ld / grad_col; dy_dx / grad_inputs go through the
+ *   per-point kernel of the plain entry (no atomics there).  The scheduling and measurement flags of the other
+ *   routes are ignored.  N * 2^D must stay below 2^32 - 8 (CNC_ERR_INVALID_VALUE otherwise).
+ *   flags     : CNC_ORDERED_KEY_BITS(n), optional: the caller's promise that every table row the call can touch is
+ *               below 2^n - 1 (n = ceil(log2(rows_total + 1)) for a table of rows_total rows); the sort then runs
+ *               over n key bits instead of 32.  Same result.
+ *   workspace : cnc_grid_encode_backward_ordered_workspace(N, D, rows_total) bytes, 16-byte aligned, sized for ONE
+ *               slot (the slots reuse it); rows_total = rows of the whole table, < 2^32 - 1.  Less returns
+ *               CNC_ERR_INVALID_VALUE.  Nothing is assumed about its contents, which are dead after the call.  The
+ *               size function asks the sort for its scratch and needs a current HIP device; it returns 0 without
+ *               one, for N = 0 and for sizes the entry refuses.
+ *   Calls that target the same grad_embeddings must be stream-ordered (plain read-modify-writes).              */
+#define CNC_ORDERED_KEY_BITS_SHIFT 24
+#define CNC_ORDERED_KEY_BITS(n) ((uint32_t)(n) << CNC_ORDERED_KEY_BITS_SHIFT)   /* n in 1 .. 32; 0 = 32 */
+uint64_t cnc_grid_encode_backward_ordered_workspace(uint32_t N, uint32_t D, uint64_t rows_total);
+int cnc_grid_encode_backward_ordered(const float* grad, const float* inputs, const float* embeddings,
+                                     const int32_t* offsets, const int32_t* resolutions,
+                                     float* grad_embeddings,
+                                     uint32_t N, uint32_t D, uint32_t F, uint32_t L, uint32_t Rb,
+                                     const float* dy_dx, float* grad_inputs,
+                                     const uint8_t* binary_vxl, const int32_t* min_level_id,
+                                     uint32_t flags, const uint32_t* ste_clip_count,
+                                     const int32_t* occ_sat,
+                                     const uint32_t* vertex_bits, const int32_t* vertex_bit_offsets,
+                                     uint32_t grad_ld, uint32_t grad_col,
+                                     void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* cnt_np_embed (gridencoder.h:39-44, gridencoder.cu:873-970): ±1 vote counts of the finest 3-D
  * level projected on a plane.  inputs i16 [N,3]; embeddings_clip [hashmap_size, F] f32;
  * outputs [res-2, res-2, F, 2] f32, ACCUMULATED into (caller zero-fills, utils_bpp_acc.py:39).
