@@ -109,10 +109,10 @@ class TableAdam:
                 torch._foreach_zero_(counters)
         b1, b2 = g["betas"]
         lr = g["lr"]
-        self.steps_done += 1
         _lib.check(_lib.lib().cnc_table_adam(C.byref(a), float(lr), float(b1), float(b2), float(g["eps"]),
-                                             float(g["weight_decay"]), float(self.steps_done),
+                                             float(g["weight_decay"]), float(self.steps_done + 1),
                                              torch.cuda.current_stream(self.tables[0].device).cuda_stream), "cnc_table_adam")
+        self.steps_done += 1           # behind the call: a refused step has changed nothing on the device, nor here
         # the kernel writes the tables through their addresses: `Tensor._version` does not move, so the copies keyed on it
         # (the encoders' sign bit planes, packed weights) are dropped here as after any optimizer step (cnc_amd._caches)
         _caches.invalidate_all()

@@ -3,8 +3,11 @@ against torch.optim.Adam — the optimizer the reference steps (examples/train_C
 against the float64 formula; then inside the Trainer against the step that flushes the pieces into `.grad` first."""
 import ctypes
 
+import numpy as np
 import pytest
 import torch
+
+import adam_twin
 
 pytestmark = pytest.mark.gpu
 
@@ -48,6 +51,7 @@ def test_table_adam_against_the_library_optimizer_and_float64(cuda, wd):
     m64 = [torch.zeros_like(t) for t in p64]
     v64 = [torch.zeros_like(t) for t in p64]
     b1, b2 = 0.9, 0.999
+    twin = [(t.cpu().numpy().reshape(-1), np.zeros(t.numel(), np.float32), np.zeros(t.numel(), np.float32)) for t in init]
     for step in range(1, 7):
         opt_a.param_groups[1]["lr"] = opt_b.param_groups[1]["lr"] = lr = 6e-3 * (0.5 + 0.1 * step)   # a schedule moves it
         pcs = _pieces(shapes, 100 + step, cuda)
@@ -78,6 +82,14 @@ def test_table_adam_against_the_library_optimizer_and_float64(cuda, wd):
             assert float((sa["exp_avg_sq"] - sb["exp_avg_sq"]).abs().max()) <= 4e-7 * float(sb["exp_avg_sq"].abs().max())
             # and neither drifts from the float64 recurrence (fp32 state: ~1e-7 per step)
             assert float((mine[k].detach().double() - p64[k]).abs().max()) <= 2e-6 * scale, (step, k)
+            # per element, not per table: every bit is the NumPy twin's (tests/adam_twin.py)
+            F, n = shapes[k][1], init[k].numel()
+            host = [(gt.cpu().numpy().reshape(-1), 0 if rows is None else rows[0] * F, n if rows is None else rows[1] * F)
+                    for gt, rows in pcs[k]]
+            want = adam_twin.adam_step(*twin[k], host, n, lr, b1, b2, 1e-15, wd, step)
+            for got, bits in ((mine[k], want.p), (sa["exp_avg"], want.m), (sa["exp_avg_sq"], want.v)):
+                assert np.array_equal(got.detach().cpu().numpy().reshape(-1).view(np.uint32), bits.view(np.uint32)), (step, k)
+            twin[k] = (want.p, want.m, want.v)
         assert torch.equal(other_a, other_b)
     # the state is the library optimizer's own: a step through the library continues from it
     for p, q, pc in zip(mine, ref, _pieces(shapes, 999, cuda)):
