@@ -17,6 +17,13 @@ def __getattr__(name):
     if name == "ordered_backward":
         from .backends.gridencoder_backend import ordered_backward
         return ordered_backward
+    # `cnc_amd.reproducible` / `reproducible_enabled` / `REPRODUCIBLE_ROUTE_CALLS`: the reproducible mode (cnc_amd._repro)
+    if name in ("reproducible", "reproducible_enabled"):
+        from . import _repro
+        return getattr(_repro, name)
+    if name == "REPRODUCIBLE_ROUTE_CALLS":
+        from . import _repro
+        return _repro.ROUTE_CALLS
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -160,6 +160,8 @@ SIGNATURES = {
     "cnc_level_stats_backward": [_vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _vp, _vp],
     "cnc_field_prepare": [_vp, _vp, _u32, _vp, _vp, _vp],
     "cnc_field_pack_all": [C.POINTER(FieldPack), _vp],
+    "cnc_field_backward_chain_ordered_workspace": [C.POINTER(FieldBwd)],
+    "cnc_field_backward_chain_ordered": [C.POINTER(FieldBwd), _vp, C.c_uint64, _vp],
     "cnc_field_backward_chain": [C.POINTER(FieldBwd), _vp],
     "cnc_field_weight_grads_workspace": [C.POINTER(FieldWGrad), C.POINTER(C.c_uint64)],
     "cnc_field_weight_grads": [C.POINTER(FieldWGrad), _vp],
@@ -173,6 +175,9 @@ SIGNATURES = {
     "cnc_field_post_backward": [_vp, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _vp],
     "cnc_ctx_mlp_forward": [_vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _u32] + [_vp] * 6 + [_vp, _vp],
     "cnc_ctx_mlp_backward": [_vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _u32] + [_vp] * 6 + [_vp] * 10 + [_u32, _u32, _u32, _u32, _vp],
+    "cnc_ctx_mlp_backward_ordered_workspace": [_u32, _u32, _u32, _u32, _u32],
+    "cnc_ctx_mlp_backward_ordered": [_vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _u32, _u32] + [_vp] * 6 + [_vp] * 10
+                                    + [_u32, _u32, _vp, C.c_uint64, _vp],
     "cnc_ctx_window_gather": [_vp] * 8,
     "cnc_rows_scatter": [_vp, _vp, _vp, C.c_uint64, _u32, _vp],
     "cnc_table_adam": [_vp] + [C.c_double] * 6 + [_vp],
@@ -191,6 +196,7 @@ SIGNATURES = {
 RESTYPES = {"cnc_grid_encode_backward_binned_workspace": C.c_uint64,
             "cnc_grid_encode_backward_overlapped_workspace": C.c_uint64,
             "cnc_grid_encode_backward_ordered_workspace": C.c_uint64, "cnc_bernoulli_bits_partials": C.c_uint32,
+            "cnc_ctx_mlp_backward_ordered_workspace": C.c_uint64, "cnc_field_backward_chain_ordered_workspace": C.c_uint64,
             "cnc_relu_backward_bias_partials": C.c_uint32, "cnc_occupancy_coarse_words": C.c_uint32}
 
 CNC_FLAG_STE_BINARY = 1

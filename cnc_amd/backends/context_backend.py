@@ -21,6 +21,27 @@ def _f32c(t, name):
 _REPLICAS = 16        # zeroed copies of the weight-gradient buffer per backward call
 
 
+def _mlp_backward(ordered, dev, in_a, lda, Ca, in_b, ldb, Cb, pg, pg_index, n_pg, N, n_layers, F, ws, g, g_a, g_b, g_pg, gws,
+                  reps, stride, ldga, ldgb):
+    """One cnc_ctx_mlp_backward call on raw pointers — or, under the reproducible mode (cnc_amd._repro), its ordered
+    form, which ignores the replicas (it adds into copy 0) and takes its scratch from the per-(device, stream) workspace."""
+    from .. import _repro
+    L, st = _lib.lib(), stream(dev)
+    if ordered:
+        from .gridencoder_backend import _workspace
+        C = Ca + (Cb if in_b else 0) + (1 if pg else 0)
+        n_pg = 0 if not (pg and g_pg) else (int(n_pg) if pg_index else 1)
+        nbytes = int(L.cnc_ctx_mlp_backward_ordered_workspace(N, n_layers, F, C, n_pg))
+        wsp = _workspace(dev, max(nbytes, 16), (st, "ctx_ordered"))
+        _repro.ROUTE_CALLS["ctx_ordered"] += 1
+        check(L.cnc_ctx_mlp_backward_ordered(in_a, lda, Ca, in_b, ldb, Cb, pg, pg_index, n_pg, N, n_layers, F, *ws, g, g_a, g_b,
+                                             g_pg, *gws, ldga, ldgb, wsp.data_ptr(), wsp.numel(), st), "ctx_mlp_backward_ordered")
+        return
+    _repro.ROUTE_CALLS["ctx_default"] += 1
+    check(L.cnc_ctx_mlp_backward(in_a, lda, Ca, in_b, ldb, Cb, pg, pg_index, N, n_layers, F, *ws, g, g_a, g_b, g_pg, *gws,
+                                 reps, stride, ldga, ldgb, st), "ctx_mlp_backward")
+
+
 class ContextMLP(Function):
     """y = MLP([in_a | in_b | pg]) per row — `seq` is the reference's nn.Sequential: one Linear (the 2-D
     heads) or Linear-LeakyReLU-Linear-LeakyReLU-Linear (context_model_3D).  in_b / pg may be None."""
@@ -70,27 +91,27 @@ class ContextMLP(Function):
         # With a gradient sink on this thread (the training step, cnc_amd._gradsink) the weight gradients of every head
         # call of the step accumulate in the sink's replicated buffer — zeroed once, reduced once — and autograd gets
         # none; only the (tiny) Pg gradient is still a fresh zero-filled vector per call.
-        from .. import _gradsink
+        from .. import _gradsink, _repro
+        ordered = _repro.reproducible_enabled()
         sink = ctx.sink
         slots = None if sink is None else sink.small_slot(ws)
         if slots is not None:
             g_pg = torch.zeros(n_pg, dtype=torch.float32, device=dev) if pgv is not None else None
-            check(_lib.lib().cnc_ctx_mlp_backward(ptr(in_a), Ca, Ca, ptr(in_b), Cb, Cb, ptr(pgv), ptr(pg_index), N, n_layers, F,
-                                                  *[ptr(w) for w in ws], ptr(g), ptr(g_a), ptr(g_b), ptr(g_pg),
-                                                  *[ptr(w) for w in slots], _gradsink.REPLICAS, sink.stride(), 0, 0, stream(dev)),
-                  "ctx_mlp_backward")
+            _mlp_backward(ordered, dev, ptr(in_a), Ca, Ca, ptr(in_b), Cb, Cb, ptr(pgv), ptr(pg_index), n_pg, N, n_layers, F,
+                          [ptr(w) for w in ws], ptr(g), ptr(g_a), ptr(g_b), ptr(g_pg), [ptr(w) for w in slots],
+                          _gradsink.REPLICAS, sink.stride(), 0, 0)
             return (g_a, g_b, None if g_pg is None else g_pg.reshape(pg_shape)) + (None,) * 7
-        zeroed = torch.zeros(_REPLICAS * total + n_pg, dtype=torch.float32, device=dev)
-        copies = zeroed[:_REPLICAS * total].view(_REPLICAS, total)
-        g_pg = zeroed[_REPLICAS * total:] if pgv is not None else None
+        n_copies = 1 if ordered else _REPLICAS        # the ordered form has its own scratch and adds into ONE copy
+        zeroed = torch.zeros(n_copies * total + n_pg, dtype=torch.float32, device=dev)
+        copies = zeroed[:n_copies * total].view(n_copies, total)
+        g_pg = zeroed[n_copies * total:] if pgv is not None else None
         first, at = [], 0
         for w in ws:
             first.append(None if w is None else copies[0, at:at + w.numel()])
             at += 0 if w is None else w.numel()
-        check(_lib.lib().cnc_ctx_mlp_backward(ptr(in_a), Ca, Ca, ptr(in_b), Cb, Cb, ptr(pgv), ptr(pg_index), N, n_layers, F,
-                                              *[ptr(w) for w in ws], ptr(g), ptr(g_a), ptr(g_b), ptr(g_pg),
-                                              *[ptr(w) for w in first], _REPLICAS, total, 0, 0, stream(dev)), "ctx_mlp_backward")
-        flat = copies.sum(0) if _REPLICAS > 1 else copies[0]
+        _mlp_backward(ordered, dev, ptr(in_a), Ca, Ca, ptr(in_b), Cb, Cb, ptr(pgv), ptr(pg_index), n_pg, N, n_layers, F,
+                      [ptr(w) for w in ws], ptr(g), ptr(g_a), ptr(g_b), ptr(g_pg), [ptr(w) for w in first], n_copies, total, 0, 0)
+        flat = copies.sum(0) if n_copies > 1 else copies[0]
         gws, at = [], 0
         for w in ws:
             gws.append(None if w is None else flat[at:at + w.numel()].view_as(w))
@@ -158,32 +179,32 @@ class ContextHeads(Function):
                 g_a[r0:r1, c0 + Ca:].zero_()
         g_b = torch.empty_like(in_b) if (in_b is not None and ctx.needs_input_grad[1]) else None
         g_pg = torch.zeros_like(pgv) if pgv is not None else None
-        from .. import _gradsink
+        from .. import _gradsink, _repro
+        ordered = _repro.reproducible_enabled()
+        n_copies = 1 if ordered else _REPLICAS
         sink = ctx.sink
         slots = None if sink is None else sink.small_slot(ws)
         if slots is not None:
             firsts, reps, stride = slots, _gradsink.REPLICAS, sink.stride()
         else:
             total = sum(w.numel() for w in ws)
-            copies = torch.zeros((_REPLICAS, total), dtype=torch.float32, device=dev)
+            copies = torch.zeros((n_copies, total), dtype=torch.float32, device=dev)
             firsts, o = [], 0
             for w in ws:
                 firsts.append(copies[0, o:o + w.numel()])
                 o += w.numel()
-            reps, stride = _REPLICAS, total
-        L, st = _lib.lib(), stream(dev)
+            reps, stride = n_copies, total
         for i, (r0, r1, c0, Ca, pg_i) in enumerate(ctx.segs):
             if r1 == r0:
                 continue
-            check(L.cnc_ctx_mlp_backward(in_a.data_ptr() + 4 * (r0 * lda + c0), lda, Ca,
-                                         None if in_b is None else in_b.data_ptr() + 4 * r0 * Cb, Cb, Cb,
-                                         None if pgv is None else pgv.data_ptr() + 4 * pg_i, None, r1 - r0, 1, F,
-                                         ptr(ws[2 * i]), ptr(ws[2 * i + 1]), None, None, None, None,
-                                         g.data_ptr() + 4 * r0 * F, g_a.data_ptr() + 4 * (r0 * lda + c0),
-                                         None if g_b is None else g_b.data_ptr() + 4 * r0 * Cb,
-                                         None if g_pg is None else g_pg.data_ptr() + 4 * pg_i,
-                                         ptr(firsts[2 * i]), ptr(firsts[2 * i + 1]), None, None, None, None,
-                                         reps, stride, lda, Cb, st), "ctx_mlp_backward")
+            _mlp_backward(ordered, dev, in_a.data_ptr() + 4 * (r0 * lda + c0), lda, Ca,
+                          None if in_b is None else in_b.data_ptr() + 4 * r0 * Cb, Cb, Cb,
+                          None if pgv is None else pgv.data_ptr() + 4 * pg_i, None, 1, r1 - r0, 1, F,
+                          [ptr(ws[2 * i]), ptr(ws[2 * i + 1]), None, None, None, None],
+                          g.data_ptr() + 4 * r0 * F, g_a.data_ptr() + 4 * (r0 * lda + c0),
+                          None if g_b is None else g_b.data_ptr() + 4 * r0 * Cb,
+                          None if g_pg is None else g_pg.data_ptr() + 4 * pg_i,
+                          [ptr(firsts[2 * i]), ptr(firsts[2 * i + 1]), None, None, None, None], reps, stride, lda, Cb)
         g_pg_out = None if g_pg is None else g_pg.reshape(ctx.pg_shape)
         if slots is not None:
             return (g_a, g_b, g_pg_out, None) + (None,) * len(ws)

@@ -254,8 +254,12 @@ class ordered_backward:
 
 
 def ordered_backward_enabled():
-    """What `ordered=None` resolves to: the process-wide mode if set, else CNC_ORDERED_BACKWARD=1 (read per call), else
-    torch's deterministic-algorithms switch."""
+    """What `ordered=None` resolves to: True under the reproducible mode where that was asked for by name
+    (`cnc_amd.reproducible(True)`, CNC_REPRODUCIBLE=1: it implies this route), else the process-wide mode if set, else
+    CNC_ORDERED_BACKWARD=1 (read per call), else torch's deterministic-algorithms switch."""
+    from .. import _repro
+    if _repro.explicitly_enabled():
+        return True
     if _ORDERED_MODE is not None:
         return _ORDERED_MODE
     if os.environ.get("CNC_ORDERED_BACKWARD") == "1":

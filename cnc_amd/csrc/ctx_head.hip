@@ -158,6 +158,10 @@ struct MlpGrads {
     uint32_t ldga, ldgb;                      // row pitch of g_a / g_b (Ca / Cb when packed)
     float *gW1, *gb1, *gW2, *gb2, *gW3, *gb3; // accumulated with atomicAdd: zeroed by the caller
     uint32_t n_rep, rep_stride;               // block b adds into copy b % n_rep, rep_stride floats further on
+    // the ordered form (cnc_ctx_mlp_backward_ordered): no atomics, partial sums into the caller's scratch
+    float*   ord_slots;                       // [n_slots][ord_P]: one image [gW1 | gb1 | gW2 | gb2 | gW3 | gb3] per slot
+    float*   ord_rowpg;                       // [N]: every row's gradient of the Pg column (null: no Pg gradient)
+    uint32_t ord_P;
 };
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -213,9 +217,26 @@ __device__ __forceinline__ void flush_mfma(float* g, uint32_t NA, uint32_t NB, u
             }
 }
 
+// the ordered form: the accumulated tiles into a slot's image of g[NA][NB], plain stores (every element is written)
+template <int TA, int TB>
+__device__ __forceinline__ void store_mfma(float* g, uint32_t NA, uint32_t NB, uint32_t lane, const f32x4 (&acc)[TA][TB])
+{
+#pragma unroll
+    for (int ta = 0; ta < TA; ta++)
+#pragma unroll
+        for (int tb = 0; tb < TB; tb++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const uint32_t i = 16u * ta + 4u * (lane >> 4) + r, j = 16u * tb + (lane & 15u);
+                if (i < NA && j < NB) g[i * NB + j] = acc[ta][tb][r];
+            }
+}
+
 constexpr int kBwdThreads = 128;    // two waves per block: each needs two 64-row LDS tiles (2 x 10.5 KB)
 
-template <int NL, int F>
+// ORD: the ordered form.  Every wave leaves its weight / bias partial sums in slot 2 blockIdx.x + wave of g.ord_slots and
+// every row its Pg gradient in g.ord_rowpg; k_ctx_ordered_pg / k_ctx_ordered_reduce add them up in a fixed order.
+template <int NL, int F, bool ORD = false>
 __global__ __launch_bounds__(kBwdThreads) void k_ctx_mlp_bwd(MlpArgs a, MlpGrads g)
 {
     constexpr int H1 = NL == 1 ? F : kH;
@@ -334,13 +355,14 @@ __global__ __launch_bounds__(kBwdThreads) void k_ctx_mlp_bwd(MlpArgs a, MlpGrads
             if (a.pg) {
                 tB[lane * kPitch + c] = a.pg[a.pg_index ? a.pg_index[row] : 0];
                 const float s = d_in(c);
-                if (a.pg_index) s_pg = s;
+                if constexpr (ORD) { if (g.ord_rowpg) g.ord_rowpg[row] = s; }
+                else if (a.pg_index) s_pg = s;
                 else apg += s;
             }
         } else {
             for (uint32_t c = 0; c < a.C; c++) tB[lane * kPitch + c] = 0.0f;
         }
-        if (g.g_pg && a.pg_index) {
+        if (!ORD && g.g_pg && a.pg_index) {
             // rows of one level are contiguous, so a wave almost always holds ONE table entry: reduce over the
             // wave and keep a running sum per wave, flushed with one atomic when the entry changes.  (One atomic
             // per lane on <= 16 addresses serialised the whole kernel: 9.6 ms instead of 0.7.)
@@ -371,6 +393,23 @@ __global__ __launch_bounds__(kBwdThreads) void k_ctx_mlp_bwd(MlpArgs a, MlpGrads
             ab1 += s;
         }
         __syncthreads();
+    }
+    if constexpr (ORD) {
+        float* const slot = g.ord_slots + (size_t)(blockIdx.x * (kBwdThreads / 64) + wave) * g.ord_P;
+        store_mfma<T1A, T1B>(slot, H1, a.C, lane, aW1);
+        uint32_t at = H1 * a.C;
+        if (lane < H1) slot[at + lane] = ab1;
+        if constexpr (NL == 3) {
+            at += H1;
+            store_mfma<TH, TH>(slot + at, kH, kH, lane, aW2);
+            at += kH * kH;
+            if (lane < kH) slot[at + lane] = ab2;
+            at += kH;
+            store_mfma<TF, TH>(slot + at, F, kH, lane, aW3);
+            at += F * kH;
+            if (lane < F) slot[at + lane] = ab3;
+        }
+        return;
     }
     // ~1000 blocks adding into the same few hundred addresses serialise at the memory side (21 us of a 72 us
     // single-Linear call): the caller hands n_rep zeroed copies of the weight-gradient buffer and sums them
@@ -594,7 +633,9 @@ __device__ __forceinline__ void head3_put(float* tile, uint32_t pitch, uint32_t 
     for (int r = 0; r < 4; r++) tile[v * pitch + c0 + r] = x[r];
 }
 
-template <int F>
+// ORD: the ordered form.  The workgroup's four waves are summed in a fixed order behind barriers (weights: the tree below;
+// biases: wave 0 + 1 + 2 + 3) into slot blockIdx.x of g.ord_slots; every row's Pg gradient goes to g.ord_rowpg.
+template <int F, bool ORD = false>
 __global__ __launch_bounds__(256, 3) void k_ctx_head3_bwd(MlpArgs a, MlpGrads g)
 {
     __shared__ __attribute__((aligned(16))) Head3LdsAll all;
@@ -687,7 +728,9 @@ __global__ __launch_bounds__(256, 3) void k_ctx_head3_bwd(MlpArgs a, MlpGrads g)
         // the Pg column's gradient
         if (g.g_pg && a.pg) {
             const bool mine = on && 4u * q <= c_pg % 16u && c_pg % 16u < 4u * q + 4u;      // the lane row that holds column c_pg
-            if (!a.pg_index) {
+            if constexpr (ORD) {
+                if (mine) g.ord_rowpg[row] = s_pg;
+            } else if (!a.pg_index) {
                 apg += mine ? s_pg : 0.0f;
             } else {
                 // rows of one level are contiguous, so a tile almost always holds ONE table entry: reduce over the wave and
@@ -788,6 +831,44 @@ __global__ __launch_bounds__(256, 3) void k_ctx_head3_bwd(MlpArgs a, MlpGrads g)
         if (wave == 2) put_all(scratch);
         __syncthreads();
         if (wave == 0) add_all(scratch);
+    }
+    if constexpr (ORD) {
+        // slot image: gW1 [32][C] | gb1 [32] | gW2 [32][32] | gb2 [32] | gW3 [F][32] | gb3 [F]
+        float* const   slot = g.ord_slots + (size_t)blockIdx.x * g.ord_P;
+        const uint32_t o_b1 = kH * a.C, o_W2 = o_b1 + kH, o_b2 = o_W2 + kH * kH, o_W3 = o_b2 + kH, o_b3 = o_W3 + F * kH;
+        if (wave == 0) {
+            store_mfma<2, 3>(slot, kH, a.C, lane, aW1);
+            store_mfma<2, 2>(slot + o_W2, kH, kH, lane, aW2);
+            store_mfma<1, 2>(slot + o_W3, F, kH, lane, aW3);
+        }
+        // bias sums over the 16 vertices of a lane row, then over the waves through the wave's (idle) tile: b1 | b2 | b3
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+#pragma unroll
+            for (int d = 8; d >= 1; d >>= 1) {
+                ab3[r] += __shfl_xor(ab3[r], d);
+#pragma unroll
+                for (int t = 0; t < 2; t++) { ab2[t][r] += __shfl_xor(ab2[t][r], d); ab1[t][r] += __shfl_xor(ab1[t][r], d); }
+            }
+            if (i16 == 0) {
+                tA[2 * kH + 4u * q + r] = ab3[r];
+#pragma unroll
+                for (int t = 0; t < 2; t++) {
+                    tA[16u * t + 4u * q + r] = ab1[t][r];
+                    tA[kH + 16u * t + 4u * q + r] = ab2[t][r];
+                }
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            for (uint32_t e = lane; e < 2 * kH + 16; e += 64) {
+                const float s = ((tilesA[0][e] + tilesA[1][e]) + tilesA[2][e]) + tilesA[3][e];
+                if (e < kH) slot[o_b1 + e] = s;
+                else if (e < 2 * kH) slot[o_b2 + (e - kH)] = s;
+                else if (e - 2 * kH < (uint32_t)F) slot[o_b3 + (e - 2 * kH)] = s;
+            }
+        }
+        return;
     }
     const size_t rep = (size_t)(blockIdx.x % g.n_rep) * g.rep_stride;
     if (wave == 0) {
@@ -891,6 +972,86 @@ __global__ __launch_bounds__(256) void k_segment_bwd(const float* __restrict__ g
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The ordered form's reductions (cnc_ctx_mlp_backward_ordered): fixed orders, no atomics
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kPgChunk = 16384;      // rows per partial sum of the Pg gradient
+
+// part[e][chunk] = sum of rowpg[row] over the chunk's rows with pg_index[row] == e (every row for the scalar Pg): thread t
+// adds rows t, t + 256, ... in ascending order, then the wave's butterfly, then wave 0 + 1 + 2 + 3.
+__global__ __launch_bounds__(256) void k_ctx_ordered_pg(const float* __restrict__ rowpg, const int64_t* __restrict__ pg_index,
+                                                        uint32_t N, uint32_t n_chunks, float* __restrict__ part)
+{
+    const uint32_t chunk = blockIdx.x, e = blockIdx.y;
+    const uint32_t r_lo = chunk * kPgChunk, r_hi = min(N, r_lo + kPgChunk);
+    float s = 0.0f;
+    for (uint32_t row = r_lo + threadIdx.x; row < r_hi; row += 256)
+        if (!pg_index || pg_index[row] == (int64_t)e) s += rowpg[row];
+    __shared__ float red[4];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(size_t)e * n_chunks + chunk] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+struct OrdDst {
+    float*   p[6];           // gW1, gb1, gW2, gb2, gW3, gb3 (null behind the last one in use)
+    uint32_t end[6];         // end of each piece in the slot image
+};
+
+// dst[e] = dst[e] + (((0 + slot 0) + slot 1) + ...): the slots in ascending index, ONE rounded add into the destination;
+// the Pg gradient likewise over its chunks.
+__global__ __launch_bounds__(256) void k_ctx_ordered_reduce(const float* __restrict__ slots, uint32_t n_slots, uint32_t P,
+                                                            OrdDst d, const float* __restrict__ part, uint32_t n_chunks,
+                                                            uint32_t n_pg, float* __restrict__ g_pg)
+{
+    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e < P) {
+        float s = 0.0f;
+        for (uint32_t k = 0; k < n_slots; k++) s += slots[(size_t)k * P + e];
+        uint32_t lo = 0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            if (e >= lo && e < d.end[i]) d.p[i][e - lo] += s;
+            lo = d.end[i];
+        }
+    } else if (e - P < n_pg) {
+        float s = 0.0f;
+        for (uint32_t c = 0; c < n_chunks; c++) s += part[(size_t)(e - P) * n_chunks + c];
+        g_pg[e - P] += s;
+    }
+}
+
+static uint32_t ordered_image(uint32_t n_layers, uint32_t F, uint32_t C)
+{
+    return n_layers == 1 ? F * C + F : kH * C + kH + kH * kH + kH + F * kH + F;
+}
+
+// slots the backward kernels of launch_mlp write for N rows: two waves per block / one per workgroup
+static uint32_t ordered_slots(uint32_t n_layers, uint32_t N)
+{
+    return n_layers == 1 ? (kBwdThreads / 64) * min(div_up(N, (uint32_t)kBwdThreads), 1024u)
+                         : min(div_up(div_up(N, 16u), 4u), 768u);
+}
+
+template <int NL>
+static int launch_mlp_ordered(uint32_t F, const MlpArgs& a, const MlpGrads& g, hipStream_t s)
+{
+    // the launch geometry of launch_mlp: a row's input gradients come out of the same instructions
+    const uint32_t wgs = min(div_up(div_up(a.N, 16u), 4u), 768u);
+    const uint32_t bwd_blocks = min(div_up(a.N, (uint32_t)kBwdThreads), 1024u);
+#define CNC_CTX_CASE(FF)                                                                                              \
+    if (F == FF) {                                                                                                    \
+        if constexpr (NL == 3) hipLaunchKernelGGL((k_ctx_head3_bwd<FF, true>), dim3(wgs), dim3(256), 0, s, a, g);     \
+        else hipLaunchKernelGGL((k_ctx_mlp_bwd<1, FF, true>), dim3(bwd_blocks), dim3(kBwdThreads), 0, s, a, g);       \
+        return launch_status();                                                                                       \
+    }
+    CNC_CTX_CASE(1) CNC_CTX_CASE(2) CNC_CTX_CASE(4) CNC_CTX_CASE(8)
+#undef CNC_CTX_CASE
+    return CNC_ERR_UNSUPPORTED;
+}
+
 template <int NL>
 static int launch_mlp(bool backward, uint32_t F, const MlpArgs& a, float* out, const MlpGrads& g, hipStream_t s)
 {
@@ -965,6 +1126,67 @@ extern "C" int cnc_ctx_mlp_backward(const float* in_a, uint32_t lda, uint32_t Ca
     MlpGrads g{grad_out, grad_a, grad_b, pg ? grad_pg : nullptr, ldga, ldgb, gW1, gb1, gW2, gb2, gW3, gb3, n_replicas, replica_stride};
     return n_layers == 1 ? launch_mlp<1>(true, F, a, nullptr, g, (hipStream_t)stream)
                          : launch_mlp<3>(true, F, a, nullptr, g, (hipStream_t)stream);
+}
+
+extern "C" uint64_t cnc_ctx_mlp_backward_ordered_workspace(uint32_t N, uint32_t n_layers, uint32_t F, uint32_t C, uint32_t n_pg)
+{
+    if (N == 0 || (n_layers != 1 && n_layers != 3)) return 0;
+    const uint64_t floats = (uint64_t)ordered_slots(n_layers, N) * ordered_image(n_layers, F, C) + (n_pg ? N : 0u) +
+                            (uint64_t)n_pg * div_up(N, kPgChunk);
+    return (floats * sizeof(float) + 15u) & ~(uint64_t)15u;
+}
+
+extern "C" int cnc_ctx_mlp_backward_ordered(const float* in_a, uint32_t lda, uint32_t Ca, const float* in_b, uint32_t ldb,
+                                            uint32_t Cb, const float* pg, const int64_t* pg_index, uint32_t n_pg,
+                                            uint32_t N, uint32_t n_layers, uint32_t F,
+                                            const float* W1, const float* b1, const float* W2, const float* b2,
+                                            const float* W3, const float* b3, const float* grad_out, float* grad_a,
+                                            float* grad_b, float* grad_pg, float* gW1, float* gb1, float* gW2,
+                                            float* gb2, float* gW3, float* gb3, uint32_t ldga, uint32_t ldgb,
+                                            void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (N == 0) return CNC_OK;
+    if (ldga == 0) ldga = Ca;
+    if (ldgb == 0) ldgb = Cb;
+    if (ldga < Ca || (in_b && grad_b && ldgb < Cb)) return CNC_ERR_INVALID_VALUE;
+    MlpArgs a{in_a, lda, Ca, in_b, ldb, in_b ? Cb : 0u, pg, pg ? pg_index : nullptr, N,
+              Ca + (in_b ? Cb : 0u) + (pg ? 1u : 0u), W1, b1, W2, b2, W3, b3};
+    if (!grad_out || !grad_a || !gW1 || !gb1 || !mlp_args_ok(a, n_layers)) return CNC_ERR_INVALID_VALUE;
+    if (n_layers == 3 && (!gW2 || !gb2 || !gW3 || !gb3)) return CNC_ERR_INVALID_VALUE;
+    if (F != 1 && F != 2 && F != 4 && F != 8) return CNC_ERR_UNSUPPORTED;
+    const bool want_pg = pg && grad_pg;
+    if (!want_pg) n_pg = 0;
+    else if (!pg_index) n_pg = 1;
+    else if (n_pg == 0) return CNC_ERR_INVALID_VALUE;
+    const uint64_t need = cnc_ctx_mlp_backward_ordered_workspace(N, n_layers, F, a.C, n_pg);
+    if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < need) return CNC_ERR_INVALID_VALUE;
+    const uint32_t P = ordered_image(n_layers, F, a.C), n_slots = ordered_slots(n_layers, N), n_chunks = div_up(N, kPgChunk);
+    float* const slots = static_cast<float*>(workspace);
+    float* const rowpg = slots + (size_t)n_slots * P;
+    float* const part = rowpg + (n_pg ? N : 0u);
+    MlpGrads g{grad_out, grad_a, grad_b, want_pg ? grad_pg : nullptr, ldga, ldgb, gW1, gb1, gW2, gb2, gW3, gb3, 1, 0,
+               slots, want_pg ? rowpg : nullptr, P};
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = n_layers == 1 ? launch_mlp_ordered<1>(F, a, g, s) : launch_mlp_ordered<3>(F, a, g, s);
+    if (rc != CNC_OK) return rc;
+    if (n_pg) {
+        hipLaunchKernelGGL(k_ctx_ordered_pg, dim3(n_chunks, n_pg), dim3(256), 0, s, rowpg, a.pg_index, N, n_chunks, part);
+        if (launch_status() != CNC_OK) return CNC_ERR_LAUNCH;
+    }
+    OrdDst d{};
+    const uint32_t H1 = n_layers == 1 ? F : (uint32_t)kH;
+    d.p[0] = gW1; d.end[0] = H1 * a.C;
+    d.p[1] = gb1; d.end[1] = d.end[0] + H1;
+    for (int i = 2; i < 6; i++) d.end[i] = d.end[1];
+    if (n_layers == 3) {
+        d.p[2] = gW2; d.end[2] = d.end[1] + kH * kH;
+        d.p[3] = gb2; d.end[3] = d.end[2] + kH;
+        d.p[4] = gW3; d.end[4] = d.end[3] + F * kH;
+        d.p[5] = gb3; d.end[5] = d.end[4] + F;
+    }
+    hipLaunchKernelGGL(k_ctx_ordered_reduce, dim3(div_up(P + n_pg, 256u)), dim3(256), 0, s, slots, n_slots, P, d, part, n_chunks,
+                       n_pg, grad_pg);
+    return launch_status();
 }
 
 extern "C" uint32_t cnc_bernoulli_bits_partials(uint64_t n_slots, uint32_t F)

@@ -44,6 +44,7 @@ struct FieldBwdArgs {
     uint32_t       ld_x;
     float*         bias_grads;      // [3 H + 84] zero-initialised by the caller: column sums of G4 | G3 | G1 | G2 (80) | G5 (4)
     uint32_t*      g_max;           // [5] zero-initialised (nullable): float bits of max |G1| .. max |G5| (atomic max)
+    float*         bias_slots;      // the ordered form: [gridDim.x][3 H + 84] column sums per workgroup (plain stores)
 };
 
 // Row-major [N, ld] float matrices through buffer resources: SGPR base + ONE 32-bit lane offset + constants — a flat pointer
@@ -131,10 +132,20 @@ struct ActTile {
     }
 };
 
+// Adds a wave's column sum into the workgroup's accumulator.  The plain form: ds_add_f32 (the two waves of a workgroup meet
+// on the columns of G2 and G5, in whatever order they get there).  The ordered form: every word has ONE writing wave
+// (bs4 / bs3 / bs1: a wave owns its columns; bs2 / bs5: an accumulator per wave), which adds in program order.
+template <bool ORD>
+__device__ __forceinline__ void bsum_add(float* at, float t)
+{
+    if constexpr (ORD) *at += t;
+    else atomicAdd(at, t);
+}
+
 // One column-split stage with a ReLU mask: X = (acc / (2^8 s_in)) where act > 0 else 0; to HBM (G), its column sums (the
 // bias gradient) into the workgroup's LDS accumulators `bsum`, and, scaled by the new tile scale, into the planes.  Returns
 // the new scale.  Barriers: [all reads of the planes done + maxima exchanged] ... writes ... [visible].
-template <int NCB, int NT>
+template <int NCB, int NT, bool ORD>
 __device__ __forceinline__ float masked_stage_out(const f32x4 (&acc)[2][NCB], float inv_in, const ActTile<NCB>& act,
                                                   wrsrc_t G, uint32_t H, uint32_t lane_off, uint32_t w,
                                                   uint32_t lane, half_t* h_hi, half_t* h_lo, float* xch, float* bsum,
@@ -161,7 +172,7 @@ __device__ __forceinline__ float masked_stage_out(const f32x4 (&acc)[2][NCB], fl
 #pragma unroll
         for (int v = 0; v < 4; v++) {
             const float t = row16_sum_to_lane15(x[0][cb][v] + x[1][cb][v]);
-            if (r == 15u) atomicAdd(bsum + col0 + v, t);          // ds_add_f32: four lanes, distinct addresses
+            if (r == 15u) bsum_add<ORD>(bsum + col0 + v, t);      // ds_add_f32: four lanes, distinct addresses
         }
     }
     m = wave_max(m);
@@ -181,7 +192,7 @@ __device__ __forceinline__ float masked_stage_out(const f32x4 (&acc)[2][NCB], fl
 #ifndef CNC_BWD_DB
 #define CNC_BWD_DB false
 #endif
-template <int NT>
+template <int NT, bool ORD = false>
 __global__ __launch_bounds__(128, CNC_BWD_WAVES) void k_field_bwd_chain(FieldBwdArgs p)
 {
     extern __shared__ float lds[];
@@ -197,7 +208,10 @@ __global__ __launch_bounds__(128, CNC_BWD_WAVES) void k_field_bwd_chain(FieldBwd
     float* const  xch = reinterpret_cast<float*>(lds16 + 2 * 32 * P::ld);       // two maxima (+ two spare words)
     // the workgroup's bias-gradient accumulators: column sums of G4 | G3 | G1 (H each) | G2 (80) | G5 (4), flushed at the end
     float* const  bs4 = xch + 4, * const bs3 = bs4 + H, * const bs1 = bs3 + H, * const bs2 = bs1 + H, * const bs5 = bs2 + 80;
-    for (uint32_t i = tid; i < 3 * H + 84; i += 128) bs4[i] = 0.0f;
+    for (uint32_t i = tid; i < 3 * H + 84 + (ORD ? 84 : 0); i += 128) bs4[i] = 0.0f;
+    // the ordered form: wave 1 sums its rows of G2 | G5 into 84 words of its own behind the workgroup's
+    float* const  bs2w = ORD && w ? bs2 + 84 : bs2, * const bs5w = ORD && w ? bs5 + 84 : bs5;
+    if constexpr (ORD) __syncthreads();                 // the accumulators are added to with plain read-modify-writes
     const uint32_t tiles = (p.N + 31u) / 32u;
     const uint32_t K2 = ((1u + p.geo + 31u) / 32u) * 32u;                        // stage 1's K: 1 + geo padded to 32
     const uint32_t bytes_h = p.N * H * 4u;
@@ -225,7 +239,7 @@ __global__ __launch_bounds__(128, CNC_BWD_WAVES) void k_field_bwd_chain(FieldBwd
             float t = g5[c];
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
-            if (lane == 0) atomicAdd(bs5 + c, t);
+            if (lane == 0) bsum_add<ORD>(bs5w + c, t);
         }
         if (lane == 0) xch[w] = m5;
         __syncthreads();                               // (also: the previous tile's last reads of the planes are done)
@@ -247,12 +261,12 @@ __global__ __launch_bounds__(128, CNC_BWD_WAVES) void k_field_bwd_chain(FieldBwd
         layer_q<2, NCB, NT, CNC_BWD_DB>(h_hi, h_lo, 1, p.Wt[0], NCBT, w * NCB, 0, acc, lane);
         __builtin_amdgcn_sched_barrier(0);
         act.load(rH4, H, lane_off);                      // behind the products' issue: in flight while the matrix pipe drains
-        s_in = masked_stage_out<NCB, NT>(acc, kWScaleInv / s_in, act, rG4, H, lane_off, w, lane, h_hi, h_lo, xch, bs4, gm4);
+        s_in = masked_stage_out<NCB, NT, ORD>(acc, kWScaleInv / s_in, act, rG4, H, lane_off, w, lane, h_hi, h_lo, xch, bs4, gm4);
         // ---- stage 3: G3 = (G4 W4) where h3 > 0 ----
         layer_q<2, NCB, NT, CNC_BWD_DB>(h_hi, h_lo, NT, p.Wt[1], NCBT, w * NCB, 0, acc, lane);
         __builtin_amdgcn_sched_barrier(0);
         act.load(rH3, H, lane_off);                      // behind the products' issue: in flight while the matrix pipe drains
-        s_in = masked_stage_out<NCB, NT>(acc, kWScaleInv / s_in, act, rG3, H, lane_off, w, lane, h_hi, h_lo, xch, bs3, gm3);
+        s_in = masked_stage_out<NCB, NT, ORD>(acc, kWScaleInv / s_in, act, rG3, H, lane_off, w, lane, h_hi, h_lo, xch, bs3, gm3);
         // ---- stage 2: G2[:, c] = (G3 W3[:, 15 + c]) for the geo features c >= 1; G2[:, 0] = g_density * d density / d raw ----
         {
             f32x4 acc2[1][NB2];
@@ -280,7 +294,7 @@ __global__ __launch_bounds__(128, CNC_BWD_WAVES) void k_field_bwd_chain(FieldBwd
 #pragma unroll
                 for (int v = 0; v < 4; v++) {
                     const float t = row16_sum_to_lane15(x2[cb][v]);
-                    if (r == 15u && c0 + v < 80u) atomicAdd(bs2 + c0 + v, t);
+                    if (r == 15u && c0 + v < 80u) bsum_add<ORD>(bs2w + c0 + v, t);
                 }
             }
             m = wave_max(m);
@@ -317,7 +331,7 @@ __global__ __launch_bounds__(128, CNC_BWD_WAVES) void k_field_bwd_chain(FieldBwd
         layer_q<2, NCB, NT, CNC_BWD_DB>(h_hi, h_lo, K2 / 32, p.Wt[3], NCBT, w * NCB, 0, acc, lane);
         __builtin_amdgcn_sched_barrier(0);
         act.load(rH1, H, lane_off);                      // behind the products' issue: in flight while the matrix pipe drains
-        s_in = masked_stage_out<NCB, NT>(acc, kWScaleInv / s_in, act, rG1, H, lane_off, w, lane, h_hi, h_lo, xch, bs1, gm1);
+        s_in = masked_stage_out<NCB, NT, ORD>(acc, kWScaleInv / s_in, act, rG1, H, lane_off, w, lane, h_hi, h_lo, xch, bs1, gm1);
         // ---- stage 0: dX[:, :n_enc] = G1 W1[:, :n_enc], rows split between the waves, the column blocks in passes of six
         // (a pass's blocks past the last one multiply whatever follows in the fragment stream: their results are dropped) ----
         {
@@ -341,7 +355,11 @@ __global__ __launch_bounds__(128, CNC_BWD_WAVES) void k_field_bwd_chain(FieldBwd
     }
     // ---- the bias gradients: this workgroup's column sums into the global accumulators (zeroed by the caller) ----
     __syncthreads();
-    if (p.bias_grads)
+    if constexpr (ORD) {
+        // this workgroup's slot: wave 0's sums + wave 1's where both have some; k_field_bias_reduce adds the slots up
+        float* const slot = p.bias_slots + (size_t)blockIdx.x * (3 * H + 84);
+        for (uint32_t i = tid; i < 3 * H + 84; i += 128) slot[i] = i < 3 * H ? bs4[i] : bs4[i] + bs4[i + 84];
+    } else if (p.bias_grads)
         for (uint32_t i = tid; i < 3 * H + 84; i += 128) {
             const float v = bs4[i];
             if (v != 0.0f) unsafeAtomicAdd(p.bias_grads + i, v);
@@ -355,11 +373,31 @@ __global__ __launch_bounds__(128, CNC_BWD_WAVES) void k_field_bwd_chain(FieldBwd
     }
 }
 
+// The ordered form's second step: dst[i] = dst[i] + (((0 + slot 0) + slot 1) + ...), the workgroups in ascending index
+__global__ __launch_bounds__(128) void k_field_bias_reduce(const float* __restrict__ slots, uint32_t n_slots, uint32_t n,
+                                                           float* __restrict__ dst)
+{
+    const uint32_t i = blockIdx.x * 128 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.0f;
+    for (uint32_t b = 0; b < n_slots; b++) s += slots[(size_t)b * n + i];
+    dst[i] += s;
+}
+
+constexpr uint32_t kOrderedMaxSlots = 2048;      // workgroups of the ordered form: bounds its scratch on every device
+
 }  // namespace cnc
 
 using namespace cnc;
 
-extern "C" int cnc_field_backward_chain(const cnc_field_bwd_t* f, void* stream)
+extern "C" uint64_t cnc_field_backward_chain_ordered_workspace(const cnc_field_bwd_t* f)
+{
+    if (!f || f->N == 0 || !f->bias_grads) return 0;
+    const uint32_t tiles = (f->N + 31u) / 32u;
+    return (uint64_t)(tiles < kOrderedMaxSlots ? tiles : kOrderedMaxSlots) * (3 * f->n_neurons + 84) * sizeof(float);
+}
+
+static int field_backward_chain(const cnc_field_bwd_t* f, bool ordered, void* workspace, uint64_t workspace_bytes, void* stream)
 {
     if (!f) return CNC_ERR_INVALID_VALUE;
     if (f->N == 0) return CNC_OK;
@@ -387,6 +425,10 @@ extern "C" int cnc_field_backward_chain(const cnc_field_bwd_t* f, void* stream)
     const size_t   lds_bytes = (size_t)2 * 32 * ld * sizeof(half_t) + 16 + (size_t)(3 * H + 84) * sizeof(float);
     p.bias_grads = f->bias_grads;
     p.g_max = f->g_max;
+    ordered = ordered && f->bias_grads;
+    if (ordered && (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < cnc_field_backward_chain_ordered_workspace(f)))
+        return CNC_ERR_INVALID_VALUE;
+    p.bias_slots = ordered ? static_cast<float*>(workspace) : nullptr;
     const uint32_t tiles = (p.N + 31u) / 32u;
     hipStream_t    s = (hipStream_t)stream;
     // the grid is what is resident at once (the workgroups loop over the tiles); asked once per thread and device
@@ -408,8 +450,29 @@ extern "C" int cnc_field_backward_chain(const cnc_field_bwd_t* f, void* stream)
         cached_dev = dev;
     }
     const uint32_t resident = cached_n[NT == 5 ? 0 : 1];
-    const uint32_t blocks = tiles < resident ? tiles : resident;
+    uint32_t blocks = tiles < resident ? tiles : resident;
+    if (ordered) {
+        // the same grid (capped: the scratch's size must not depend on the device), 84 more words of LDS; no atomics on floats
+        if (blocks > kOrderedMaxSlots) blocks = kOrderedMaxSlots;
+        const size_t lds_ord = lds_bytes + 84 * sizeof(float);
+        if (NT == 5) hipLaunchKernelGGL((k_field_bwd_chain<5, true>), dim3(blocks), dim3(128), lds_ord, s, p);
+        else hipLaunchKernelGGL((k_field_bwd_chain<2, true>), dim3(blocks), dim3(128), lds_ord, s, p);
+        if (launch_status() != CNC_OK) return CNC_ERR_LAUNCH;
+        const uint32_t n = 3 * H + 84;
+        hipLaunchKernelGGL(k_field_bias_reduce, dim3((n + 127u) / 128u), dim3(128), 0, s, p.bias_slots, blocks, n, p.bias_grads);
+        return launch_status();
+    }
     if (NT == 5) hipLaunchKernelGGL((k_field_bwd_chain<5>), dim3(blocks), dim3(128), lds_bytes, s, p);
     else hipLaunchKernelGGL((k_field_bwd_chain<2>), dim3(blocks), dim3(128), lds_bytes, s, p);
     return launch_status();
+}
+
+extern "C" int cnc_field_backward_chain(const cnc_field_bwd_t* f, void* stream)
+{
+    return field_backward_chain(f, false, nullptr, 0, stream);
+}
+
+extern "C" int cnc_field_backward_chain_ordered(const cnc_field_bwd_t* f, void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    return field_backward_chain(f, true, workspace, workspace_bytes, stream);
 }

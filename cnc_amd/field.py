@@ -623,7 +623,18 @@ class _FieldChain(Function):
         st.g_max = bsum.data_ptr() + (3 * H + 84) * 4
         gb_of = (bsum[2 * H:3 * H], bsum[3 * H:3 * H + 1 + geo], bsum[H:2 * H], bsum[:H], bsum[3 * H + 80:3 * H + 83])
         import ctypes
-        _lib.check(_lib.lib().cnc_field_backward_chain(ctypes.byref(st), _lib.stream(dev)), "field_backward_chain")
+        from . import _repro
+        if _repro.reproducible_enabled():
+            # the bias gradients' sums in a fixed order (cnc_field_backward_chain_ordered): scratch per (device, stream)
+            from .backends.gridencoder_backend import _workspace
+            nbytes = int(_lib.lib().cnc_field_backward_chain_ordered_workspace(ctypes.byref(st)))
+            wsp = _workspace(dev, max(nbytes, 16), (_lib.stream(dev), "field_ordered"))
+            _repro.ROUTE_CALLS["field_ordered"] += 1
+            _lib.check(_lib.lib().cnc_field_backward_chain_ordered(ctypes.byref(st), wsp.data_ptr(), wsp.numel(), _lib.stream(dev)),
+                       "field_backward_chain_ordered")
+        else:
+            _repro.ROUTE_CALLS["field_default"] += 1
+            _lib.check(_lib.lib().cnc_field_backward_chain(ctypes.byref(st), _lib.stream(dev)), "field_backward_chain")
         pairs = ((G1, feat, K0, H), (G2, h1, H, 1 + geo), (G3, head_in, 16 + geo, H), (G4, h3, H, H), (G5, h4, H, 3))
         gws = [None] * 5
         if any(need[0::2]):

@@ -50,6 +50,9 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=42, help="set_random_seed value (the reference drivers fix 42, train:135)")
     ap.add_argument("--results", type=str, default=None, help="results file (default ./results/<dataset>/output.txt)")
     ap.add_argument("--out_dir", type=str, default=None, help="bitstream directory (default ./bitstreams/<scene>)")
+    ap.add_argument("--reproducible", action="store_true",
+                    help="the reproducible mode: ordered reductions, one host thread, one stream (DESIGN.md §5); two runs "
+                         "from one seed give the same bits on one GPU")
     return ap
 
 
@@ -63,7 +66,7 @@ def make_config_and_data(args, device, rank=0, world=1):
               log2_hashmap_size=args.log2_hashmap_size, log2_hashmap_size_2D=args.log2_hashmap_size_2D,
               sample_num=args.sample_num, max_context_layer_num=args.max_context_layer_num,
               n_features=args.n_features, max_steps=args.max_steps, image_size=args.image_size, seed=args.seed,
-              out_dir=args.out_dir or f"./bitstreams/{scene}",
+              out_dir=args.out_dir or f"./bitstreams/{scene}", reproducible=bool(getattr(args, "reproducible", False)),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0

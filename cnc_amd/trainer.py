@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _gradsink, _table_adam
+from . import _gradsink, _repro, _table_adam
 from . import dist as cdist
 from .context import CNC_context_models
 from .field import NGPRadianceField_mygrid_2D3D
@@ -74,6 +74,9 @@ class TrainConfig:
     dimension_wise_resolution: Optional[int] = None   # default: finest 3-D resolution
     out_dir: str = "./bitstreams/ball"
     log_every: int = 200
+    # the reproducible mode (cnc_amd._repro): every step of this Trainer under `cnc_amd.reproducible(True)`, on
+    # the one-thread, one-stream schedule and without the planes' graph
+    reproducible: bool = False
 
 
 class SyntheticBallDataset:
@@ -290,7 +293,11 @@ class Trainer:
         self._pool_graph = None
         self._planes_replayed = False
         self._fwd_enqueued = None
-        if self.device.type == "cuda" and os.environ.get("CNC_PLANES_GRAPH", "1") == "1":
+        # The reproducible mode fixes what is not a kernel by taking the schedule that has nothing to fix: the entropy pass
+        # on the main stream from the main thread, behind the render forward (one order of random draws on the default
+        # generator, ONE backward call whose engine adds the gradient pieces in the graph's order), no captured graph.
+        self.reproducible = bool(cfg.reproducible)
+        if self.device.type == "cuda" and os.environ.get("CNC_PLANES_GRAPH", "1") == "1" and not self.reproducible:
             from ._planes_graph import PlanesGraph
             self.planes_graph = PlanesGraph(self)
         self.prefetch = os.environ.get("CNC_PREFETCH_BATCH", "1") == "1"
@@ -303,7 +310,7 @@ class Trainer:
             self.ahead_stream = reserve_streams(self.device)[2]
         # The entropy pass (context forward and backward) runs on its own stream next to the render pass — see train_step
         self.ctx_stream = None
-        if self.device.type == "cuda" and os.environ.get("CNC_CTX_STREAM", "1") == "1":
+        if self.device.type == "cuda" and os.environ.get("CNC_CTX_STREAM", "1") == "1" and not self.reproducible:
             self.ctx_stream = reserve_streams(self.device)[0]
         # ... and its planes' half on a third one (CNC_CTX_STREAM_2D=0: both halves on the side stream, one after the other)
         self.ctx_stream_2D = None
@@ -551,6 +558,9 @@ class Trainer:
         (reading them back is a device->host sync per step; the reference only looks at them every 200 steps,
         train:368-381) — `n_rendering_samples` and `num_rays` are always there."""
         c = self.cfg
+        if self.reproducible and not _repro.explicitly_enabled():
+            with _repro.reproducible(True):         # process-wide for the step: the backward kernels run on autograd's thread
+                return self.train_step(step, want_stats)
         self.field.train(); self.estimator.train(); self.context.train()
         self._planes_replayed = False       # (set by this step's entropy pass if the planes' half runs apart from it)
         # the batch: drawn at the end of the step before (`_prefetch`), while that step's backward kept the GPU busy

@@ -707,6 +707,28 @@ int cnc_ctx_mlp_backward(const float* in_a, uint32_t lda, uint32_t Ca, const flo
                          float* grad_b, float* grad_pg, float* gW1, float* gb1, float* gW2, float* gb2,
                          float* gW3, float* gb3, uint32_t n_replicas, uint32_t replica_stride,
                          uint32_t ldga, uint32_t ldgb, void* stream);
+/* (extension) The ORDERED form of cnc_ctx_mlp_backward: the same gradients with every sum in an order that
+ * depends on N, the shapes and the build only — not on scheduling, the stream, other work on the device or the run.  No
+ * atomics on floats.  Both kernel families, every shape of the plain entry.  grad_a / grad_b: bit-equal to the plain
+ * entry's.  Weight and bias gradients: every wave (n_layers 1; two per workgroup of 128 rows, the plain entry's launch) or
+ * workgroup (n_layers 3; its four waves summed behind barriers) stores its partial sums into a slot of `workspace`, a second
+ * kernel computes s = ((0 + slot 0) + slot 1) + ... in ascending slot index and adds s to the destination with ONE rounded
+ * add: the entry ACCUMULATES into gW1 .. gb3 and *grad_pg like the plain one (dst = fl(dst + s)), and there are no
+ * replicas.  The Pg gradient: every row's value goes to the workspace; entry e of the table receives, in ascending chunk
+ * order, the sums over chunks of 16,384 rows of the rows with pg_index[row] == e (all rows for the scalar Pg) — an order
+ * fixed by N alone.  n_pg: entries of the pg table (pg_index values < n_pg; ignored without pg_index or grad_pg).
+ * workspace: cnc_ctx_mlp_backward_ordered_workspace(N, n_layers, F, C = Ca + Cb + (pg ? 1 : 0), n_pg) bytes (n_pg = 1 for
+ * the scalar Pg, 0 without a Pg gradient), 16-byte aligned, written with plain stores, free again when the call's work on
+ * `stream` is done.  Calls that target the same destination must be stream-ordered.                              */
+uint64_t cnc_ctx_mlp_backward_ordered_workspace(uint32_t N, uint32_t n_layers, uint32_t F, uint32_t C, uint32_t n_pg);
+int cnc_ctx_mlp_backward_ordered(const float* in_a, uint32_t lda, uint32_t Ca, const float* in_b, uint32_t ldb,
+                                 uint32_t Cb, const float* pg, const int64_t* pg_index, uint32_t n_pg, uint32_t N,
+                                 uint32_t n_layers, uint32_t F,
+                                 const float* W1, const float* b1, const float* W2, const float* b2,
+                                 const float* W3, const float* b3, const float* grad_out, float* grad_a,
+                                 float* grad_b, float* grad_pg, float* gW1, float* gb1, float* gW2, float* gb2,
+                                 float* gW3, float* gb3, uint32_t ldga, uint32_t ldgb, void* workspace,
+                                 uint64_t workspace_bytes, void* stream);
 /* The per-step sample of the 3-D context pass (utils_bpp_acc.py:619-667), all coded levels at once: level i
  * contributes the vertices pos[i][0 .. p_at[i+1]-p_at[i]) (int16 triples, already offset to the window start)
  * and the slots cnt[i] / val[i][0 .. v_at[i+1]-v_at[i]).  Written, concatenated over the levels: pts i16 [P,3],
@@ -1031,6 +1053,15 @@ typedef struct {
                                          max |G1|, max |G2|, max |G3|, max |G4|, max |G5|: cnc_field_weight_grads' scales   */
 } cnc_field_bwd_t;
 int cnc_field_backward_chain(const cnc_field_bwd_t* chain, void* stream);
+/* (extension) The ORDERED form of the chain's bias sums: the same call with the column sums added in an order that depends on
+ * N, the shapes, the device and the build only.  A word of a workgroup's column sums has one writing wave (the two waves'
+ * sums of G2 | G5 are added wave 0 + wave 1 behind a barrier), every workgroup stores its sums into a slot of `workspace`,
+ * a second kernel adds s = ((0 + slot 0) + slot 1) + ... (ascending workgroup, at most 2,048 of them) to bias_grads with ONE
+ * rounded add: it accumulates like the plain entry.  No atomics on floats; g_max (integer atomic max) and every other output
+ * are bit-equal to the plain entry's.  workspace: cnc_field_backward_chain_ordered_workspace(chain) bytes (reads N and
+ * n_neurons; 0 without bias_grads), 16-byte aligned, plain stores, free again when the call's work on `stream` is done. */
+uint64_t cnc_field_backward_chain_ordered_workspace(const cnc_field_bwd_t* chain);
+int cnc_field_backward_chain_ordered(const cnc_field_bwd_t* chain, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* (extension, ABI v27) The five weight gradients of the field's Linears, dW_l = G_l^T A_l  (autograd's LinearBackward,
  * ngp.py:506-547), from the gradient matrices cnc_field_backward_chain left in HBM and the layers' inputs — one kernel
