@@ -221,7 +221,7 @@ struct UnitRec {
 // The same F features with the vector work cut down (566 -> ~370 instructions per 3-D unit; the kernel was 53 % vector
 // issue, tools/pmc_field.sh), BIT-IDENTICAL to `unit_features` / k_grid_encode_fwd_bits on the units a GridEncoder makes:
 //   * a level is either dense (R^D <= rows: index = q0 + q1 R + q2 R^2 < rows) or hashed into a power-of-two table
-//     (index = xor of primes & (rows - 1)) — the host refuses anything else (`FusedFieldForward._unit_table`) — so every
+//     (index = xor of primes & (rows - 1)) — the host refuses anything else (`FusedFieldForward.supported`) — so every
 //     index is in range by construction: no modulo, no per-corner branch around the gather (an invalid corner's byte
 //     is read and multiplied by a zero weight), coordinates of an outside point are replaced by 0 first;
 //   * per-axis work is shared by the corners: 2 D multiplies for the index parts, the D = 3 weights as four x-y

@@ -33,7 +33,8 @@
 
 namespace cnc {
 
-constexpr uint32_t kMaxUnits = 64;        // rows of the unit table kept in LDS (the host refuses more)
+constexpr uint32_t kMaxUnits = 64;        // rows of the unit table kept in LDS: launch_field_fused_w2 refuses more, and so does
+                                          // FusedFieldForward.supported (cnc_amd/field.py), whose models then take the op chain
 
 // LDS layout in halves: [4 chunk buffers of two planes | colour: the activation planes alias them, + 32 floats] [unit table]
 template <int NT, bool RGB>

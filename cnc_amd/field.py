@@ -328,6 +328,8 @@ class FusedFieldForward:
     The default three-product fp16 form carries a range guard: a call in which a hidden activation or a weight left
     fp16's range is recomputed by the exact-fp32 kernel, decided on the device (include/cnc_hip.h)."""
 
+    MAX_UNITS = 64          # kMaxUnits of field_fused2.hip: cnc_field_fused_forward returns CNC_ERR_UNSUPPORTED above it
+
     def __init__(self, field: "NGPRadianceField_mygrid_2D3D"):
         from . import _caches
         self.field = field
@@ -355,6 +357,8 @@ class FusedFieldForward:
                 and all(e.ste_binary and e.fused_ste and e.bitplane and e.n_features == F_ for e in encs)
                 and encs[0].num_dim == 3 and all(e.num_dim == 2 for e in encs[1:])
                 and len({e.n_levels for e in encs[1:]}) == 1
+                # the two-wave kernels keep the unit table in LDS: 64 (encoder, level) units (kMaxUnits, field_fused2.hip)
+                and sum(e.n_levels for e in encs) <= FusedFieldForward.MAX_UNITS
                 and F_ in (2, 4, 8) and H in (64, 160) and 1 + geo <= 32 * nt2 and (17 + geo + 31) // 32 * 32 <= H
                 and len(mb.network) == 3 and len(field.mlp_head) == 5
                 and all(l.out_features == H for l in (field.mlp_head[0], field.mlp_head[2]))

@@ -192,10 +192,11 @@ def _sh4_f64(d):
         1.4453057213202769 * z * (x2 - y2), 0.59004358992664352 * x * (-x2 + 3.0 * y2)], -1)
 
 
-def _float64_field(f, feats, xu, dirs, wr, wd):
+def _float64_field(f, feats, xu, dirs, wr, wd, want_dx=False):
     """The two networks of ngp.py:506-566 on given first-layer input rows, forward and backward, in float64 NumPy:
     (rgb, density, {parameter name: gradient of sum(rgb * wr) + sum(density * wd)}, {parameter name: the same sums over the
-    ABSOLUTE values of every term — what an entry's rounding error is proportional to})."""
+    ABSOLUTE values of every term — what an entry's rounding error is proportional to}); `want_dx`: and, fifth, the gradient
+    of the rows' encoder columns dX = g1 W1[:, :n_enc] (what the four encoders' backward is fed)."""
     import numpy as np
     mb, mh = f.mlp_base.network, f.mlp_head
     P = {n: t.detach().cpu().numpy().astype(np.float64) for n, t in
@@ -229,6 +230,9 @@ def _float64_field(f, feats, xu, dirs, wr, wd):
     a1 = (a2 @ np.abs(P["W2"])) * (h1 > 0)
     A = {"W5": a5.T @ np.abs(h4), "b5": a5.sum(0), "W4": a4.T @ np.abs(h3), "b4": a4.sum(0), "W3": a3.T @ np.abs(hin),
          "b3": a3.sum(0), "W2": a2.T @ np.abs(h1), "b2": a2.sum(0), "W1": a1.T @ np.abs(X), "b1": a1.sum(0)}
+    if want_dx:
+        n_enc = sum(e.n_output_dims for e in f.mlp_base._encoders())
+        return rgb, den, G, A, g1 @ P["W1"][:, :n_enc]
     return rgb, den, G, A
 
 
