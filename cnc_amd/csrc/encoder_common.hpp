@@ -166,6 +166,146 @@ struct Corners {
     }
 };
 
+// Two cut-down forms of Corners<3, false>::setup for callers that need part of it and are bound by vector issue (the
+// bin pass of grid_encode_binned.hip).  BIT-IDENTICAL to it in what they do return: the same float operations in the
+// same order (the file is built with -ffp-contract=off), the same integer values.
+//
+// What a level fixes is worked out once (scalar registers): dense or hashed by the stride walk of grid_row, the
+// multiplier of every axis (a stride or a prime; x always has 1), power-of-two rows or not.
+// HP2 = true is the form for a level that is hashed into a power-of-two number of rows (`hashed_pow2()`, wave-uniform:
+// the caller branches on it once, outside its loops): the multipliers are the primes as literals and a row is
+// xor & (rows - 1), with no branch per corner.  HP2 = false handles every level — dense ones, other row counts — with
+// the run-time decisions of Corners::setup, the modulo behind its wave-uniform test.
+struct LevelGeom3 {
+    uint32_t R, hs;
+    uint32_t m[3];
+    bool     hashed, pow2;
+
+    __device__ __forceinline__ void init(uint32_t R_, uint32_t hs_)
+    {
+        constexpr uint32_t primes[3] = {1u, 2654435761u, 805459861u};
+        R = R_;
+        hs = hs_;
+        uint32_t stride = 1, sd[3];
+#pragma unroll
+        for (uint32_t d = 0; d < 3; d++) {
+            sd[d] = stride;
+            if (stride <= hs) stride *= R;
+        }
+        hashed = stride > hs;
+        pow2 = (hs & (hs - 1)) == 0;
+#pragma unroll
+        for (uint32_t d = 0; d < 3; d++) m[d] = hashed ? primes[d] : sd[d];
+    }
+
+    __device__ __forceinline__ bool hashed_pow2() const { return hashed && pow2; }
+
+    template <bool HP2>
+    __device__ __forceinline__ uint32_t mul(uint32_t d) const
+    {
+        constexpr uint32_t primes[3] = {1u, 2654435761u, 805459861u};
+        return HP2 ? primes[d] : m[d];
+    }
+
+    // one corner's row from its three per-axis parts, as Corners::setup finishes it
+    template <bool HP2>
+    __device__ __forceinline__ uint32_t fold(uint32_t px, uint32_t py, uint32_t pz) const
+    {
+        if constexpr (HP2) return (px ^ py ^ pz) & (hs - 1);
+        uint32_t index = hashed ? px ^ py ^ pz : px + py + pz;
+        if (pow2) index &= hs - 1;
+        else if (index >= hs) index %= hs;
+        return index;
+    }
+
+    // cell coordinate and fraction along one axis
+    __device__ __forceinline__ uint32_t cell(float x, float& frac) const
+    {
+        float p = x * (float)(R - 2);
+        p = p + 0.5f;
+        const float fl = floorf(p);
+        frac = p - fl;
+        return (uint32_t)fl;
+    }
+
+    __device__ __forceinline__ bool border(uint32_t q) const { return (q == 0) | (q == R - 1); }
+};
+
+// Rows and validity of the eight corners, nothing else: no weight, no sum, no division.  Two 32-bit multiplies (y and
+// z; x's multiplier is 1): the +1 neighbour's part is an add behind its axis' multiply, (g + 1) m == g m + m in
+// uint32, and where the clamp min(g + 1, R - 1) bites (g + 1 > R - 1: no point of the unit box gets there, but the
+// value stays Corners' for any input) the part is the wave-uniform (R - 1) m.
+// Handed out pair by pair, fn(p, valid0, valid1, row0, row1) for p = 0 .. 3 (corners 2 p and 2 p + 1), and the flags
+// kept in named scalars: an array of bool is an array of bytes to the compiler, which then keeps the flags in vector
+// registers and combines them with 16-bit vector instructions instead of scalar lane-mask operations.
+template <bool HP2, typename Fn>
+__device__ __forceinline__ void corner_rows3(const float (&x)[3], const LevelGeom3& lv, Fn&& fn)
+{
+    float          frac;
+    const uint32_t gx = lv.cell(x[0], frac), gy = lv.cell(x[1], frac), gz = lv.cell(x[2], frac);
+    const uint32_t x1 = min(gx + 1, lv.R - 1), y1 = min(gy + 1, lv.R - 1), z1 = min(gz + 1, lv.R - 1);
+    const bool     bx0 = lv.border(gx), bx1 = lv.border(x1);
+    const bool     by0 = lv.border(gy), by1 = lv.border(y1);
+    const bool     bz0 = lv.border(gz), bz1 = lv.border(z1);
+    const uint32_t my = lv.mul<HP2>(1), mz = lv.mul<HP2>(2);
+    const uint32_t py0 = gy * my, py1 = gy + 1 <= lv.R - 1 ? py0 + my : (lv.R - 1) * my;
+    const uint32_t pz0 = gz * mz, pz1 = gz + 1 <= lv.R - 1 ? pz0 + mz : (lv.R - 1) * mz;
+#pragma unroll
+    for (uint32_t p = 0; p < 4; p++) {
+        const bool     byz = ((p & 1u) ? by1 : by0) || ((p & 2u) ? bz1 : bz0);
+        const uint32_t py = (p & 1u) ? py1 : py0, pz = (p & 2u) ? pz1 : pz0;
+        const bool     v0 = !(bx0 || byz), v1 = !(bx1 || byz);
+        fn(p, v0, v1, v0 ? lv.fold<HP2>(gx, py, pz) : 0u, v1 ? lv.fold<HP2>(x1, py, pz) : 0u);
+    }
+}
+
+// Corner pair p (corners 2 p and 2 p + 1: the x-neighbours at y bit p & 1, z bit p >> 1) with everything an item of the
+// bin pass carries: the pair's weights, rows and validity, and 1 / (sum of the valid weights of all eight corners).
+// The eight weights are formed as Corners forms them, ((tx ty) tz), and summed over the valid corners in corner order;
+// rows only for the pair (two multiplies, on the selected y and z coordinates).  p may be a run-time value.
+struct CornerPair3 {
+    float    w0, w1;
+    uint32_t row0, row1;
+    bool     valid0, valid1;
+    float    wn_re;
+
+    template <bool HP2>
+    __device__ __forceinline__ void setup(const float (&x)[3], const LevelGeom3& lv, uint32_t p)
+    {
+        float          fx, fy, fz;
+        const uint32_t gx = lv.cell(x[0], fx), gy = lv.cell(x[1], fy), gz = lv.cell(x[2], fz);
+        const uint32_t x1 = min(gx + 1, lv.R - 1), y1 = min(gy + 1, lv.R - 1), z1 = min(gz + 1, lv.R - 1);
+        const float    ex = 1 - fx, ey = 1 - fy, ez = 1 - fz;
+        const bool     bx0 = lv.border(gx), bx1 = lv.border(x1);
+        const bool     by0 = lv.border(gy), by1 = lv.border(y1);
+        const bool     bz0 = lv.border(gz), bz1 = lv.border(z1);
+        float          wn = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++) {
+            float wi = 1;
+            wi *= (i & 1u) ? fx : ex;
+            wi *= (i & 2u) ? fy : ey;
+            wi *= (i & 4u) ? fz : ez;
+            const bool ok = !(((i & 1u) ? bx1 : bx0) || ((i & 2u) ? by1 : by0) || ((i & 4u) ? bz1 : bz0));
+            wn += ok ? wi : 0.0f;
+        }
+        if (wn == 0) wn = 1e-9f;
+        wn_re = 1.0f / wn;
+        // the pair's own two weights again, from the selected y and z factors: the same products, the same bits
+        const bool  by = p & 1u, bz = p & 2u;
+        const float ty = by ? fy : ey, tz = bz ? fz : ez;
+        w0 = (ex * ty) * tz;
+        w1 = (fx * ty) * tz;
+        const uint32_t qy = by ? y1 : gy, qz = bz ? z1 : gz;
+        const bool     byz = lv.border(qy) || lv.border(qz);     // (tested on the selected coordinates: no select of flags)
+        const uint32_t py = qy * lv.mul<HP2>(1), pz = qz * lv.mul<HP2>(2);
+        valid0 = !(bx0 || byz);
+        valid1 = !(bx1 || byz);
+        row0 = valid0 ? lv.fold<HP2>(gx, py, pz) : 0u;
+        row1 = valid1 ? lv.fold<HP2>(x1, py, pz) : 0u;
+    }
+};
+
 // One point's gradient row g[0 .. F) scattered to the table rows of its valid corners (bit i of `valid`): the path of
 // the points the merging kernels cannot key (kCellKeyMaxRes).  The STE mask (|param| <= 1) when mask_on.  Weights and
 // rows are rebuilt corner by corner from the cell and the fractions with the arithmetic of Corners::setup and grid_row

@@ -32,6 +32,8 @@
 #include "common.hpp"
 #include "encoder_common.hpp"
 
+#include <type_traits>
+
 namespace cnc {
 
 constexpr uint32_t kSlabLog2 = 8;                  // rows per owner wave (<= 12: item row fields)
@@ -100,28 +102,30 @@ __global__ __launch_bounds__(1024) void k_bwd_bin(BinnedArgs a)
     uint32_t*      bin_count = a.bin_count + (size_t)blockIdx.y * a.bins;
     Item*          items = a.items + (size_t)blockIdx.y * a.bins * a.cap;
     const uint32_t base_i = blockIdx.x * 1024 * kBinSamplesPerThread;
+    LevelGeom3     lv;
+    lv.init(R, hs);
 
     for (uint32_t b = threadIdx.x; b < a.bins; b += 1024) s_cnt[b] = 0;
     __syncthreads();
 
-    // ---- count ----
-    if (binnable) {
+    // ---- count (rows and validity only; the level's kind decided once, see LevelGeom3) ----
+    auto count = [&](auto hp2) {
 #pragma unroll
         for (uint32_t k = 0; k < kBinSamplesPerThread; k++) {
             const uint32_t i = base_i + k * 1024 + threadIdx.x;
             float x[3];
             if (i < a.N && load_point<3>(a.inputs, i, x)) {
-                Corners<3, false> c;
-                c.setup(x, R, hs, 0, nullptr);
-#pragma unroll
-                for (uint32_t p = 0; p < 4; p++) {
-                    const bool     v0 = c.valid[2 * p], v1 = c.valid[2 * p + 1];
-                    const uint32_t b0 = c.row[2 * p] >> kSlabLog2, b1 = c.row[2 * p + 1] >> kSlabLog2;
+                corner_rows3<decltype(hp2)::value>(x, lv, [&](uint32_t p, bool v0, bool v1, uint32_t r0, uint32_t r1) {
+                    const uint32_t b0 = r0 >> kSlabLog2, b1 = r1 >> kSlabLog2;
                     if (v0) atomicAdd(&s_cnt[b0], 1u);
                     if (v1 && !(v0 && b1 == b0)) atomicAdd(&s_cnt[b1], 1u);
-                }
+                });
             }
         }
+    };
+    if (binnable) {
+        if (lv.hashed_pow2()) count(std::true_type{});
+        else count(std::false_type{});
     }
     __syncthreads();
     // ---- reserve: one global atomic per non-empty bin of this block ----
@@ -193,9 +197,12 @@ __global__ __launch_bounds__(1024) void k_bwd_bin(BinnedArgs a)
 // 64-byte request), and with everything else overlapped the whole backward call sits on the L2 -> fabric request
 // rate (53 M requests in 1.06 ms = 50 G/s, the ceiling of tools/fetch_calib.hip).  Here the block sorts the SOURCE
 // IDS of its items by bin in LDS (a 16-bit id per item: 40 KB where the 16-byte payloads would need 256 KB) and then
-// walks the sorted list: lane t rebuilds item t from its sample (the corner set-up again: vector ALU is what this
-// pass has to spare) and stores it, so that a wave-instruction writes 64 consecutive slots of the sorted order —
-// whole (block, bin) runs, 128 contiguous bytes on average.
+// walks the sorted list: lane t rebuilds item t from its sample and stores it, so that a wave-instruction writes 64
+// consecutive slots of the sorted order — whole (block, bin) runs, 128 contiguous bytes on average.
+// The set-up runs once per sample to count and once per item in the walk, about 5.4 times per (sample, level), and the
+// pass shares the SIMDs with the vector-issue-bound merge kernel of the coarse levels on the other stream: the count
+// phase takes rows and validity only (corner_rows3) and the walk one corner pair (CornerPair3), not the general
+// Corners::setup; the cold paths keep that one.
 constexpr uint32_t kSortBins = 2048;                                  // three LDS arrays of that many words
 #ifndef CNC_SORT_SAMPLES_PER_THREAD
 #define CNC_SORT_SAMPLES_PER_THREAD 4
@@ -203,8 +210,25 @@ constexpr uint32_t kSortBins = 2048;                                  // three L
 constexpr uint32_t kSortSamplesPerThread = CNC_SORT_SAMPLES_PER_THREAD;   // 4096 samples per block: runs of 8 items per bin
 constexpr uint32_t kSortItems = 1024 * kSortSamplesPerThread * 5;     // source ids per block (typically 4.2 per sample)
 
-// item of corner pair p (half 0: the x corner's bin, carrying both corners when they share it; half 1: the x+1
-// corner's bin when it differs) — exactly what k_bwd_bin emits
+// The item of one corner pair from its two weights, rows and validity flags (half 0: the x corner's bin, carrying both
+// corners when they share it; half 1: the x+1 corner's bin when it differs) — exactly what k_bwd_bin emits.  The one place
+// that packs an item of the sorted pass.
+__device__ __forceinline__ Item make_item(uint32_t sample, uint32_t half, float w0, float w1, uint32_t r0, uint32_t r1, bool v0,
+                                          bool v1, float wn_re, uint32_t& bin, uint32_t& mask)
+{
+    const uint32_t b0 = r0 >> kSlabLog2, b1 = r1 >> kSlabLog2;
+    const bool     together = v0 && v1 && b1 == b0;
+    Item           it;
+    it.sample = sample;
+    it.w0 = w0 * wn_re;
+    it.w1 = w1 * wn_re;
+    mask = half ? 2u : (together ? 3u : 1u);
+    bin = half ? b1 : b0;
+    it.rows = (r0 & (kSlab - 1)) | (r1 & (kSlab - 1)) << 12 | mask << 24;
+    return it;
+}
+
+// item of corner pair p of a full set-up
 __device__ __forceinline__ Item pair_item(const Corners<3, false>& c, uint32_t sample, uint32_t p, uint32_t half, uint32_t& bin,
                                           uint32_t& mask)
 {
@@ -223,16 +247,13 @@ __device__ __forceinline__ Item pair_item(const Corners<3, false>& c, uint32_t s
         w0 = hit ? c.w[2 * q] : w0;
         w1 = hit ? c.w[2 * q + 1] : w1;
     }
-    const uint32_t b0 = r0 >> kSlabLog2, b1 = r1 >> kSlabLog2;
-    const bool     together = v0 && v1 && b1 == b0;
-    Item           it;
-    it.sample = sample;
-    it.w0 = w0 * c.wn_re;
-    it.w1 = w1 * c.wn_re;
-    mask = half ? 2u : (together ? 3u : 1u);
-    bin = half ? b1 : b0;
-    it.rows = (r0 & (kSlab - 1)) | (r1 & (kSlab - 1)) << 12 | mask << 24;
-    return it;
+    return make_item(sample, half, w0, w1, r0, r1, v0, v1, c.wn_re, bin, mask);
+}
+
+// the same item from the one-pair set-up (the walk of k_bwd_bin_sorted): no selects over the corners
+__device__ __forceinline__ Item pair_item(const CornerPair3& c, uint32_t sample, uint32_t half, uint32_t& bin, uint32_t& mask)
+{
+    return make_item(sample, half, c.w0, c.w1, c.row0, c.row1, c.valid0, c.valid1, c.wn_re, bin, mask);
 }
 
 template <uint32_t F, bool STE>
@@ -254,9 +275,11 @@ __global__ __launch_bounds__(1024) void k_bwd_bin_sorted(BinnedArgs a)
     const uint32_t base_i = blockIdx.x * 1024 * kSortSamplesPerThread;
     const uint32_t tid = threadIdx.x;
     constexpr uint32_t V = F < 4 ? F : 4;
+    LevelGeom3     lv;
+    lv.init(R, hs);
 
-    auto spill_corners = [&](const Corners<3, false>& c, uint32_t i, uint32_t corners) {
-        float        g[F];
+    // sample i's gradient row of this level: what a spilled corner adds atomically
+    auto grad_row = [&](uint32_t i, float (&g)[F]) {
         const float* gp = a.grad + feat_index(a.lay, slot, a.N, i, F);
 #pragma unroll
         for (uint32_t q = 0; q < F; q += V) {
@@ -265,9 +288,20 @@ __global__ __launch_bounds__(1024) void k_bwd_bin_sorted(BinnedArgs a)
 #pragma unroll
             for (uint32_t j = 0; j < V; j++) g[q + j] = gv[j];
         }
+    };
+    auto spill_corners = [&](const Corners<3, false>& c, uint32_t i, uint32_t corners) {
+        float g[F];
+        grad_row(i, g);
 #pragma unroll
         for (uint32_t q = 0; q < 8; q++)
             if ((corners >> q) & 1u) atomic_row<F, STE>(a, mask_on, off + c.row[q], c.w[q] * c.wn_re, g);
+    };
+    // the same for the corners `mask` of one pair, from the pair's own set-up: the item's weights are the products above
+    auto spill_pair = [&](const CornerPair3& c, const Item& it, uint32_t mask) {
+        float g[F];
+        grad_row(it.sample, g);
+        if (mask & 1u) atomic_row<F, STE>(a, mask_on, off + c.row0, it.w0, g);
+        if (mask & 2u) atomic_row<F, STE>(a, mask_on, off + c.row1, it.w1, g);
     };
 
     if (!binnable) {      // a level with more rows than the bins were sized for: every corner goes to atomics
@@ -289,25 +323,26 @@ __global__ __launch_bounds__(1024) void k_bwd_bin_sorted(BinnedArgs a)
     for (uint32_t b = tid; b < kSortBins; b += 1024) s_start[b] = 0;
     __syncthreads();
     // ---- count: every item takes its rank inside its bin; (bin, rank) stay in registers ----
+    // (rows and validity only; the level's kind is decided once for the block, see LevelGeom3)
     uint32_t key[kSortSamplesPerThread][8];
+    auto count = [&](auto hp2) {
 #pragma unroll
-    for (uint32_t k = 0; k < kSortSamplesPerThread; k++) {
+        for (uint32_t k = 0; k < kSortSamplesPerThread; k++) {
 #pragma unroll
-        for (uint32_t q = 0; q < 8; q++) key[k][q] = 0xFFFFFFFFu;
-        const uint32_t i = base_i + k * 1024 + tid;
-        float x[3];
-        if (i < a.N && load_point<3>(a.inputs, i, x)) {
-            Corners<3, false> c;
-            c.setup(x, R, hs, 0, nullptr);
-#pragma unroll
-            for (uint32_t p = 0; p < 4; p++) {
-                const bool     v0 = c.valid[2 * p], v1 = c.valid[2 * p + 1];
-                const uint32_t b0 = c.row[2 * p] >> kSlabLog2, b1 = c.row[2 * p + 1] >> kSlabLog2;
-                if (v0) key[k][2 * p] = b0 | atomicAdd(&s_start[b0], 1u) << 11;
-                if (v1 && !(v0 && b1 == b0)) key[k][2 * p + 1] = b1 | atomicAdd(&s_start[b1], 1u) << 11;
+            for (uint32_t q = 0; q < 8; q++) key[k][q] = 0xFFFFFFFFu;
+            const uint32_t i = base_i + k * 1024 + tid;
+            float x[3];
+            if (i < a.N && load_point<3>(a.inputs, i, x)) {
+                corner_rows3<decltype(hp2)::value>(x, lv, [&](uint32_t p, bool v0, bool v1, uint32_t r0, uint32_t r1) {
+                    const uint32_t b0 = r0 >> kSlabLog2, b1 = r1 >> kSlabLog2;
+                    if (v0) key[k][2 * p] = b0 | atomicAdd(&s_start[b0], 1u) << 11;
+                    if (v1 && !(v0 && b1 == b0)) key[k][2 * p + 1] = b1 | atomicAdd(&s_start[b1], 1u) << 11;
+                });
             }
         }
-    }
+    };
+    if (lv.hashed_pow2()) count(std::true_type{});
+    else count(std::false_type{});
     __syncthreads();
     // ---- reserve (one global atomic per non-empty bin of this block) and exclusive prefix over the bins ----
     const uint32_t n0 = s_start[2 * tid], n1 = s_start[2 * tid + 1];
@@ -362,20 +397,24 @@ __global__ __launch_bounds__(1024) void k_bwd_bin_sorted(BinnedArgs a)
             if (key[k][q] != 0xFFFFFFFFu)
                 s_src[s_start[key[k][q] & 0x7FFu] + (key[k][q] >> 11)] = (uint16_t)((k * 1024 + tid) | (q >> 1) << 13 | (q & 1u) << 15);
     __syncthreads();
-    // ---- walk the sorted list: consecutive lanes, consecutive slots ----
-    for (uint32_t pos = tid; pos < total; pos += 1024) {
-        const uint32_t src = s_src[pos];
-        const uint32_t i = base_i + (src & 0x1FFFu);
-        float x[3];
-        load_point<3>(a.inputs, i, x);
-        Corners<3, false> c;
-        c.setup(x, R, hs, 0, nullptr);
-        uint32_t bin, mask;
-        const Item it = pair_item(c, i, (src >> 13) & 3u, (src >> 15) & 1u, bin, mask);
-        const uint32_t at = s_base[bin] + (pos - s_start[bin]);
-        if (at < a.cap) items[(size_t)bin * a.cap + at] = it;
-        else spill_corners(c, i, mask << (2 * ((src >> 13) & 3u)));
-    }
+    // ---- walk the sorted list: consecutive lanes, consecutive slots (one corner pair's set-up per item) ----
+    auto walk = [&](auto hp2) {
+        for (uint32_t pos = tid; pos < total; pos += 1024) {
+            const uint32_t src = s_src[pos];
+            const uint32_t i = base_i + (src & 0x1FFFu);
+            float x[3];
+            load_point<3>(a.inputs, i, x);
+            CornerPair3 c;
+            c.setup<decltype(hp2)::value>(x, lv, (src >> 13) & 3u);
+            uint32_t bin, mask;
+            const Item it = pair_item(c, i, (src >> 15) & 1u, bin, mask);
+            const uint32_t at = s_base[bin] + (pos - s_start[bin]);
+            if (at < a.cap) items[(size_t)bin * a.cap + at] = it;
+            else spill_pair(c, it, mask);
+        }
+    };
+    if (lv.hashed_pow2()) walk(std::true_type{});
+    else walk(std::false_type{});
 }
 
 // LDS accumulators are stored by 16-byte chunk: acc[chunk][row][4 floats].  With row-major
