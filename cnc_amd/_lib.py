@@ -181,6 +181,7 @@ SIGNATURES = {
     "cnc_ctx_window_gather": [_vp] * 8,
     "cnc_rows_scatter": [_vp, _vp, _vp, C.c_uint64, _u32, _vp],
     "cnc_table_adam": [_vp] + [C.c_double] * 6 + [_vp],
+    "cnc_table_adam_scaled": [_vp, _vp] + [C.c_double] * 6 + [_vp],
     "cnc_ray_window_positions": [_vp] * 10 + [_u32, _vp],
     "cnc_scatter_counted": [_vp, _vp, _vp, _vp, C.c_uint64, _vp],
     "cnc_ctx_compact": [_vp, _vp, _vp, _vp, C.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp],

@@ -1,11 +1,14 @@
 """The optimizer's update of the feature tables as ONE kernel that sums the step's gradient pieces on the way in
-(cnc_table_adam, csrc/table_adam.hip) — for the single-process training step (cnc_amd.trainer).
+(cnc_table_adam, csrc/table_adam.hip) — for the training step (cnc_amd.trainer), single-process and data-parallel alike: the
+data-parallel step hands the all-reduced SUM of the ray-loss gradient over as the first piece with the factor 1 / world
+(cnc_table_adam_scaled), so the mean is taken inside the kernel.
 
 The tables stay in the Trainer's torch.optim.Adam (their own parameter group: one learning-rate schedule for everything),
 and the kernel works on THAT optimizer's state tensors (`exp_avg`, `exp_avg_sq`, the float32 device-side `step` of its
 fused form): a step may go through either — `TableAdam.step(...)` leaves the tables' `.grad` None, which is how
 `Optimizer.step()` skips a parameter, so the library's step that follows updates everything else; a step whose gradients
-were flushed into `.grad` instead (data parallel, the tests that read `.grad`) goes through the library as before.
+were flushed into `.grad` instead (`Trainer.fused_table_adam = False`, the tests that read `.grad`) goes through the library
+as before.
 
 Reference: torch.optim.Adam(lr, eps=1e-15, weight_decay) over every parameter, stepped once per iteration
 (examples/train_CNC_nerf_synthetic.py:254-259,363).
@@ -50,6 +53,22 @@ class TableAdam:
             if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or p.numel() % 4:
                 raise ValueError("TableAdam: contiguous float32 device tables of a multiple of 4 elements")
         self.steps_done = 0            # host mirror of the state's step count (the bias corrections are host scalars)
+        self.last_grad_scale = 1.0     # the factor of the last `step`'s `.grad` pieces (for the tests)
+        self.resync()                  # an optimizer that has stepped (or loaded a state) before this was built
+
+    def refusal(self, row_ranges: Dict[int, Sequence[Tuple[int, int]]], max_pieces: int) -> Optional[str]:
+        """What cnc_table_adam would refuse in the middle of a step, checked once: `row_ranges[id(p)]` = every (first row, end
+        row) a piece of table `p` can cover short of the whole table, `max_pieces` = the most pieces any schedule hands
+        over for one table, `.grad` included.  Returns the reason, or None when every step can go through the kernel."""
+        if max_pieces > 4:
+            return f"a step can hold {max_pieces} gradient pieces for one table, the kernel takes four"
+        for p in self.tables:
+            row = p.numel() // p.shape[0]
+            for r0, r1 in row_ranges.get(id(p), ()):
+                lo, hi = r0 * row, r1 * row
+                if not 0 <= lo <= hi <= p.numel() or lo % 4 or (hi % 4 and hi != p.numel()):
+                    return f"a gradient piece covers elements [{lo}, {hi}) of a table of {p.numel()}: not whole float4s"
+        return None
 
     def _state(self, p):
         st = self.opt.state[p]
@@ -62,17 +81,24 @@ class TableAdam:
         return st
 
     def resync(self) -> None:
-        """Take the step count over from the optimizer's state (after steps that went through the library)."""
+        """Take the step count over from the optimizer's state (after steps that went through the library).  Nothing
+        re-reads it per step: whoever loads a state into the optimizer calls this — `Trainer.load_optimizer_state` does;
+        `opt.load_state_dict` on its own leaves `steps_done`, and with it the bias corrections, stale."""
         st = self.opt.state.get(self.tables[0], {})
-        self.steps_done = int(st["step"].item()) if len(st) else 0
+        self.steps_done = int(float(st["step"])) if len(st) else 0
 
     @torch.no_grad()
-    def step(self, pieces: Dict[int, List[Piece]]) -> None:
+    def step(self, pieces: Dict[int, List[Piece]], grad_scale: float = 1.0) -> None:
         """One Adam update of every table from its gradient pieces (`pieces[id(p)]`, in the order they are to be summed; a
         table's own `.grad`, if autograd left one, goes first and is dropped).  On the current stream: every piece must
         be complete on it.  A table with no piece at all is updated with a zero gradient — like the library's step on a
-        `.grad` of zeros (a table always has a gradient in a training step; moments and weight decay move it regardless)."""
+        `.grad` of zeros (a table always has a gradient in a training step; moments and weight decay move it regardless).
+        `grad_scale` (a float32 value): the factor of every table's `.grad` piece — 1 / world for the data-parallel step,
+        whose `.grad` is the SUM over the ranks; the other pieces are taken as they are."""
         g = self.group
+        grad_scale = float(grad_scale)
+        if grad_scale != 1.0 and any(p.grad is None for p in self.tables):
+            raise RuntimeError("TableAdam: a gradient scale but a table without `.grad` (the scale belongs to that piece)")
         a = _lib.AdamTables()
         a.n_tables = len(self.tables)
         keep = []
@@ -109,10 +135,15 @@ class TableAdam:
                 torch._foreach_zero_(counters)
         b1, b2 = g["betas"]
         lr = g["lr"]
-        _lib.check(_lib.lib().cnc_table_adam(C.byref(a), float(lr), float(b1), float(b2), float(g["eps"]),
-                                             float(g["weight_decay"]), float(self.steps_done + 1),
-                                             torch.cuda.current_stream(self.tables[0].device).cuda_stream), "cnc_table_adam")
+        args = (float(lr), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), float(self.steps_done + 1),
+                torch.cuda.current_stream(self.tables[0].device).cuda_stream)
+        if grad_scale == 1.0:
+            _lib.check(_lib.lib().cnc_table_adam(C.byref(a), *args), "cnc_table_adam")
+        else:                          # `.grad` is slot 0 of every table (checked above: they all have one)
+            scale = (C.c_float * 4)(grad_scale, 1.0, 1.0, 1.0)
+            _lib.check(_lib.lib().cnc_table_adam_scaled(C.byref(a), scale, *args), "cnc_table_adam_scaled")
         self.steps_done += 1           # behind the call: a refused step has changed nothing on the device, nor here
+        self.last_grad_scale = grad_scale
         # the kernel writes the tables through their addresses: `Tensor._version` does not move, so the copies keyed on it
         # (the encoders' sign bit planes, packed weights) are dropped here as after any optimizer step (cnc_amd._caches)
         _caches.invalidate_all()

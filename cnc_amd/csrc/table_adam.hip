@@ -17,6 +17,10 @@
 //     v    = b2 v + (1 - b2) g g
 //     p   -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // tests/test_gpu_table_adam.py holds it against torch.optim.Adam(fused=True) and the plain float64 formula.
+//
+// cnc_table_adam_scaled: the same with a factor per piece slot, g = ((s0 g0 + s1 g1) + s2 g2) + s3 g3 — the data-parallel step's
+// first piece is the all-reduced SUM of the ray-loss gradient and s0 = 1 / world, so the bucket is not divided first
+// (tests/test_gpu_table_adam_scaled.py, tests/test_gpu_dp_table_adam.py).
 #include "common.hpp"
 
 namespace cnc {
@@ -36,7 +40,16 @@ __device__ __forceinline__ void adam_one(float& p, float& m, float& v, float g, 
 
 constexpr uint32_t kAdamThreads = 256, kAdamVec = 4, kAdamPerBlock = kAdamThreads * kAdamVec * 4;   // 4096 elements a block
 
-__global__ __launch_bounds__(kAdamThreads) void k_table_adam(cnc_adam_tables_t a, AdamScalars s)
+// cnc_table_adam_scaled's per-slot factors (data parallel: the all-reduced SUM of the ray-loss gradient times 1 / world)
+struct AdamPieceScale {
+    float s[4];
+};
+
+// SCALED = false is cnc_table_adam's kernel as it always was (nothing reads `scale`: 16 bytes of kernel arguments);
+// SCALED = true multiplies slot k's piece by scale.s[k] — its own fp32 product, rounded, then the add (-ffp-contract=off) —
+// unless that factor is exactly 1.
+template <bool SCALED>
+__global__ __launch_bounds__(kAdamThreads) void k_table_adam(cnc_adam_tables_t a, AdamScalars s, AdamPieceScale scale)
 {
     // which table this block works on (block ranges are consecutive per table)
     uint32_t t = 0;
@@ -60,7 +73,11 @@ __global__ __launch_bounds__(kAdamThreads) void k_table_adam(cnc_adam_tables_t a
             for (uint32_t k = 0; k < 4; k++) {
                 // a source covers [lo, hi) of the table (multiples of 4: whole rows of F >= 4 features, checked by the host)
                 if (T.g[k] && i >= T.g_lo[k] && i < T.g_hi[k]) {
-                    const float4 q = *reinterpret_cast<const float4*>(T.g[k] + (i - T.g_lo[k]));
+                    float4 q = *reinterpret_cast<const float4*>(T.g[k] + (i - T.g_lo[k]));
+                    if constexpr (SCALED) {
+                        const float w = scale.s[k];
+                        if (w != 1.0f) { q.x *= w; q.y *= w; q.z *= w; q.w *= w; }
+                    }
                     if (first) g = q;
                     else { g.x += q.x; g.y += q.y; g.z += q.z; g.w += q.w; }
                     first = false;
@@ -89,7 +106,10 @@ __global__ __launch_bounds__(kAdamThreads) void k_table_adam(cnc_adam_tables_t a
                 bool  first = true;
                 for (uint32_t k = 0; k < 4; k++)
                     if (T.g[k] && j >= T.g_lo[k] && j < T.g_hi[k]) {
-                        const float q = T.g[k][j - T.g_lo[k]];
+                        float q = T.g[k][j - T.g_lo[k]];
+                        if constexpr (SCALED) {
+                            if (scale.s[k] != 1.0f) q *= scale.s[k];
+                        }
                         g = first ? q : g + q;
                         first = false;
                     }
@@ -104,10 +124,16 @@ __global__ __launch_bounds__(kAdamThreads) void k_table_adam(cnc_adam_tables_t a
 
 }   // namespace cnc
 
-extern "C" int cnc_table_adam(const cnc_adam_tables_t* tables, double lr, double beta1, double beta2, double eps,
-                              double weight_decay, double step, void* stream)
+// the argument checks, the block ranges and the scalar factors both entries share; `scale` = NULL: cnc_table_adam
+static int table_adam_launch(const cnc_adam_tables_t* tables, const float* scale, double lr, double beta1, double beta2,
+                             double eps, double weight_decay, double step, void* stream)
 {
     if (!tables || tables->n_tables == 0 || tables->n_tables > 4 || !(step >= 1.0)) return CNC_ERR_INVALID_VALUE;
+    cnc::AdamPieceScale ps;
+    for (uint32_t k = 0; k < 4; k++) {
+        ps.s[k] = scale ? scale[k] : 1.0f;
+        if (!(ps.s[k] > 0.0f) || std::isinf(ps.s[k])) return CNC_ERR_INVALID_VALUE;      // NaN, zero, negative, infinite
+    }
     cnc_adam_tables_t a = *tables;
     uint64_t          blocks = 0;
     for (uint32_t t = 0; t < a.n_tables; t++) {
@@ -134,6 +160,21 @@ extern "C" int cnc_table_adam(const cnc_adam_tables_t* tables, double lr, double
     s.bc2_sqrt = sqrt(bc2);
     s.eps = eps;
     s.wd = weight_decay;
-    hipLaunchKernelGGL(cnc::k_table_adam, dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, s);
+    if (scale)
+        hipLaunchKernelGGL(cnc::k_table_adam<true>, dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, s, ps);
+    else
+        hipLaunchKernelGGL(cnc::k_table_adam<false>, dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, s, ps);
     return cnc::launch_status();
+}
+
+extern "C" int cnc_table_adam(const cnc_adam_tables_t* tables, double lr, double beta1, double beta2, double eps,
+                              double weight_decay, double step, void* stream)
+{
+    return table_adam_launch(tables, nullptr, lr, beta1, beta2, eps, weight_decay, step, stream);
+}
+
+extern "C" int cnc_table_adam_scaled(const cnc_adam_tables_t* tables, const float* piece_scale, double lr, double beta1,
+                                     double beta2, double eps, double weight_decay, double step, void* stream)
+{
+    return table_adam_launch(tables, piece_scale, lr, beta1, beta2, eps, weight_decay, step, stream);
 }

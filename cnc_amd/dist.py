@@ -103,6 +103,26 @@ class GradBucket:
                 v.copy_(p.grad)
             p.grad = v
 
+    def runs_excluding(self, params: Iterable[torch.nn.Parameter]) -> List[Tuple[int, int]]:
+        """The contiguous runs [lo, hi) of the gradient part of the flat buffer that belong to none of `params` (which must
+        all be in the bucket), in ascending order; neighbouring parameters share a run, the tail slots are in none.  What a
+        caller that averages some parameters' gradients elsewhere (the tables: inside their optimizer kernel) still has to
+        divide: `flat[lo:hi]` per run."""
+        skip = {id(p) for p in params}
+        if not skip <= {id(p) for p in self.params}:
+            raise ValueError("GradBucket.runs_excluding: a parameter that is not in the bucket")
+        runs: List[Tuple[int, int]] = []
+        o = 0
+        for p in self.params:
+            n = p.numel()
+            if id(p) not in skip and n:
+                if runs and runs[-1][1] == o:
+                    runs[-1] = (runs[-1][0], o + n)
+                else:
+                    runs.append((o, o + n))
+            o += n
+        return runs
+
     def zero(self) -> None:
         self.flat.zero_()
 

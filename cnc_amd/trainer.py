@@ -262,6 +262,7 @@ class Trainer:
         self.rank, self.local_rank, self.world = cdist.init()
         self.device = torch.device(device)
         self.dp = self.world > 1 or cdist.forced()       # data-parallel control flow (forced: a one-rank group, test hook)
+        self._inv_world = float(torch.tensor(1.0, dtype=torch.float32) / self.world)     # 1 / world as a float32
         if self.dp and self.device.type == "cuda":
             self.device = torch.device("cuda", cdist.local_device_index())
         elif self.device.type == "cuda" and self.device.index is None:
@@ -356,6 +357,7 @@ class Trainer:
                 return r
             self._ctx_rand = None
             self.context.rand_like = synced_rand_like
+        self._check_table_adam()            # (again: the sinks, the planes' graph and the buckets exist now)
 
     def build_context(self):
         """The context models of this configuration (train:221-241).  Their vertex tables draw from the CPU
@@ -393,20 +395,59 @@ class Trainer:
         self.opt = torch.optim.Adam([{"params": rest}, {"params": tables}], lr=c.lr, eps=1e-15, weight_decay=c.weight_decay,
                                     fused=one_pass)
         self.opt2 = torch.optim.Adam(self.context.parameters(), lr=c.lr, eps=1e-15, fused=one_pass)
-        # Single-process steps with the gradient sinks: the tables' update reads the gradient pieces where they lie (one
-        # kernel instead of clone + multi-tensor add + the library's Adam over the sum; CNC_TABLE_ADAM=0 or
-        # `self.fused_table_adam = False`: pieces flushed into `.grad`, library step — what data-parallel steps do)
+        # The tables' update reads the gradient pieces where they lie (one kernel instead of clone + multi-tensor add + the
+        # library's Adam over the sum; CNC_TABLE_ADAM=0 or `self.fused_table_adam = False`: pieces flushed into `.grad`,
+        # library step).  Data parallel too: the all-reduced sum is one more piece, the mean is taken inside the kernel.
         self.table_adam = None
-        if one_pass and not self.dp and os.environ.get("CNC_TABLE_ADAM", "1") == "1" \
-                and all(t.numel() % 4 == 0 for t in tables):
+        if one_pass and os.environ.get("CNC_TABLE_ADAM", "1") == "1" and all(t.numel() % 4 == 0 for t in tables):
             self.table_adam = _table_adam.TableAdam(self.opt, tables, self.field.mlp_base._encoders())
         self.fused_table_adam = self.table_adam is not None
+        self._check_table_adam()
 
         def sched(o):
             return torch.optim.lr_scheduler.ChainedScheduler([
                 torch.optim.lr_scheduler.LinearLR(o, start_factor=0.01, total_iters=c.warmup_iters),
                 torch.optim.lr_scheduler.MultiStepLR(o, milestones=list(c.milestones), gamma=0.33)])
         self.sched, self.sched2 = sched(self.opt), sched(self.opt2)
+
+    def _check_table_adam(self) -> None:
+        """Once, not in the middle of a step: what cnc_table_adam would refuse of the pieces this Trainer's schedules can
+        hand it — then the steps take the `.grad` path (`fused_table_adam = False`), with one warning."""
+        ta = self.table_adam
+        if ta is None or not self.fused_table_adam:
+            return
+        # the one piece that is not table-sized: the 3-D table's finest level out of the planes' graph (_planes_graph.capture)
+        off3 = getattr(self.context, "_off3_host", None)
+        rows = {} if off3 is None or len(off3) < 2 else {id(ta.tables[0]): [(int(off3[-2]), int(off3[-1]))]}
+        # the most pieces a step of THIS Trainer hands over for one table (what is not built yet counts as present).  Single
+        # process: `.grad`, the render sink, the entropy sink, the planes' graph; data parallel: `.grad` (the bucket: the
+        # render sink is flushed into it), the entropy pass's returned gradient, the entropy sink, the planes' graph
+        bucket = getattr(self, "bucket", None)
+        sinks = [getattr(self, "sink_render", True) is not None, getattr(self, "sink_ctx", True) is not None]
+        graph = getattr(self, "planes_graph", True) is not None
+        if self.dp:
+            pieces = 1 + 1 + sinks[1] + (graph and getattr(self, "planes_graph_dp", True))
+        else:
+            pieces = 1 + sinks[0] + sinks[1] + graph
+        why = ta.refusal(rows, max_pieces=pieces)
+        if why is None and bucket is not None:
+            tids = {id(p) for p in ta.tables}
+            for b in (bucket, self.bucket_ctx):
+                if any(v.data_ptr() % 16 for p, v in zip(b.params, b.views) if id(p) in tids):
+                    why = "a table's slice of the gradient bucket is not 16-byte aligned"
+        if why is not None:
+            import warnings
+            warnings.warn(f"cnc_amd: the tables' Adam kernel is off, their gradients go through `.grad` ({why})")
+            self.fused_table_adam = False
+
+    def load_optimizer_state(self, opt_state, opt2_state=None) -> None:
+        """`load_state_dict` of the field's (and the context models') optimizer.  The tables' kernel takes its bias corrections
+        from a host mirror of the optimizer's step count: re-read here."""
+        self.opt.load_state_dict(opt_state)
+        if opt2_state is not None:
+            self.opt2.load_state_dict(opt2_state)
+        if self.table_adam is not None:
+            self.table_adam.resync()
 
     # -------------------------------------------------------------------------------- training
     def _context_pass_worker(self, step, fork, params, grad_mode, autocast):
@@ -806,20 +847,50 @@ class Trainer:
             ev = torch.cuda.Event()
             ev.record()
             self._count_pending = (ev, len(pixels))
-            A.grads.div_(self.world)
-            if ctx_grads is not None:
-                pairs = [(v, g) for v, g in zip(A.views, ctx_grads) if g is not None]
-                torch._foreach_add_([v for v, _ in pairs], [g for _, g in pairs])
-                if self.sink_ctx is not None:
-                    self.sink_ctx.flush()              # `.grad` = A's views (bound before the fork): after the mean
-                if self._planes_replayed:
-                    self.planes_graph.flush()
-            elif c.lmbda > 0:
-                A.grads.add_(B.flat)
+            if self.table_adam is not None and self.fused_table_adam:
+                # The tables' share of the bucket stays the SUM the collective left: it is the first piece of their Adam
+                # update, times 1 / world inside the kernel; the entropy gradient follows as further pieces, in the order and
+                # grouping in which the branch below adds them.  Only the rest of the bucket is averaged and added to here.
+                tids = {id(p) for p in self.table_adam.tables}
+                runs = A.runs_excluding(self.table_adam.tables)
+                table_pieces = {}
+                for lo, hi in runs:
+                    A.flat[lo:hi].div_(self.world)
+                if ctx_grads is not None:
+                    pairs = [(v, g) for p, v, g in zip(A.params, A.views, ctx_grads) if g is not None and id(p) not in tids]
+                    if pairs:
+                        torch._foreach_add_([v for v, _ in pairs], [g for _, g in pairs])
+                    for p, g in zip(A.params, ctx_grads):
+                        if g is not None and id(p) in tids:
+                            table_pieces[id(p)] = [(g if g.is_contiguous() else g.contiguous(), None)]
+                    if self.sink_ctx is not None:      # the heads' gradients into `.grad` = A's views, the tables' buffers listed
+                        self.sink_ctx.flush(table_pieces=table_pieces)
+                    if self._planes_replayed:
+                        self.planes_graph.flush(table_pieces=table_pieces)
+                elif c.lmbda > 0:
+                    for lo, hi in runs:
+                        A.flat[lo:hi].add_(B.flat[lo:hi])
+                    for p, v in zip(B.params, B.views):
+                        if id(p) in tids:              # autograd's gradient + the entropy sink's flush, as ONE piece
+                            table_pieces[id(p)] = [(v, None)]
+            else:
+                A.grads.div_(self.world)
+                if ctx_grads is not None:
+                    pairs = [(v, g) for v, g in zip(A.views, ctx_grads) if g is not None]
+                    torch._foreach_add_([v for v, _ in pairs], [g for _, g in pairs])
+                    if self.sink_ctx is not None:
+                        self.sink_ctx.flush()              # `.grad` = A's views (bound before the fork): after the mean
+                    if self._planes_replayed:
+                        self.planes_graph.flush()
+                elif c.lmbda > 0:
+                    A.grads.add_(B.flat)
             A.bind(force=True)
         if self.table_adam is not None:
             if table_pieces is not None:
-                self.table_adam.step(table_pieces)         # leaves the tables' `.grad` None: the library's step skips them
+                # leaves the tables' `.grad` None: the library's step skips them.  Data parallel: `.grad` is the bucket's view
+                # with the sum over the ranks (bound just above), the first piece; 1 / world as a float32
+                scale = 1.0 if self.bucket is None else self._inv_world
+                self.table_adam.step(table_pieces, grad_scale=scale)
             else:
                 self.table_adam.steps_done += 1            # the library steps them below
         self.opt.step()

@@ -792,6 +792,15 @@ typedef struct {
 int cnc_table_adam(const cnc_adam_tables_t* tables, double lr, double beta1, double beta2, double eps, double weight_decay,
                    double step, void* stream);
 
+/* (ABI v33, added entry: no signature changed) cnc_table_adam with a factor per piece SLOT — the data-parallel step hands over
+ * the all-reduced SUM of the ray-loss gradient as slot 0 with 1 / world: piece_scale = host float[4], applied to slot k of
+ * every table, NULL = all 1 (cnc_table_adam itself).  g = ((s0 g0 + s1 g1) + s2 g2) + s3 g3: each product formed and rounded
+ * in fp32 before its add (no fused multiply-add), a slot whose factor is exactly 1 is not multiplied; on the float4 path and
+ * on the scalar tail alike.  Everything else — step counter, sign plane, clip counter, argument checks — is cnc_table_adam's;
+ * a factor that is NaN, infinite, zero or negative: CNC_ERR_INVALID_VALUE before anything is launched.                  */
+int cnc_table_adam_scaled(const cnc_adam_tables_t* tables, const float* piece_scale, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, double step, void* stream);
+
 /* (ABI v30) The front-to-back sampler's depth windows without a host round trip per window (nerfacc/estimators/occ_grid.py
  * `_density_front_to_back`; the reference evaluates sigma_fn on ALL marched samples at once, occ_grid.py:172-238).
  * cnc_ray_window_positions: samples [win_lo[r], win_lo[r] + win_n[r]) of ray r -> positions[o + k] = o_r + (d_r (t0 + t1)) / 2
