@@ -44,6 +44,25 @@ class AdamTables(C.Structure):
     _fields_ = [("table", AdamTable * 4), ("n_tables", _u32), ("first_block", _u32 * 4)]
 
 
+class StepVerdict(C.Structure):
+    """cnc_step_verdict_t (include/cnc_hip.h)."""
+    _fields_ = [("acc", _u32), ("skip", _u32), ("skipped", _u32), ("reasons_seen", _u32), ("b1_pow", C.c_double),
+                ("b2_pow", C.c_double), ("lr_over_bc1", C.c_double), ("one_minus_b1", C.c_double), ("b2", C.c_double),
+                ("one_minus_b2", C.c_double), ("bc2_sqrt", C.c_double), ("eps", C.c_double), ("wd", C.c_double)]
+
+
+class VerdictScan(C.Structure):
+    """cnc_verdict_scan_t (include/cnc_hip.h)."""
+    _fields_ = [("ptr", _vp * 48), ("n", C.c_uint64 * 48), ("n_tensors", _u32), ("guard_seen", _u32), ("pack_id", _u32),
+                ("guard", _vp), ("poison", _vp), ("verdict", _vp)]
+
+
+class VerdictSeal(C.Structure):
+    """cnc_verdict_seal_t (include/cnc_hip.h)."""
+    _fields_ = [("verdict", _vp), ("found_inf", _vp), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("weight_decay", C.c_double), ("clip_count", _vp * 4)]
+
+
 class FieldSave(C.Structure):
     """cnc_field_save_t (include/cnc_hip.h)."""
     _fields_ = [("feat", _vp), ("ld_feat", _u32), ("h1", _vp), ("h3", _vp), ("h4", _vp), ("head_in", _vp), ("ld_head", _u32),
@@ -182,6 +201,9 @@ SIGNATURES = {
     "cnc_rows_scatter": [_vp, _vp, _vp, C.c_uint64, _u32, _vp],
     "cnc_table_adam": [_vp] + [C.c_double] * 6 + [_vp],
     "cnc_table_adam_scaled": [_vp, _vp] + [C.c_double] * 6 + [_vp],
+    "cnc_step_verdict_scan": [C.POINTER(VerdictScan), _vp],
+    "cnc_step_verdict_seal": [C.POINTER(VerdictSeal), _vp],
+    "cnc_table_adam_guarded": [_vp, _vp, _vp, _vp],
     "cnc_ray_window_positions": [_vp] * 10 + [_u32, _vp],
     "cnc_scatter_counted": [_vp, _vp, _vp, _vp, C.c_uint64, _vp],
     "cnc_ctx_compact": [_vp, _vp, _vp, _vp, C.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp],
@@ -215,6 +237,9 @@ CNC_PACK_TRANSPOSE = 1
 CNC_PACK_ZERO_FIRST = 2
 CNC_VOLREND_ACCUMULATE = 1
 CNC_VOLREND_FINALIZE = 2
+CNC_VERDICT_NONFINITE = 1
+CNC_VERDICT_RANGE_GUARD = 2
+CNC_VERDICT_MAX_TENSORS = 48
 ABI_VERSION = 33          # cnc_abi_version() of the library this table was written for
 
 

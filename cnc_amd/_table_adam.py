@@ -52,7 +52,9 @@ class TableAdam:
         for p in self.tables:
             if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or p.numel() % 4:
                 raise ValueError("TableAdam: contiguous float32 device tables of a multiple of 4 elements")
-        self.steps_done = 0            # host mirror of the state's step count (the bias corrections are host scalars)
+        # host mirror of the state's step count (the bias corrections are host scalars).  With a guard (`step(guard=...)`):
+        # the steps ATTEMPTED — a skipped one counts here and not on the device — and no arithmetic reads it
+        self.steps_done = 0
         self.last_grad_scale = 1.0     # the factor of the last `step`'s `.grad` pieces (for the tests)
         self.resync()                  # an optimizer that has stepped (or loaded a state) before this was built
 
@@ -87,14 +89,34 @@ class TableAdam:
         st = self.opt.state.get(self.tables[0], {})
         self.steps_done = int(float(st["step"])) if len(st) else 0
 
+    def _plane_targets(self):
+        """(table index, encoder, table, sign plane, clip counter) for every table whose encoder holds cache buffers of the
+        size the table needs: where the kernel leaves the updated tables' planes."""
+        out = []
+        if self.encoders is not None:
+            for k, (p, e) in enumerate(zip(self.tables, self.encoders)):
+                bits, cc = getattr(e, "_bits", None), getattr(e, "_clip_count", None)
+                if (p.numel() % 8 == 0 and bits is not None and cc is not None and bits.device == p.device
+                        and bits.dtype == torch.uint8 and bits.numel() == p.numel() // 8 and cc.device == p.device
+                        and cc.numel() == 1 and cc.dtype == torch.int32 and getattr(e, "bitplane", True)):
+                    out.append((k, e, p, bits, cc))
+        return out
+
+    def clip_counters(self) -> List[torch.Tensor]:
+        """The clip counters the next `step` adds to: what a guard's seal zeroes in this class's stead."""
+        return [t[4] for t in self._plane_targets()]
+
     @torch.no_grad()
-    def step(self, pieces: Dict[int, List[Piece]], grad_scale: float = 1.0) -> None:
+    def step(self, pieces: Dict[int, List[Piece]], grad_scale: float = 1.0, guard=None) -> None:
         """One Adam update of every table from its gradient pieces (`pieces[id(p)]`, in the order they are to be summed; a
         table's own `.grad`, if autograd left one, goes first and is dropped).  On the current stream: every piece must
         be complete on it.  A table with no piece at all is updated with a zero gradient — like the library's step on a
         `.grad` of zeros (a table always has a gradient in a training step; moments and weight decay move it regardless).
         `grad_scale` (a float32 value): the factor of every table's `.grad` piece — 1 / world for the data-parallel step,
-        whose `.grad` is the SUM over the ranks; the other pieces are taken as they are."""
+        whose `.grad` is the SUM over the ranks; the other pieces are taken as they are.
+        `guard` (a `_step_guard.StepGuard`, sealed for this step with `clip_counters()`): the update goes through
+        cnc_table_adam_guarded — skip and bias corrections come from the guard's buffer on the device, the clip counters
+        were zeroed by its seal, and `steps_done` only counts the attempt."""
         g = self.group
         grad_scale = float(grad_scale)
         if grad_scale != 1.0 and any(p.grad is None for p in self.tables):
@@ -121,23 +143,21 @@ class TableAdam:
         # the updated tables' sign planes into the encoders' own cache buffers (kept at their addresses: a recorded graph
         # reads them there), when those exist in the size the table needs
         self._planes_written = []
-        if self.encoders is not None:
-            counters = []
-            for k, (p, e) in enumerate(zip(self.tables, self.encoders)):
-                bits, cc = getattr(e, "_bits", None), getattr(e, "_clip_count", None)
-                if (p.numel() % 8 == 0 and bits is not None and cc is not None and bits.device == p.device
-                        and bits.dtype == torch.uint8 and bits.numel() == p.numel() // 8 and cc.device == p.device
-                        and cc.numel() == 1 and cc.dtype == torch.int32 and getattr(e, "bitplane", True)):
-                    a.table[k].sign_bits, a.table[k].clip_count = bits.data_ptr(), cc.data_ptr()
-                    counters.append(cc)
-                    self._planes_written.append((e, p))
-            if counters:
-                torch._foreach_zero_(counters)
+        counters = []
+        for k, e, p, bits, cc in self._plane_targets():
+            a.table[k].sign_bits, a.table[k].clip_count = bits.data_ptr(), cc.data_ptr()
+            counters.append(cc)
+            self._planes_written.append((e, p))
+        if counters and guard is None:
+            torch._foreach_zero_(counters)
         b1, b2 = g["betas"]
         lr = g["lr"]
         args = (float(lr), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), float(self.steps_done + 1),
                 torch.cuda.current_stream(self.tables[0].device).cuda_stream)
-        if grad_scale == 1.0:
+        if guard is not None:
+            scale = None if grad_scale == 1.0 else (C.c_float * 4)(grad_scale, 1.0, 1.0, 1.0)
+            _lib.check(_lib.lib().cnc_table_adam_guarded(C.byref(a), scale, guard.ptr, args[-1]), "cnc_table_adam_guarded")
+        elif grad_scale == 1.0:
             _lib.check(_lib.lib().cnc_table_adam(C.byref(a), *args), "cnc_table_adam")
         else:                          # `.grad` is slot 0 of every table (checked above: they all have one)
             scale = (C.c_float * 4)(grad_scale, 1.0, 1.0, 1.0)

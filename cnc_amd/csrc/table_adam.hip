@@ -21,6 +21,12 @@
 // cnc_table_adam_scaled: the same with a factor per piece slot, g = ((s0 g0 + s1 g1) + s2 g2) + s3 g3 — the data-parallel step's
 // first piece is the all-reduced SUM of the ray-loss gradient and s0 = 1 / world, so the bucket is not divided first
 // (tests/test_gpu_table_adam_scaled.py, tests/test_gpu_dp_table_adam.py).
+//
+// cnc_table_adam_guarded: either of the two with the step's verdict in front (step_verdict.hip): `skip` and the scalar factors
+// come from the sealed cnc_step_verdict_t on the device; a skipped step returns before it has loaded or stored anything of a
+// table (tests/test_gpu_guarded_table_adam.py).
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace cnc {
@@ -48,9 +54,20 @@ struct AdamPieceScale {
 // SCALED = false is cnc_table_adam's kernel as it always was (nothing reads `scale`: 16 bytes of kernel arguments);
 // SCALED = true multiplies slot k's piece by scale.s[k] — its own fp32 product, rounded, then the add (-ffp-contract=off) —
 // unless that factor is exactly 1.
-template <bool SCALED>
-__global__ __launch_bounds__(kAdamThreads) void k_table_adam(cnc_adam_tables_t a, AdamScalars s, AdamPieceScale scale)
+// GUARDED = false takes the scalar factors as kernel arguments, as ever (nothing in it knows of a verdict); GUARDED = true takes
+// the sealed verdict's address in their place: two uniform loads, and on skip the block is done.
+template <bool SCALED, bool GUARDED>
+__global__ __launch_bounds__(kAdamThreads) void k_table_adam(
+    cnc_adam_tables_t a, std::conditional_t<GUARDED, const cnc_step_verdict_t*, AdamScalars> sv, AdamPieceScale scale)
 {
+    AdamScalars s;
+    if constexpr (GUARDED) {
+        if (sv->skip != 0u) return;
+        s.lr_over_bc1 = sv->lr_over_bc1; s.one_minus_b1 = sv->one_minus_b1; s.b2 = sv->b2; s.one_minus_b2 = sv->one_minus_b2;
+        s.bc2_sqrt = sv->bc2_sqrt; s.eps = sv->eps; s.wd = sv->wd;
+    } else {
+        s = sv;
+    }
     // which table this block works on (block ranges are consecutive per table)
     uint32_t t = 0;
 #pragma unroll
@@ -124,11 +141,14 @@ __global__ __launch_bounds__(kAdamThreads) void k_table_adam(cnc_adam_tables_t a
 
 }   // namespace cnc
 
-// the argument checks, the block ranges and the scalar factors both entries share; `scale` = NULL: cnc_table_adam
+// the argument checks, the block ranges and the scalar factors the entries share; `scale` = NULL: cnc_table_adam;
+// `verdict` != NULL: cnc_table_adam_guarded (the scalar arguments are then not looked at)
 static int table_adam_launch(const cnc_adam_tables_t* tables, const float* scale, double lr, double beta1, double beta2,
-                             double eps, double weight_decay, double step, void* stream)
+                             double eps, double weight_decay, double step, void* stream,
+                             const cnc_step_verdict_t* verdict = nullptr)
 {
-    if (!tables || tables->n_tables == 0 || tables->n_tables > 4 || !(step >= 1.0)) return CNC_ERR_INVALID_VALUE;
+    if (!tables || tables->n_tables == 0 || tables->n_tables > 4 || !(verdict || step >= 1.0)) return CNC_ERR_INVALID_VALUE;
+    if ((uintptr_t)verdict & 7) return CNC_ERR_INVALID_VALUE;
     cnc::AdamPieceScale ps;
     for (uint32_t k = 0; k < 4; k++) {
         ps.s[k] = scale ? scale[k] : 1.0f;
@@ -151,6 +171,13 @@ static int table_adam_launch(const cnc_adam_tables_t* tables, const float* scale
         blocks += (T.n + cnc::kAdamPerBlock - 1) / cnc::kAdamPerBlock;
     }
     if (blocks > 0x7fffffffull) return CNC_ERR_INVALID_VALUE;
+    if (verdict) {
+        if (scale)
+            hipLaunchKernelGGL((cnc::k_table_adam<true, true>), dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, verdict, ps);
+        else
+            hipLaunchKernelGGL((cnc::k_table_adam<false, true>), dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, verdict, ps);
+        return cnc::launch_status();
+    }
     cnc::AdamScalars s;
     const double     bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
     s.lr_over_bc1 = lr / bc1;
@@ -161,9 +188,9 @@ static int table_adam_launch(const cnc_adam_tables_t* tables, const float* scale
     s.eps = eps;
     s.wd = weight_decay;
     if (scale)
-        hipLaunchKernelGGL(cnc::k_table_adam<true>, dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, s, ps);
+        hipLaunchKernelGGL((cnc::k_table_adam<true, false>), dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, s, ps);
     else
-        hipLaunchKernelGGL(cnc::k_table_adam<false>, dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, s, ps);
+        hipLaunchKernelGGL((cnc::k_table_adam<false, false>), dim3((uint32_t)blocks), dim3(cnc::kAdamThreads), 0, (hipStream_t)stream, a, s, ps);
     return cnc::launch_status();
 }
 
@@ -177,4 +204,11 @@ extern "C" int cnc_table_adam_scaled(const cnc_adam_tables_t* tables, const floa
                                      double beta2, double eps, double weight_decay, double step, void* stream)
 {
     return table_adam_launch(tables, piece_scale, lr, beta1, beta2, eps, weight_decay, step, stream);
+}
+
+extern "C" int cnc_table_adam_guarded(const cnc_adam_tables_t* tables, const float* piece_scale, const cnc_step_verdict_t* verdict,
+                                      void* stream)
+{
+    if (!verdict) return CNC_ERR_INVALID_VALUE;
+    return table_adam_launch(tables, piece_scale, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, stream, verdict);
 }

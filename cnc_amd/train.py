@@ -53,6 +53,9 @@ def build_parser():
     ap.add_argument("--reproducible", action="store_true",
                     help="the reproducible mode: ordered reductions, one host thread, one stream (DESIGN.md §5); two runs "
                          "from one seed give the same bits on one GPU")
+    ap.add_argument("--guarded-step", dest="guarded_step", action="store_true",
+                    help="the guarded step: an optimizer update whose gradients or loss are non-finite, or whose forward "
+                         "tripped the fp16 range guard, is skipped, decided on the device (DESIGN.md §13)")
     return ap
 
 
@@ -67,6 +70,7 @@ def make_config_and_data(args, device, rank=0, world=1):
               sample_num=args.sample_num, max_context_layer_num=args.max_context_layer_num,
               n_features=args.n_features, max_steps=args.max_steps, image_size=args.image_size, seed=args.seed,
               out_dir=args.out_dir or f"./bitstreams/{scene}", reproducible=bool(getattr(args, "reproducible", False)),
+              guarded_step=bool(getattr(args, "guarded_step", False)),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _gradsink, _repro, _table_adam
+from . import _gradsink, _repro, _step_guard, _table_adam
 from . import dist as cdist
 from .context import CNC_context_models
 from .field import NGPRadianceField_mygrid_2D3D
@@ -77,6 +77,10 @@ class TrainConfig:
     # the reproducible mode (cnc_amd._repro): every step of this Trainer under `cnc_amd.reproducible(True)`, on
     # the one-thread, one-stream schedule and without the planes' graph
     reproducible: bool = False
+    # the guarded step (cnc_amd._step_guard): a step whose small gradients or loss scalars hold a non-finite
+    # value, or whose forward tripped the fp16 range guard, updates nothing — decided on the device, no host wait.
+    # Also CNC_GUARDED_STEP=1
+    guarded_step: bool = False
 
 
 class SyntheticBallDataset:
@@ -336,7 +340,8 @@ class Trainer:
             plist = list(self.field.parameters()) + list(self.context.parameters())
             # ray-loss gradients (all-reduced) + ONE tail slot: this rank's sample count, so that the sum over the
             # ranks arrives with the gradients instead of through a blocking collective in the middle of the step
-            self.bucket = cdist.GradBucket(plist, tail=1)
+            # (the guarded step: one more, the range guard's trip of any rank as +inf in the sum — `_step_guard`)
+            self.bucket = cdist.GradBucket(plist, tail=2 if self.step_guard is not None else 1)
             self.bucket_ctx = cdist.GradBucket(plist)      # entropy-loss gradients (replica-identical)
             self._count_host = torch.zeros(1, dtype=torch.float32)
             if self.device.type == "cuda":
@@ -391,6 +396,7 @@ class Trainer:
         # the four tables as a parameter group of their own (same hyper-parameters, same schedule): what `_table_adam` steps
         tables = [e.params for e in self.field.mlp_base._encoders()]
         tids = {id(p) for p in tables}
+        self._tables, self._table_ids = tables, tids
         rest = [p for p in self.field.parameters() if id(p) not in tids]
         self.opt = torch.optim.Adam([{"params": rest}, {"params": tables}], lr=c.lr, eps=1e-15, weight_decay=c.weight_decay,
                                     fused=one_pass)
@@ -403,12 +409,25 @@ class Trainer:
             self.table_adam = _table_adam.TableAdam(self.opt, tables, self.field.mlp_base._encoders())
         self.fused_table_adam = self.table_adam is not None
         self._check_table_adam()
+        # the guarded step: the verdict's buffer, seeded with the step count of the optimizer as it stands
+        self.step_guard = None
+        if bool(getattr(c, "guarded_step", False)) or os.environ.get("CNC_GUARDED_STEP", "0") == "1":
+            if not one_pass:
+                raise RuntimeError("the guarded step needs the fused Adam (a GPU, CNC_FUSED_ADAM=1): the library's other "
+                                   "forms take no device-side `found_inf`")
+            b1, b2 = self.opt.param_groups[1]["betas"]
+            self.step_guard = _step_guard.StepGuard(self.device, b1, b2, self._table_steps_taken())
 
         def sched(o):
             return torch.optim.lr_scheduler.ChainedScheduler([
                 torch.optim.lr_scheduler.LinearLR(o, start_factor=0.01, total_iters=c.warmup_iters),
                 torch.optim.lr_scheduler.MultiStepLR(o, milestones=list(c.milestones), gamma=0.33)])
         self.sched, self.sched2 = sched(self.opt), sched(self.opt2)
+
+    def _table_steps_taken(self) -> int:
+        """The tables' step count as the optimizer's state has it (a synchronisation: construction and state loads only)."""
+        st = self.opt.state.get(self.opt.param_groups[1]["params"][0], {})
+        return int(float(st["step"])) if len(st) else 0
 
     def _check_table_adam(self) -> None:
         """Once, not in the middle of a step: what cnc_table_adam would refuse of the pieces this Trainer's schedules can
@@ -448,6 +467,8 @@ class Trainer:
             self.opt2.load_state_dict(opt2_state)
         if self.table_adam is not None:
             self.table_adam.resync()
+        if self.step_guard is not None:
+            self.step_guard.seed(self._table_steps_taken())        # the running products b^t restart from the loaded count
 
     # -------------------------------------------------------------------------------- training
     def _context_pass_worker(self, step, fork, params, grad_mode, autocast):
@@ -730,7 +751,7 @@ class Trainer:
             if c.target_sample_batch_size > 0 and mean >= 1.0:
                 self.dataset.update_num_rays(int(rays_then * (c.target_sample_batch_size / mean)))
         self._count_pending = None
-        self.bucket.tail.fill_(float(n_samples))    # enqueued before the backward; the bucket is zeroed before this
+        self.bucket.tail[:1].fill_(float(n_samples))    # enqueued before the backward; the bucket is zeroed before this
 
     def _train_step_tail(self, step, want_stats, data, ctx_future):
         c = self.cfg
@@ -741,6 +762,11 @@ class Trainer:
                 render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True)
         self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event() if self.device.type == "cuda" else None
         if self.device.type == "cuda":
+            # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
+            # fused one is asked before the poll below can switch it off)
+            ff = self.field._field_fused
+            guard_live = self.step_guard is not None and bool(ff) and self.field.fused_train \
+                and ff._buffers is not None and getattr(ff, "_train_calls", False)
             # the fused training forward's fp16 range guard, every step and without a wait: the words of the step before have
             # arrived by now (the sampler has synchronised the host since), this step's are sent on their way
             self.field.poll_range_guard()
@@ -770,6 +796,8 @@ class Trainer:
             return bits_per_param, mb_, grads
 
         table_pieces = None
+        sg = self.step_guard
+        range_guard = (ff._buffers["guard"], self.field._guard_seen, ff._pack_id) if sg is not None and guard_live else None
         if self.bucket is None:
             if ctx_future is not None:
                 (mse * self.loss_scale).backward()
@@ -823,6 +851,9 @@ class Trainer:
                 (mse * self.loss_scale).backward()     # collective below must still be entered by everyone
             if self.sink_render is not None:
                 self.sink_render.flush()               # `.grad` = the bucket's views: the encoder scatters join it here
+            if sg is not None:
+                # this rank's range-guard trip as +inf (else 0) in the second tail slot: every rank reads it in the sum
+                sg.scan((), range_guard=range_guard, poison=A.tail[1:2])
             work = A.allreduce(average=False, async_op=True)
             ctx_grads = None
             if ctx_future is not None:
@@ -843,7 +874,7 @@ class Trainer:
                     e1.record()
                     self._comm_events.append((e0, e1))
             # the summed sample count goes to the host behind the collective; nobody waits for it before the next step
-            self._count_host.copy_(A.tail, non_blocking=True)
+            self._count_host.copy_(A.tail[:1], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             self._count_pending = (ev, len(pixels))
@@ -885,12 +916,29 @@ class Trainer:
                 elif c.lmbda > 0:
                     A.grads.add_(B.flat)
             A.bind(force=True)
+        if sg is not None:
+            # The step's verdict, on the device and before any update: every gradient the two library optimizers will read
+            # (the tables' pieces are not scanned: DESIGN.md §13) and the loss scalars; data parallel: what every rank holds
+            # alike — the bucket's summed non-table runs with the entropy gradient added, and the all-reduced guard slot.
+            if self.bucket is None:
+                scan = [p.grad for o in (self.opt, self.opt2) for g in o.param_groups for p in g["params"]
+                        if p.grad is not None and id(p) not in self._table_ids]
+                scan += [t.detach().reshape(-1) for t in (mse, bpp) if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
+                sg.scan(scan, range_guard=range_guard)
+            else:
+                A = self.bucket
+                sg.scan([A.flat[lo:hi] for lo, hi in A.runs_excluding(self._tables)] + [A.tail[1:2]])
+            grp = self.opt.param_groups[1]
+            sg.seal(grp["lr"], grp["eps"], grp["weight_decay"],
+                    self.table_adam.clip_counters() if (self.table_adam is not None and table_pieces is not None) else ())
+            self.opt.found_inf = self.opt2.found_inf = sg.found_inf
+            sg.poll()
         if self.table_adam is not None:
             if table_pieces is not None:
                 # leaves the tables' `.grad` None: the library's step skips them.  Data parallel: `.grad` is the bucket's view
                 # with the sum over the ranks (bound just above), the first piece; 1 / world as a float32
                 scale = 1.0 if self.bucket is None else self._inv_world
-                self.table_adam.step(table_pieces, grad_scale=scale)
+                self.table_adam.step(table_pieces, grad_scale=scale, guard=sg)
             else:
                 self.table_adam.steps_done += 1            # the library steps them below
         self.opt.step()
@@ -930,7 +978,8 @@ class Trainer:
             if log and s is not None and step % self.cfg.log_every == 0 and self.rank == 0:
                 log(f"elapsed_time={time.time() - tic:.2f}s | step={step} | psnr={s['psnr']:.2f} | "
                     f"n_rendering_samples={s['n_rendering_samples']} | num_rays={s['num_rays']} | "
-                    f"bits_per_param={s['bpp']:.3f} | embed_bits_MB={s['embed_bits_MB']:.3f}")
+                    f"bits_per_param={s['bpp']:.3f} | embed_bits_MB={s['embed_bits_MB']:.3f}"
+                    + (f" | skipped={self.step_guard.stats()['skipped']}" if self.step_guard is not None else ""))
         return last
 
     # ------------------------------------------------------------------------------ evaluation

@@ -801,6 +801,66 @@ int cnc_table_adam(const cnc_adam_tables_t* tables, double lr, double beta1, dou
 int cnc_table_adam_scaled(const cnc_adam_tables_t* tables, const float* piece_scale, double lr, double beta1, double beta2,
                           double eps, double weight_decay, double step, void* stream);
 
+/* (ABI v33, added entries: no signature changed) The guarded training step: the step's verdict — go, or skip — reached on the
+ * device before the optimizer's update, and an Adam launch that honours it.  No call below waits for the device.
+ *
+ * cnc_step_verdict_t: device memory owned by the caller (8-byte aligned, zero-filled once, b1_pow / b2_pow then seeded with
+ * beta^t0 for an optimizer that has taken t0 updates).  cnc_step_verdict_scan ORs reasons into `acc`; cnc_step_verdict_seal,
+ * after the step's last scan, moves them to `skip`, clears `acc`, and on go (skip == 0) advances the running products by ONE
+ * IEEE double multiplication each and writes the scalar factors of the update that follows; on skip it touches neither and
+ * counts.  The products replace pow(beta, t): reproducible bit for bit by a NumPy twin, within t 2^-52 relative of beta^t. */
+#define CNC_VERDICT_NONFINITE   1u    /* a scanned float32 had all exponent bits set: +-inf or any NaN                */
+#define CNC_VERDICT_RANGE_GUARD 2u    /* the fp16 range guard's predicate held (cnc_fused_field_t.guard, below)       */
+#define CNC_VERDICT_MAX_TENSORS 48u
+typedef struct {
+    uint32_t acc;              /* reasons of the step under way (scan: atomicOr; seal: cleared)                       */
+    uint32_t skip;             /* the sealed step's reasons; 0 = go.  What cnc_table_adam_guarded reads               */
+    uint32_t skipped;          /* number of sealed steps with skip != 0                                               */
+    uint32_t reasons_seen;     /* OR of every skipped step's reasons                                                  */
+    double   b1_pow, b2_pow;   /* beta1^t, beta2^t after t updates that went ahead                                    */
+    /* the factors of the update sealed last on go, as cnc_table_adam's launcher computes them from pow:             */
+    double   lr_over_bc1;      /* lr / (1 - b1_pow)                                                                   */
+    double   one_minus_b1, b2, one_minus_b2;
+    double   bc2_sqrt;         /* sqrt(1 - b2_pow)                                                                    */
+    double   eps, wd;
+} cnc_step_verdict_t;
+
+/* cnc_step_verdict_scan: CNC_VERDICT_NONFINITE when any element of up to 48 float32 tensors has (bits & 0x7f800000) ==
+ * 0x7f800000 (the largest finite values and denormals do not count); pointers 4-byte aligned — a view at any element offset —
+ * NULL or n == 0: skipped; more tensors: several calls, which accumulate.  guard (nullable): the field's guard words;
+ * CNC_VERDICT_RANGE_GUARD when guard[0] != 0 && guard[0] >= guard_seen, or any of guard[1..5] == pack_id — the host's
+ * check_range_guard.  poison (nullable): receives +inf when that predicate held, else 0.0f — a slot of an all-reduced buffer
+ * that carries one rank's trip to every rank.  A scan that finds nothing writes nothing to the verdict.              */
+typedef struct {
+    const float*        ptr[48];
+    uint64_t            n[48];
+    uint32_t            n_tensors;
+    uint32_t            guard_seen, pack_id;
+    const uint32_t*     guard;
+    float*              poison;
+    cnc_step_verdict_t* verdict;
+} cnc_verdict_scan_t;
+int cnc_step_verdict_scan(const cnc_verdict_scan_t* scan, void* stream);
+
+/* cnc_step_verdict_seal: found_inf (nullable, device float32) = 1.0f on skip, 0.0f on go — torch's fused Adam takes it as its
+ * `found_inf` and un-counts a skipped step itself.  lr, beta1, beta2 (in [0, 1)), eps, weight_decay: the tables' parameter
+ * group as it stands at this step.  clip_count: the up to four counters cnc_table_adam_guarded adds to, zeroed on go only. */
+typedef struct {
+    cnc_step_verdict_t* verdict;
+    float*              found_inf;
+    double              lr, beta1, beta2, eps, weight_decay;
+    uint32_t*           clip_count[4];
+} cnc_verdict_seal_t;
+int cnc_step_verdict_seal(const cnc_verdict_seal_t* seal, void* stream);
+
+/* cnc_table_adam_guarded: cnc_table_adam (piece_scale == NULL) or cnc_table_adam_scaled with `skip` and the scalar factors read
+ * from the sealed verdict instead of computed from a host-side step count.  skip != 0: every block returns before its first
+ * load of a table — p, m, v, table.step, the sign planes and the clip counters keep every bit.  skip == 0: the same
+ * arithmetic, piece order and products; m and v equal cnc_table_adam's at the same step, p to within the rounding that
+ * b^t-by-products against pow can move (one fp32 ulp).  The caller does not zero the clip counters: the seal did.       */
+int cnc_table_adam_guarded(const cnc_adam_tables_t* tables, const float* piece_scale, const cnc_step_verdict_t* verdict,
+                           void* stream);
+
 /* (ABI v30) The front-to-back sampler's depth windows without a host round trip per window (nerfacc/estimators/occ_grid.py
  * `_density_front_to_back`; the reference evaluates sigma_fn on ALL marched samples at once, occ_grid.py:172-238).
  * cnc_ray_window_positions: samples [win_lo[r], win_lo[r] + win_n[r]) of ray r -> positions[o + k] = o_r + (d_r (t0 + t1)) / 2
