@@ -269,8 +269,9 @@ struct CornerPair3 {
     bool     valid0, valid1;
     float    wn_re;
 
-    template <bool HP2>
-    __device__ __forceinline__ void setup(const float (&x)[3], const LevelGeom3& lv, uint32_t p)
+    // 1 / (sum of the valid weights of all eight corners): a property of the sample, not of the pair.  The bin pass
+    // computes it once per sample in its count phase and keeps it in LDS for the walk (k_bwd_bin_sorted).
+    static __device__ __forceinline__ float normaliser(const float (&x)[3], const LevelGeom3& lv)
     {
         float          fx, fy, fz;
         const uint32_t gx = lv.cell(x[0], fx), gy = lv.cell(x[1], fy), gz = lv.cell(x[2], fz);
@@ -290,8 +291,20 @@ struct CornerPair3 {
             wn += ok ? wi : 0.0f;
         }
         if (wn == 0) wn = 1e-9f;
-        wn_re = 1.0f / wn;
-        // the pair's own two weights again, from the selected y and z factors: the same products, the same bits
+        return 1.0f / wn;
+    }
+
+    // the pair alone, the normaliser handed in: two weights from the selected y and z factors (the same products, the
+    // same bits as the eight of the sum), rows and validity of the pair
+    template <bool HP2>
+    __device__ __forceinline__ void setup_pair(const float (&x)[3], const LevelGeom3& lv, uint32_t p, float wn_re_)
+    {
+        float          fx, fy, fz;
+        const uint32_t gx = lv.cell(x[0], fx), gy = lv.cell(x[1], fy), gz = lv.cell(x[2], fz);
+        const uint32_t x1 = min(gx + 1, lv.R - 1), y1 = min(gy + 1, lv.R - 1), z1 = min(gz + 1, lv.R - 1);
+        const float    ex = 1 - fx, ey = 1 - fy, ez = 1 - fz;
+        const bool     bx0 = lv.border(gx), bx1 = lv.border(x1);
+        wn_re = wn_re_;
         const bool  by = p & 1u, bz = p & 2u;
         const float ty = by ? fy : ey, tz = bz ? fz : ez;
         w0 = (ex * ty) * tz;
@@ -303,6 +316,12 @@ struct CornerPair3 {
         valid1 = !(bx1 || byz);
         row0 = valid0 ? lv.fold<HP2>(gx, py, pz) : 0u;
         row1 = valid1 ? lv.fold<HP2>(x1, py, pz) : 0u;
+    }
+
+    template <bool HP2>
+    __device__ __forceinline__ void setup(const float (&x)[3], const LevelGeom3& lv, uint32_t p)
+    {
+        setup_pair<HP2>(x, lv, p, normaliser(x, lv));
     }
 };
 

@@ -202,7 +202,9 @@ __global__ __launch_bounds__(1024) void k_bwd_bin(BinnedArgs a)
 // The set-up runs once per sample to count and once per item in the walk, about 5.4 times per (sample, level), and the
 // pass shares the SIMDs with the vector-issue-bound merge kernel of the coarse levels on the other stream: the count
 // phase takes rows and validity only (corner_rows3) and the walk one corner pair (CornerPair3), not the general
-// Corners::setup; the cold paths keep that one.
+// Corners::setup; the cold paths keep that one.  The weights' sum and its division are per sample, not per item: the
+// count phase, which visits every sample once, computes 1 / sum as Corners::setup does and leaves it in LDS (s_wn, one
+// float per sample of the block: 16 KB), and the walk's lane reads it for its item's sample.
 constexpr uint32_t kSortBins = 2048;                                  // three LDS arrays of that many words
 #ifndef CNC_SORT_SAMPLES_PER_THREAD
 #define CNC_SORT_SAMPLES_PER_THREAD 4
@@ -264,6 +266,7 @@ __global__ __launch_bounds__(1024) void k_bwd_bin_sorted(BinnedArgs a)
     __shared__ uint16_t s_src[kSortItems];        // source ids in bin order: sample-in-block | pair << 13 | half << 15
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_total;
+    __shared__ float    s_wn[1024 * kSortSamplesPerThread];   // 1 / (sum of the valid weights) per sample: count phase -> walk
     const uint32_t slot = a.first_level + blockIdx.y;
     const uint32_t off = (uint32_t)a.offsets[slot];
     const uint32_t hs = (uint32_t)a.offsets[slot + 1] - off;
@@ -333,6 +336,7 @@ __global__ __launch_bounds__(1024) void k_bwd_bin_sorted(BinnedArgs a)
             const uint32_t i = base_i + k * 1024 + tid;
             float x[3];
             if (i < a.N && load_point<3>(a.inputs, i, x)) {
+                s_wn[k * 1024 + tid] = CornerPair3::normaliser(x, lv);     // (an outside point's slot: never written, never read)
                 corner_rows3<decltype(hp2)::value>(x, lv, [&](uint32_t p, bool v0, bool v1, uint32_t r0, uint32_t r1) {
                     const uint32_t b0 = r0 >> kSlabLog2, b1 = r1 >> kSlabLog2;
                     if (v0) key[k][2 * p] = b0 | atomicAdd(&s_start[b0], 1u) << 11;
@@ -405,7 +409,7 @@ __global__ __launch_bounds__(1024) void k_bwd_bin_sorted(BinnedArgs a)
             float x[3];
             load_point<3>(a.inputs, i, x);
             CornerPair3 c;
-            c.setup<decltype(hp2)::value>(x, lv, (src >> 13) & 3u);
+            c.setup_pair<decltype(hp2)::value>(x, lv, (src >> 13) & 3u, s_wn[src & 0x1FFFu]);
             uint32_t bin, mask;
             const Item it = pair_item(c, i, (src >> 15) & 1u, bin, mask);
             const uint32_t at = s_base[bin] + (pos - s_start[bin]);

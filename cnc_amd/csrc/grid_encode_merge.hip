@@ -20,6 +20,12 @@
 //   * per-cell accumulation as an 8 x n by n x 8 product on v_mfma_f32_16x16x4_f32: 0.403;
 //   * one packed LDS word per run and one 16-byte record per cell: 0.384;
 //   * the cost now being per distinct cell, 1024 samples (75 KB of LDS, 2 blocks per CU): 0.365.
+//   * the call's kernels compete for vector issue slots (profiles/r14_bin_pass_setup.md), and all lanes of a wave walk the
+//     same chain: run records through readfirstlane (fields, lone-run split, step count and loop tests in scalar
+//     registers: 31 -> 13 vector instructions per run pair outside the step loop), the per-wave prefixes as one 16-lane
+//     DPP scan (two 16-term loops before), the valid-corner mask from six per-axis flags: 154.0 M -> 122.1 M vector
+//     wave-instructions per call of the bench, 41 -> 32 vector registers, the bench frame +2.0 %
+//     (profiles/r17_backward_issue_slots.md).
 //
 // D = 3, F = 8 (one cell per wave at a time: 64 lanes = 8 corners x 8 features), no occupancy mask, no
 // per-point level window: the coarse half of a binned backward call.  Everything else stays on
@@ -169,7 +175,7 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     constexpr uint32_t kMB = MB;
     constexpr uint32_t kMW = kMB / 64;        // waves per block
     constexpr uint32_t kMSlots = kMB <= 512 ? 1024 : 2048;   // hash slots, power of two, >= 2 x the most runs a block can have
-    constexpr uint32_t D = 3, F = 8, C = 8, END = 0x7FFu;
+    constexpr uint32_t D = 3, F = 8, END = 0x7FFu;
     static_assert(kMB <= 1024, "run records pack start (10 bits) / end (11) / next (11)");
     // the three fractional positions and 1 / (sum of valid weights): the lane rebuilds its corner's
     // weight from them (same products, same order as Corners::setup) — half the LDS of 8 stored weights
@@ -186,8 +192,24 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     __shared__ uint32_t s_run_rec[kMB];         // start | end << 10 | next run of the cell << 21: one read per run
     __shared__ uint32_t s_wave_heads[kMW], s_wave_claims[kMW];
 
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // (the wave index through readfirstlane: the compiler cannot see that tid >> 6 is wave-uniform, and everything that
+    // hangs on it — the prefix reads below, the cell loop of phase B — is scalar work once it can)
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool     mask_on = STE && (clip_count == nullptr || *clip_count != 0);
+    // Exclusive prefix and total of one count per wave (s_wave_heads, s_wave_claims): lane l reads the word of wave
+    // l % kMW, an inclusive scan inside the 16-lane row (four DPP row shifts that shift zeros in) and two readlanes at
+    // wave-uniform lanes.  The counts of the waves in wave order, i.e. in sample order: runs and cells keep their numbers.
+    auto wave_prefix = [&](const uint32_t* counts, uint32_t& before, uint32_t& total) {
+        static_assert(kMW == 8 || kMW == 16, "the counts of a block fit one DPP row");
+        const uint32_t h = counts[lane & (kMW - 1)];
+        uint32_t       x = h;
+        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);      // row_shr:1
+        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);      // row_shr:2
+        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);      // row_shr:4
+        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);      // row_shr:8
+        before = (uint32_t)__builtin_amdgcn_readlane((int)(x - h), (int)wave);
+        total = (uint32_t)__builtin_amdgcn_readlane((int)x, (int)(kMW - 1));
+    };
     // 1-D grid, level slot as the fast index (see k_grid_encode_bwd), slots walked last to first
     const uint32_t n_slots = lay.n_slots;
     const uint32_t chunk = blockIdx.x / n_slots;
@@ -219,8 +241,15 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
             c.setup(x, R, hs, 0, nullptr);
             key = (uint64_t)c.cell[0] | (uint64_t)c.cell[1] << 16 | (uint64_t)c.cell[2] << 32;
             if (R > kCellKeyMaxRes) key = ~0ull;               // cells the key cannot hold: k_grid_encode_bwd_wide
-#pragma unroll
-            for (uint32_t i = 0; i < C; i++) validmask |= (c.valid[i] ? 1u : 0u) << i;
+            // valid corners from the six per-axis border flags (a corner is valid iff none of its three coordinates
+            // is 0 or R - 1: c.valid[i], without a select / shift / or per corner)
+            {
+                const uint32_t x1 = min(c.cell[0] + 1, R - 1), y1 = min(c.cell[1] + 1, R - 1), z1 = min(c.cell[2] + 1, R - 1);
+                auto           border = [&](uint32_t q) { return (q == 0) | (q == R - 1); };
+                const uint32_t inv = (border(c.cell[0]) ? 0x55u : 0u) | (border(x1) ? 0xAAu : 0u) | (border(c.cell[1]) ? 0x33u : 0u)
+                    | (border(y1) ? 0xCCu : 0u) | (border(c.cell[2]) ? 0x0Fu : 0u) | (border(z1) ? 0xF0u : 0u);
+                validmask = inv ^ 0xFFu;
+            }
             *reinterpret_cast<float4*>(s_w4[tid]) = make_float4(c.frac[0], c.frac[1], c.frac[2], c.wn_re);
             const float* gp = grad + feat_index(lay, slot, N, b, F);
             float        g0[4], g1[4];
@@ -241,13 +270,8 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     const uint64_t hb = __ballot(head);
     if (lane == 0) s_wave_heads[wave] = (uint32_t)__popcll(hb);
     __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kMW; w++) {
-        const uint32_t h = s_wave_heads[w];
-        before += w < wave ? h : 0u;
-        total += h;
-    }
+    uint32_t before, total;
+    wave_prefix(s_wave_heads, before, total);
     const uint32_t my_run = before + (uint32_t)__popcll(hb & ((1ull << lane) - 1ull));
     if (head) s_run_start[my_run] = (uint16_t)tid;
     if (tid == 0) s_run_start[total] = (uint16_t)kMB;
@@ -271,13 +295,8 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     const uint64_t cb = __ballot(claimer);
     if (lane == 0) s_wave_claims[wave] = (uint32_t)__popcll(cb);
     __syncthreads();
-    uint32_t g_before = 0, n_cells = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kMW; w++) {
-        const uint32_t h = s_wave_claims[w];
-        g_before += w < wave ? h : 0u;
-        n_cells += h;
-    }
+    uint32_t g_before, n_cells;
+    wave_prefix(s_wave_claims, g_before, n_cells);
     // (the sync above also ends the life of the keys and the hash table: s_u is rewritten here)
     uint4 my_cell = make_uint4(0, 0, 0, 0);
     if (claimer) my_cell = make_uint4(s_run_rec[l_head[my_run]], (uint32_t)key, (uint32_t)(key >> 32), validmask);
@@ -331,7 +350,10 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     // whole backward call next to the bin / owner passes.
     for (uint32_t g = wave; g < n_cells; g += kMW) {
         const uint4 cell = s_u[g];                         // {first run of the chain, key, valid corners}
-        uint32_t    rec = cell.x;
+        // The chain is the wave's, not the lane's: the records go through readfirstlane, so their fields, the lone-run
+        // split, the step count and both loop conditions live in scalar registers behind scalar branches.  Per lane
+        // stays what depends on the lane: which run of the pair it feeds, its sample slot, the two LDS reads, the weight.
+        uint32_t    rec = __builtin_amdgcn_readfirstlane(cell.x);
         const uint32_t k_lo = __builtin_amdgcn_readfirstlane(cell.y);
         const uint32_t k_hi = __builtin_amdgcn_readfirstlane(cell.z);
         // S[corner][feature] = sum over the chain's samples of w[corner] * g[feature]: a K = n product of
@@ -346,7 +368,7 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
         for (;;) {
             uint32_t a0 = rec & 0x3FFu, a1 = (rec >> 10) & 0x7FFu, b0, b1, nxt = rec >> 21;
             if (nxt != END) {
-                const uint32_t rb = s_run_rec[nxt];
+                const uint32_t rb = __builtin_amdgcn_readfirstlane(s_run_rec[nxt]);
                 b0 = rb & 0x3FFu, b1 = (rb >> 10) & 0x7FFu, nxt = rb >> 21;
             } else {
                 b1 = a1;
@@ -354,6 +376,9 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
             }
             const uint32_t steps = max(a1 - a0, b1 - b0);
             const uint32_t m0 = half_b ? b0 : a0, m1 = half_b ? b1 : a1;
+            // the next pair's first record, asked for before the step loop and taken after it (END & (kMB - 1) is a slot
+            // of the array like any other: read and not used)
+            const uint32_t ahead = s_run_rec[nxt & (kMB - 1)];
             for (uint32_t p = 0; p < steps; p += 4) {
                 const uint32_t ps = m0 + p + mk;
                 float          a = 0.0f, bv = 0.0f;
@@ -368,7 +393,7 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
                 S = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, S, 0, 0, 0);
             }
             if (nxt == END) break;
-            rec = s_run_rec[nxt];
+            rec = __builtin_amdgcn_readfirstlane(ahead);
         }
         // tile element (row, col) sits in lane col + 16 * (row / 4), register row % 4; block B is 8 rows
         // and 8 columns further on = 40 lanes
