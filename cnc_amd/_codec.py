@@ -12,6 +12,11 @@ SIGNATURES = {
     "cnc_rc_decode_pm1": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "cnc_rc_encode_cdf16": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64]),
     "cnc_rc_decode_cdf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    # the "rans1" format: host twin of the device coder
+    "cnc_rans_bound": (C.c_int64, [C.c_int64, C.c_int64]),
+    "cnc_rans_encode_pm1_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "cnc_rans_decode_pm1_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cnc_rans_check": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int64]),
 }
 
 

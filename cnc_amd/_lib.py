@@ -107,6 +107,12 @@ class FieldPack(C.Structure):
     _fields_ = [("layer", FieldPackLayer * 5), ("row0", _vp), ("row0_len", _u32), ("guard", _vp), ("pack_id", _u32)]
 
 
+class RansStream(C.Structure):
+    """cnc_rans_stream_t (include/cnc_hip.h)."""
+    _fields_ = [("p", _vp), ("p_stride", _i64), ("x", _vp), ("n", _i64), ("symbols_per_lane", _i64), ("bytes", _vp),
+                ("cap_or_len", _i64)]
+
+
 # name -> argtypes, in the order of include/cnc_hip.h
 SIGNATURES = {
     "cnc_grid_encode_forward": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _f32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp],
@@ -213,6 +219,9 @@ SIGNATURES = {
     "cnc_bernoulli_bits_backward": [_vp, _vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp],
     "cnc_segment_weighted_sum_backward": [_vp, _vp, _vp, _vp, _u32, C.c_uint64, _u32, _i32, _vp, _vp],
     "cnc_segment_weighted_sum_gathered_backward": [_vp, _vp, _vp, _vp, _vp, _u32, C.c_uint64, _u32, _i32, _vp, _vp],
+    "cnc_rans_scratch_bytes": [C.POINTER(RansStream), _u32],
+    "cnc_rans_encode_pm1": [C.POINTER(RansStream), _u32, _vp, C.c_uint64, _vp, _vp],
+    "cnc_rans_decode_pm1": [C.POINTER(RansStream), _u32, _vp, _vp],
 }
 
 # entry points that return something other than a status code
@@ -220,7 +229,8 @@ RESTYPES = {"cnc_grid_encode_backward_binned_workspace": C.c_uint64,
             "cnc_grid_encode_backward_overlapped_workspace": C.c_uint64,
             "cnc_grid_encode_backward_ordered_workspace": C.c_uint64, "cnc_bernoulli_bits_partials": C.c_uint32,
             "cnc_ctx_mlp_backward_ordered_workspace": C.c_uint64, "cnc_field_backward_chain_ordered_workspace": C.c_uint64,
-            "cnc_relu_backward_bias_partials": C.c_uint32, "cnc_occupancy_coarse_words": C.c_uint32}
+            "cnc_relu_backward_bias_partials": C.c_uint32, "cnc_occupancy_coarse_words": C.c_uint32,
+            "cnc_rans_scratch_bytes": C.c_uint64}
 
 CNC_FLAG_STE_BINARY = 1
 CNC_FLAG_LEVELS_FINEST_FIRST = 2

@@ -71,10 +71,12 @@ def build_codec(force=False, verbose=False):
     src = os.path.join(CSRC, "range_coder.cpp")
     if not os.path.exists(src):
         return None
-    if not (force or _newer([src, os.path.join(INCLUDE, "cnc_codec.h")], LIB_CODEC)):
+    srcs = [src, os.path.join(CSRC, "rans_coder.cpp")]       # the range coder and the host twin of the device coder
+    deps = srcs + [os.path.join(CSRC, "rans_format.hpp"), os.path.join(INCLUDE, "cnc_codec.h"), os.path.abspath(__file__)]
+    if not (force or _newer(deps, LIB_CODEC)):
         return LIB_CODEC
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", INCLUDE,
-           "-o", LIB_CODEC, src]
+           "-o", LIB_CODEC] + srcs
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)

@@ -341,6 +341,125 @@ class CoderPool:
         self.pool.shutdown(wait=True)
 
 
+# Symbols per rANS lane of the device coder when the caller names none: the smallest of 2^12, 2^14, 2^16 whose
+# full-size container stays within 1 % of the host coder's (profiles/device_coder.md).
+DEVICE_CODER_SYMBOLS_PER_LANE = 16384
+
+
+def _flat_p(p):
+    """(float32 device tensor, p_stride, n) of a probability tensor: an expanded scalar (the levels coded with one
+    Pg) stays one element, read with stride 0."""
+    n = p.numel()
+    if p.dim() == 1 and n > 1 and p.stride(0) == 0:
+        return p.detach()[:1].to(torch.float32).contiguous(), 0, n
+    return p.detach().to(torch.float32).contiguous().view(-1), 1, n
+
+
+class DeviceCoder:
+    """The call shape of `CoderPool` on the device entropy coder (cnc_amd/csrc/rans_coder.hip, the "rans1" format of
+    include/cnc_codec.h): symbols and probabilities stay where they are, one batched call codes every stream handed
+    over, and only compressed bytes cross PCIe.  `encode` collects; `finish` launches, copies sizes and bytes to the
+    host, writes the .b files and returns the bits.  `decode_group` checks the files on the host (`cnc_rans_check`),
+    uploads their bytes in one copy and returns the decoded DEVICE tensors without waiting; the streams' status words
+    are read by `check()`, once, when the caller is done."""
+
+    def __init__(self, symbols_per_lane=None):
+        self.S = int(symbols_per_lane or DEVICE_CODER_SYMBOLS_PER_LANE)
+        if self.S < 1:
+            raise ValueError("symbols_per_lane must be >= 1")
+        self._queued = []            # (x, p, p_stride, n, file name)
+        self._status = []            # (status tensor, file names) of the decode groups so far
+
+    # ---- encode
+    def encode(self, x, p, file_name):
+        assert file_name[-2:] == ".b"
+        if not x.is_cuda:
+            raise RuntimeError("x must be a CUDA tensor")
+        x = x.detach().to(torch.float32).contiguous().view(-1)
+        p, stride, n = _flat_p(p)
+        assert n == x.numel() or (stride == 1 and n == 1 == x.numel())
+        self._queued.append((x, p, stride, x.numel(), file_name))
+
+    def finish(self):
+        """Codes everything queued; returns the total size in bits."""
+        from . import _lib
+        if not self._queued:
+            return 0
+        L, Lc = _lib.lib(), _codec_lib()
+        dev = self._queued[0][0].device
+        caps = [int(Lc.cnc_rans_bound(n, self.S)) for _, _, _, n, _ in self._queued]
+        at = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+        out = torch.empty(int(at[-1]), dtype=torch.uint8, device=dev)
+        table = (_lib.RansStream * len(caps))()
+        for k, (x, p, stride, n, _) in enumerate(self._queued):
+            table[k] = _lib.RansStream(p.data_ptr(), stride, x.data_ptr(), n, self.S, out.data_ptr() + int(at[k]), caps[k])
+        need = int(L.cnc_rans_scratch_bytes(table, len(caps)))
+        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        sizes = torch.empty(len(caps), dtype=torch.int64, device=dev)
+        _lib.check(L.cnc_rans_encode_pm1(table, len(caps), scratch.data_ptr(), need, sizes.data_ptr(), _lib.stream(dev)),
+                   "rans_encode_pm1")
+        sizes_h = sizes.cpu().tolist()
+        if min(sizes_h) < 0:
+            raise RuntimeError("device coder: output buffer too small")
+        # the streams packed on the device, then one copy of what was written (a few hundred KB of the worst-case buffer)
+        packed = torch.cat([out[int(at[k]):int(at[k]) + s] for k, s in enumerate(sizes_h)]).cpu().numpy()
+        pos = 0
+        for (_, _, _, _, file_name), s in zip(self._queued, sizes_h):
+            with open(file_name, "wb") as fout:
+                fout.write(packed[pos:pos + s].tobytes())
+            pos += s
+        self._queued = []
+        return 8 * sum(sizes_h)
+
+    # ---- decode
+    def decode_group(self, items):
+        """items: [(p, file name)], streams that do not depend on each other.  Returns their symbols as float32 +-1
+        DEVICE tensors, in order.  A file that is not a well-formed rans1 stream for p's length raises here, on the host,
+        before anything is uploaded or launched."""
+        Lc = _codec_lib()
+        blobs, ps = [], []
+        for p, file_name in items:
+            assert file_name[-2:] == ".b"
+            if not p.is_cuda:
+                raise RuntimeError("p must be a CUDA tensor")
+            with open(file_name, "rb") as fin:
+                blob = np.frombuffer(fin.read(), dtype=np.uint8)
+            p, stride, n = _flat_p(p)
+            if Lc.cnc_rans_check(blob.ctypes.data, blob.shape[0], n) < 0:
+                raise RuntimeError(f"{file_name}: not a valid rans1 stream of {n} symbols")
+            blobs.append(blob)
+            ps.append((p, stride, n))
+        return self._launch_decode(ps, blobs, [f for _, f in items])
+
+    def _launch_decode(self, ps, blobs, names):
+        from . import _lib
+        L = _lib.lib()
+        dev = ps[0][0].device
+        at = np.concatenate([[0], np.cumsum([b.shape[0] for b in blobs])]).astype(np.int64)
+        host = torch.from_numpy(np.concatenate(blobs))
+        data = (host.pin_memory() if dev.type == "cuda" else host).to(dev, non_blocking=True)
+        outs = [torch.empty(n, dtype=torch.float32, device=dev) for _, _, n in ps]
+        status = torch.empty(len(ps), dtype=torch.int32, device=dev)
+        table = (_lib.RansStream * len(ps))()
+        for k, (p, stride, n) in enumerate(ps):
+            table[k] = _lib.RansStream(p.data_ptr(), stride, outs[k].data_ptr(), n, 0, data.data_ptr() + int(at[k]),
+                                       int(blobs[k].shape[0]))
+        _lib.check(L.cnc_rans_decode_pm1(table, len(ps), status.data_ptr(), _lib.stream(dev)), "rans_decode_pm1")
+        self._status.append((status, names))
+        return outs
+
+    def check(self):
+        """One host wait for every group decoded so far: raises if a lane of any stream did not end where it began."""
+        for status, names in self._status:
+            bad = [n for n, s in zip(names, status.cpu().tolist()) if s != 0]
+            if bad:
+                raise RuntimeError(f"device coder: damaged stream(s) {bad}")
+        self._status = []
+
+    def shutdown(self):
+        self._queued = []
+
+
 class align_and_pack(Function):
     """Ragged [T, F] rows grouped by `unique_cnt` -> padded [N, max(cnt), F] (utils_bpp_acc.py:113-139)."""
 
@@ -1298,9 +1417,13 @@ class CNC_context_models(nn.Module):
 
     # ------------------------------------------------------------------------------- encode
     def encode_binary_vxl_mixPg_3D2D(self, Encoding_xyz, Encoding_xy, Encoding_xz, Encoding_yz,
-                                     binary_vxl=None, filename_prefix="b"):
+                                     binary_vxl=None, filename_prefix="b", coder="host", symbols_per_lane=None):
         """Arithmetic-code all four tables into {prefix}_{axis}{n}.b / {prefix}_3D{n}[_{chunk}].b.
-        Returns (Pgs_dict, estimated MB, coded MB) (utils_bpp_acc.py:709-865)."""
+        Returns (Pgs_dict, estimated MB, coded MB) (utils_bpp_acc.py:709-865).  coder="host": the range coder on worker
+        threads (`CoderPool`); coder="device" (an extension): the same streams through `DeviceCoder`, one batched call
+        at the end, in the "rans1" format — the two kinds of file are not interchangeable."""
+        if coder not in ("host", "device"):
+            raise ValueError(f"coder must be 'host' or 'device', not {coder!r}")
         Pgs_dict = {}
         params_q_xy = self.get_STE_params(Encoding_xy)
         params_q_xz = self.get_STE_params(Encoding_xz)
@@ -1308,7 +1431,7 @@ class CNC_context_models(nn.Module):
         params_q_xyz = self.get_STE_params(Encoding_xyz)
         F = self.n_features
         ttl_bit_sum = 0
-        coders = CoderPool()
+        coders = DeviceCoder(symbols_per_lane) if coder == "device" else CoderPool()
         streams = []            # futures: every stream is an independent file, coded while the next is prepared
 
         idx_coords2 = self.get_idx_coords2(binary_vxl) if self.use_dimension_wise else None
@@ -1349,17 +1472,25 @@ class CNC_context_models(nn.Module):
                 ttl_bit_sum = ttl_bit_sum + torch.sum(self.entropy_model(values_q, mean))
                 ps = torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1)
                 streams.append(coders.encode(values_q.reshape(-1), ps, f"{filename_prefix}_3D{n}_{sn}.b"))
-        encode_bits = sum(f.result() for f in streams)
+        encode_bits = coders.finish() if coder == "device" else sum(f.result() for f in streams)
         coders.shutdown()
         return Pgs_dict, ttl_bit_sum.item() / 8.0 / 1024 / 1024, encode_bits / 8.0 / 1024 / 1024
 
     # ------------------------------------------------------------------------------- decode
     def decode_binary_vxl_mixPg_3D2D(self, Encoding_xyz, Encoding_xy, Encoding_xz, Encoding_yz,
                                      params_q_xyz_rec, params_q_xy_rec, params_q_xz_rec,
-                                     params_q_yz_rec, binary_vxl=None, Pgs_dict=None, filename_prefix="b"):
+                                     params_q_yz_rec, binary_vxl=None, Pgs_dict=None, filename_prefix="b",
+                                     coder="host"):
         """Sequential inverse of encode: 3-D levels coarse to fine (each level's context reads the
         already decoded lower levels), then the three planes (which need the decoded finest 3-D
-        level).  Rows never coded keep the caller's initial value (utils_bpp_acc.py:867-999)."""
+        level).  Rows never coded keep the caller's initial value (utils_bpp_acc.py:867-999).  `coder` names what
+        wrote the files: "host" (range coder) or "device" (rans1, decoded on the device)."""
+        if coder not in ("host", "device"):
+            raise ValueError(f"coder must be 'host' or 'device', not {coder!r}")
+        if coder == "device":
+            return self._decode_on_device(Encoding_xyz, Encoding_xy, Encoding_xz, Encoding_yz, params_q_xyz_rec,
+                                          params_q_xy_rec, params_q_xz_rec, params_q_yz_rec, binary_vxl, Pgs_dict,
+                                          filename_prefix)
         F = self.n_features
         coders = CoderPool()
         dev = params_q_xyz_rec.device
@@ -1409,5 +1540,59 @@ class CNC_context_models(nn.Module):
                     pending.append((coders.decode(ps, fname), rec, rows))
                 for fut, rec, dst in pending:
                     rec[dst] = fut.result().to(dev).view(-1, F)
+        coders.shutdown()
+        return params_q_xyz_rec, params_q_xy_rec, params_q_xz_rec, params_q_yz_rec
+
+    def _decode_on_device(self, Encoding_xyz, Encoding_xy, Encoding_xz, Encoding_yz, params_q_xyz_rec, params_q_xy_rec,
+                          params_q_xz_rec, params_q_yz_rec, binary_vxl, Pgs_dict, filename_prefix):
+        """`decode_binary_vxl_mixPg_3D2D` for files of the device coder: the same order of levels, every group of
+        streams that do not depend on each other (the chunks of a 3-D level; level n of the three planes) as one
+        `DeviceCoder.decode_group` call.  The decoded symbols never leave the device and nothing waits on the host
+        between the levels; the streams' status words are read once, at the end."""
+        F = self.n_features
+        coders = DeviceCoder()
+        with torch.no_grad():
+            for n in range(self.n_levels):
+                Pg_n = Pgs_dict["3D" + str(n)]
+                if not self._coded_3D(n):
+                    rows = int(self.offsets_list[n + 1] - self.offsets_list[n])
+                    sout, = coders.decode_group([(Pg_n.reshape(1).expand(rows * F), f"{filename_prefix}_3D{n}.b")])
+                    params_q_xyz_rec[self.offsets_list[n]:self.offsets_list[n + 1]] = sout.view(rows, F)
+                    continue
+                group, where = [], []
+                for sn, v0, v1 in self._chunks_3D(n):
+                    mean, mask_exist, rows = self._level_chunk_3D(Encoding_xyz, n, v0, v1, Pg_n,
+                                                                  binary_vxl, params_q_xyz_rec)
+                    group.append((torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1), f"{filename_prefix}_3D{n}_{sn}.b"))
+                    where.append((rows[mask_exist], mean.shape))
+                for sout, (dst, shape) in zip(coders.decode_group(group), where):
+                    params_q_xyz_rec[dst] = sout.view(*shape)
+
+            idx_coords2 = self.get_idx_coords2(binary_vxl) if self.use_dimension_wise else None
+            finest_3D = params_q_xyz_rec[self.offsets_list[-2]:self.offsets_list[-1]]
+            planes = []
+            for Ec, rec, axis in zip((Encoding_xy, Encoding_xz, Encoding_yz),
+                                     (params_q_xy_rec, params_q_xz_rec, params_q_yz_rec), ("xy", "xz", "yz")):
+                binary_2D = self._project(binary_vxl, axis)
+                pn_frac = self.get_pn_embed_frac(finest_3D, idx_coords2, axis=axis) if self.use_dimension_wise else None
+                planes.append((Ec, rec, axis, binary_2D, pn_frac))
+            for n in range(self.n_levels_2D):
+                group, where = [], []
+                for Ec, rec, axis, binary_2D, pn_frac in planes:
+                    Pg_n = Pgs_dict[axis + str(n)]
+                    fname = f"{filename_prefix}_{axis}{n}.b"
+                    if not self._coded_2D(n):
+                        rows = int(self.offsets_list_2D[n + 1] - self.offsets_list_2D[n])
+                        group.append((Pg_n.reshape(1).expand(rows * F), fname))
+                        where.append((rec, slice(int(self.offsets_list_2D[n]), int(self.offsets_list_2D[n + 1]))))
+                        continue
+                    points_n, order, rows, unique_cnt = self._sorted_slots_2D(binary_2D, n)
+                    mean = self._mean_2D(Ec, n, points_n, Pg_n, binary_2D, pn_frac, order, unique_cnt,
+                                         outspace_params=rec, detach_pn=True)
+                    group.append((torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1), fname))
+                    where.append((rec, rows))
+                for sout, (rec, dst) in zip(coders.decode_group(group), where):
+                    rec[dst] = sout.view(-1, F)
+            coders.check()
         coders.shutdown()
         return params_q_xyz_rec, params_q_xy_rec, params_q_xz_rec, params_q_yz_rec

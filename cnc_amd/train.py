@@ -56,6 +56,9 @@ def build_parser():
     ap.add_argument("--guarded-step", dest="guarded_step", action="store_true",
                     help="the guarded step: an optimizer update whose gradients or loss are non-finite, or whose forward "
                          "tripped the fp16 range guard, is skipped, decided on the device (DESIGN.md §13)")
+    ap.add_argument("--device-coder", dest="device_coder", action="store_true",
+                    help="code the tables with the device entropy coder (interleaved rANS on the GPU, DESIGN.md §4.8) "
+                         "instead of the host range coder; the .b files are then in the rans1 format")
     return ap
 
 
@@ -71,6 +74,7 @@ def make_config_and_data(args, device, rank=0, world=1):
               n_features=args.n_features, max_steps=args.max_steps, image_size=args.image_size, seed=args.seed,
               out_dir=args.out_dir or f"./bitstreams/{scene}", reproducible=bool(getattr(args, "reproducible", False)),
               guarded_step=bool(getattr(args, "guarded_step", False)),
+              device_coder=bool(getattr(args, "device_coder", False)),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0

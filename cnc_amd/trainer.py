@@ -81,6 +81,10 @@ class TrainConfig:
     # value, or whose forward tripped the fp16 range guard, updates nothing — decided on the device, no host wait.
     # Also CNC_GUARDED_STEP=1
     guarded_step: bool = False
+    # the device entropy coder (cnc_amd.context.DeviceCoder): `encode` / `save_container` code the tables on
+    # the GPU in the "rans1" format instead of with the host range coder.  Also CNC_DEVICE_CODER=1.  Off by default.
+    device_coder: bool = False
+    symbols_per_lane: Optional[int] = None     # of the device coder; None = cnc_amd.context.DEVICE_CODER_SYMBOLS_PER_LANE
 
 
 class SyntheticBallDataset:
@@ -1003,8 +1007,13 @@ class Trainer:
         return tot / max(n_views, 1)
 
     # ------------------------------------------------------------------------------ codec
+    def coder_name(self) -> str:
+        """"device" when this Trainer codes with the device coder (TrainConfig.device_coder or CNC_DEVICE_CODER=1)."""
+        on = bool(getattr(self.cfg, "device_coder", False)) or os.environ.get("CNC_DEVICE_CODER", "0") == "1"
+        return "device" if on else "host"
+
     @torch.no_grad()
-    def encode(self, prefix: Optional[str] = None):
+    def encode(self, prefix: Optional[str] = None, coder: Optional[str] = None):
         os.makedirs(self.cfg.out_dir, exist_ok=True)
         prefix = prefix or os.path.join(self.cfg.out_dir, "b")
         os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
@@ -1012,11 +1021,13 @@ class Trainer:
         self.context.eval()
         return self.context.encode_binary_vxl_mixPg_3D2D(e.encoding_xyz, e.encoding_xy, e.encoding_xz,
                                                          e.encoding_yz, self.estimator.binaries,
-                                                         filename_prefix=prefix) + (prefix,)
+                                                         filename_prefix=prefix, coder=coder or self.coder_name(),
+                                                         symbols_per_lane=getattr(self.cfg, "symbols_per_lane", None)) + (prefix,)
 
     @torch.no_grad()
-    def decode_into_field(self, Pgs, prefix):
-        """Wipe the four tables, decode them from the .b files, install them (train:445-470)."""
+    def decode_into_field(self, Pgs, prefix, coder: Optional[str] = None):
+        """Wipe the four tables, decode them from the .b files, install them (train:445-470).  `coder`: what wrote the
+        files (default: this Trainer's coder)."""
         e = self.field.mlp_base
         recs = [torch.ones_like(t.params.data) for t in (e.encoding_xyz, e.encoding_xy, e.encoding_xz, e.encoding_yz)]
         for t in (e.encoding_xyz, e.encoding_xy, e.encoding_xz, e.encoding_yz):
@@ -1024,7 +1035,7 @@ class Trainer:
             t.invalidate_caches()
         recs = self.context.decode_binary_vxl_mixPg_3D2D(e.encoding_xyz, e.encoding_xy, e.encoding_xz,
                                                          e.encoding_yz, *recs, self.estimator.binaries, Pgs,
-                                                         filename_prefix=prefix)
+                                                         filename_prefix=prefix, coder=coder or self.coder_name())
         self.field.update_embedding_params(*recs)
 
     def sizes_MB(self, coded_MB: float) -> Dict[str, float]:
@@ -1053,6 +1064,8 @@ class Trainer:
                 "resolutions_list_2D": list(self.cfg.resolutions_list_2D),
                 "log2_hashmap_size": self.cfg.log2_hashmap_size,
                 "log2_hashmap_size_2D": self.cfg.log2_hashmap_size_2D}
+        if self.coder_name() == "device":
+            meta["coder"] = "rans1"       # the table streams' format; no key = the range coder's
         size = write_container(path, meta=meta, table_streams=streams, binaries=self.estimator.binaries,
                                field_mlp=self._mlp_state(), context_state=self.context.state_dict())
         return {"file_KB": size / 1024.0, "embeddings_KB": coded_MB * 1024.0, "estimate_KB": est_MB * 1024.0}
@@ -1071,4 +1084,7 @@ class Trainer:
         with tempfile.TemporaryDirectory() as td:
             for name, blob in streams.items():
                 open(os.path.join(td, f"b_{name}.b"), "wb").write(blob)
-            self.decode_into_field(Pgs, os.path.join(td, "b"))
+            fmt = meta.get("coder")
+            if fmt not in (None, "rans1"):
+                raise RuntimeError(f"{path}: table streams in an unknown format {fmt!r}")
+            self.decode_into_field(Pgs, os.path.join(td, "b"), coder="device" if fmt == "rans1" else "host")

@@ -1192,6 +1192,44 @@ int cnc_field_post_backward(const float* base_out, uint32_t ld_base, uint32_t ge
                             const uint8_t* selector, const float* grad_density, const float* grad_head_in,
                             uint32_t ld_head, uint32_t N, float* grad_base_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Device entropy coder (csrc/rans_coder.hip) — an extension: the reference codes on the host (torchac behind .cpu()
+ * copies, examples/utils_bpp_acc.py:77-110), and so does libcnc_codec.so's range coder.  Interleaved rANS, the
+ * "rans1" stream format of include/cnc_codec.h, byte for byte what cnc_rans_encode_pm1_host writes.
+ * One call codes a TABLE of independent streams: launches on one HIP stream serialise, and a single stream may have
+ * only a handful of lanes.
+ *
+ * A stream: x [n] float32 symbols (> 0 codes as +1; the decoder writes +-1.0f), p the probability of +1 of symbol i at
+ * p[i * p_stride], p_stride 0 (one probability for the stream) or 1; `bytes` with `cap_or_len` its capacity (encode)
+ * or the stream's length (decode), at any alignment.  symbols_per_lane >= 1 sets the lane count K = ceil(n / S) of an
+ * encode; a decode reads K from the stream and ignores it.  p, x and bytes are DEVICE pointers; the table itself is
+ * read from HOST memory during the call (it travels to the kernels as an argument, 24 streams per launch).          */
+typedef struct {
+    const float* p;
+    int64_t      p_stride;
+    float*       x;                  /* encode: read only */
+    int64_t      n;
+    int64_t      symbols_per_lane;
+    uint8_t*     bytes;
+    int64_t      cap_or_len;
+} cnc_rans_stream_t;
+
+/* Scratch of an encode call in bytes (2 bytes per symbol, the most a lane can emit, + 8 per lane); 0 for an invalid table. */
+uint64_t cnc_rans_scratch_bytes(const cnc_rans_stream_t* streams, uint32_t n_streams);
+
+/* Two launches per 24 streams: every lane codes its symbols last to first into its own part of `scratch` (16-byte
+ * aligned, contents dead after the call), backwards, so that its bytes lie in decode order; the second lays each stream
+ * out (header, directory, the lanes' states and bytes) and writes its size to sizes_dev[s] — or -1 when cap_or_len is
+ * too small, and then nothing of that stream is written.  Bytes of `bytes` past the size are left as they were.     */
+int cnc_rans_encode_pm1(const cnc_rans_stream_t* streams, uint32_t n_streams, void* scratch, uint64_t scratch_bytes,
+                        int64_t* sizes_dev, void* stream);
+
+/* One launch per 24 streams.  status_dev[s] = 0, or -3 for a stream whose header is not a rans1 header for n symbols
+ * (nothing of x is written then) or one of whose lanes does not end at L with its bytes used up (x is written, and
+ * wrong).  Whatever the bytes hold, reads stay inside bytes[0, cap_or_len) — a lane that runs off its sub-stream reads
+ * zeros — and writes inside x[0, n).  Callers run cnc_rans_check (cnc_codec.h) on the host before they upload a file. */
+int cnc_rans_decode_pm1(const cnc_rans_stream_t* streams, uint32_t n_streams, int32_t* status_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
