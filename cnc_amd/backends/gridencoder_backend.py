@@ -106,22 +106,48 @@ def _common_checks(named):
         check_contiguous(t, name)
 
 
-def grid_encode_forward(inputs, embeddings, offsets_list, resolutions_list, outputs, N, num_dim,
-                        n_features, n_levels, max_level, Rb, PV, dy_dx=None, binary_vxl=None,
-                        min_level_id=None, *, ste_binary=False, occ_sat=None, out_ld=0, out_col=0, vertex_bits=None):
-    _common_checks([("inputs", inputs), ("embeddings", embeddings), ("offsets_list", offsets_list),
-                    ("resolutions_list", resolutions_list), ("outputs", outputs)])
-    _check_floating(inputs, "inputs")
-    _check_floating(embeddings, "embeddings")
-    _check_int(offsets_list, "offsets_list")
-    _check_int(resolutions_list, "resolutions_list")
-    _check_floating(outputs, "outputs")
-    for name, t in (("inputs", inputs), ("embeddings", embeddings), ("outputs", outputs)):
-        _require_f32(t, name)
+_INT_TENSORS = ("offsets_list", "resolutions_list")
+
+
+def _check_encoder_call(named, n_features, num_dim, bits=None):
+    """The checks the encoder entries share, on the call's tensors in argument order: the level tables int32, `bits`
+    (the forward on a bit plane: no floating check there) uint8, every other tensor fp32."""
+    _common_checks(named)
+    for name, t in named:
+        if name in _INT_TENSORS:
+            _check_int(t, name)
+        elif bits is None:
+            _check_floating(t, name)
+    for name, t in named:
+        if name not in _INT_TENSORS and t is not bits:
+            _require_f32(t, name)
+    if bits is not None and bits.dtype != torch.uint8:
+        raise RuntimeError("bits must be a uint8 tensor")
     if n_features not in (1, 2, 4, 8, 16, 32):
         raise RuntimeError("GridEncoding: n_fearures must be 1, 2, 4, 8, 16 or 32.")
     if num_dim not in (1, 2, 3):
         raise RuntimeError("GridEncoding: num_dim must be 1, 2, 3.")
+
+
+def _backward_flags(ste_binary, *, key_bits=None, binned=False, interleave_levels=False, cell_merge=False,
+                    cell_carry=False):
+    """The flag word of a backward call: what the caller asked for and the route's measurement switches."""
+    flags = _lib.CNC_FLAG_STE_BINARY if ste_binary else 0
+    if key_bits is not None:                                  # the ordered route
+        return flags | (key_bits << _lib.CNC_ORDERED_KEY_BITS_SHIFT)
+    flags |= 0 if _MERGE_TILES else _lib.CNC_FLAG_MERGE_CONSECUTIVE
+    if binned:
+        return flags | (_lib.CNC_FLAG_BIN_LANE_STORES if _BIN_LANE_STORES else 0) \
+            | (_lib.CNC_FLAG_OWNER_XCD_PAIRS if _OWNER_XCD_PAIRS else 0)
+    return flags | (_lib.CNC_FLAG_LEVELS_FINEST_FIRST if interleave_levels else 0) \
+        | (_lib.CNC_FLAG_CELL_MERGE if cell_merge else 0) | (_lib.CNC_FLAG_CELL_CARRY if cell_merge and cell_carry else 0)
+
+
+def grid_encode_forward(inputs, embeddings, offsets_list, resolutions_list, outputs, N, num_dim,
+                        n_features, n_levels, max_level, Rb, PV, dy_dx=None, binary_vxl=None,
+                        min_level_id=None, *, ste_binary=False, occ_sat=None, out_ld=0, out_col=0, vertex_bits=None):
+    _check_encoder_call([("inputs", inputs), ("embeddings", embeddings), ("offsets_list", offsets_list),
+                         ("resolutions_list", resolutions_list), ("outputs", outputs)], n_features, num_dim)
     if binary_vxl is not None:
         binary_vxl = binary_vxl.contiguous()
     rc = _lib.lib().cnc_grid_encode_forward(
@@ -149,22 +175,8 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
     (level slot, point, corner) order and so the same from run to run; the route arguments above are then ignored.
     False = the routes above.  None = `ordered_backward_enabled()`: the process-wide mode, CNC_ORDERED_BACKWARD=1,
     torch.are_deterministic_algorithms_enabled()."""
-    _common_checks([("grad", grad), ("inputs", inputs), ("embeddings", embeddings),
-                    ("offsets_list", offsets_list), ("resolutions_list", resolutions_list),
-                    ("grad_embeddings", grad_embeddings)])
-    _check_floating(grad, "grad")
-    _check_floating(inputs, "inputs")
-    _check_floating(embeddings, "embeddings")
-    _check_int(offsets_list, "offsets_list")
-    _check_int(resolutions_list, "resolutions_list")
-    _check_floating(grad_embeddings, "grad_embeddings")
-    for name, t in (("grad", grad), ("inputs", inputs), ("embeddings", embeddings),
-                    ("grad_embeddings", grad_embeddings)):
-        _require_f32(t, name)
-    if n_features not in (1, 2, 4, 8, 16, 32):
-        raise RuntimeError("GridEncoding: n_fearures must be 1, 2, 4, 8, 16 or 32.")
-    if num_dim not in (1, 2, 3):
-        raise RuntimeError("GridEncoding: num_dim must be 1, 2, 3.")
+    _check_encoder_call([("grad", grad), ("inputs", inputs), ("embeddings", embeddings), ("offsets_list", offsets_list),
+                         ("resolutions_list", resolutions_list), ("grad_embeddings", grad_embeddings)], n_features, num_dim)
     if binary_vxl is not None:
         binary_vxl = binary_vxl.contiguous()
     if ordered_backward_enabled() if ordered is None else ordered:
@@ -178,8 +190,7 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
             ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets_list), ptr(resolutions_list),
             ptr(grad_embeddings), int(N), int(num_dim), int(n_features), int(n_levels), int(Rb),
             ptr(dy_dx), ptr(grad_inputs), ptr(binary_vxl), ptr(min_level_id),
-            (_lib.CNC_FLAG_STE_BINARY if ste_binary else 0)
-            | (max(rows_total.bit_length(), 1) << _lib.CNC_ORDERED_KEY_BITS_SHIFT), ptr(ste_clip_count),
+            _backward_flags(ste_binary, key_bits=max(rows_total.bit_length(), 1)), ptr(ste_clip_count),
             ptr(_check_sat(occ_sat, binary_vxl)), *_vb(vertex_bits, binary_vxl, 0 if min_level_id is not None else n_levels),
             int(grad_ld), int(grad_col), ptr(ws), nbytes, st)
         check(rc, "grid_encode_backward_ordered")
@@ -190,8 +201,7 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
         n_binned, level_rows = int(binned[0]), int(binned[1])
         L = _lib.lib()
         nbytes = int(L.cnc_grid_encode_backward_binned_workspace(int(N), n_binned, level_rows))
-        flags = (_lib.CNC_FLAG_STE_BINARY if ste_binary else 0) | (_lib.CNC_FLAG_BIN_LANE_STORES if _BIN_LANE_STORES else 0) \
-            | (_lib.CNC_FLAG_OWNER_XCD_PAIRS if _OWNER_XCD_PAIRS else 0) | (0 if _MERGE_TILES else _lib.CNC_FLAG_MERGE_CONSECUTIVE)
+        flags = _backward_flags(ste_binary, binned=True)
         if overlap_streams and _OVERLAP_ENABLED:
             # coarse levels on the caller's stream, the finest ones on side streams the library owns through a plan
             # object: fork, join and the split into groups live behind the C ABI (grid_encode_overlap.hip)
@@ -217,11 +227,8 @@ def grid_encode_backward(grad, inputs, embeddings, offsets_list, resolutions_lis
         ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets_list), ptr(resolutions_list),
         ptr(grad_embeddings), int(N), int(num_dim), int(n_features), int(n_levels), int(Rb),
         ptr(dy_dx), ptr(grad_inputs), ptr(binary_vxl), ptr(min_level_id),
-        (_lib.CNC_FLAG_STE_BINARY if ste_binary else 0)
-        | (_lib.CNC_FLAG_LEVELS_FINEST_FIRST if interleave_levels else 0)
-        | (0 if _MERGE_TILES else _lib.CNC_FLAG_MERGE_CONSECUTIVE)
-        | (_lib.CNC_FLAG_CELL_MERGE if cell_merge else 0)
-        | (_lib.CNC_FLAG_CELL_CARRY if cell_merge and cell_carry else 0), ptr(ste_clip_count),
+        _backward_flags(ste_binary, interleave_levels=interleave_levels, cell_merge=cell_merge, cell_carry=cell_carry),
+        ptr(ste_clip_count),
         ptr(_check_sat(occ_sat, binary_vxl)), *_vb(vertex_bits, binary_vxl, 0 if min_level_id is not None else n_levels),
         int(grad_ld), int(grad_col), stream(grad.device))
     check(rc, "grid_encode_backward")
@@ -351,18 +358,8 @@ def grid_encode_forward_bits(inputs, bits, offsets_list, resolutions_list, outpu
                              out_ld=0, out_col=0, vertex_bits=None):
     """(extension) grid_encode_forward on the bit plane of a binarised table; same outputs as
     grid_encode_forward(..., ste_binary=True) on the fp32 table."""
-    _common_checks([("inputs", inputs), ("bits", bits), ("offsets_list", offsets_list),
-                    ("resolutions_list", resolutions_list), ("outputs", outputs)])
-    _check_int(offsets_list, "offsets_list")
-    _check_int(resolutions_list, "resolutions_list")
-    _require_f32(inputs, "inputs")
-    _require_f32(outputs, "outputs")
-    if bits.dtype != torch.uint8:
-        raise RuntimeError("bits must be a uint8 tensor")
-    if n_features not in (1, 2, 4, 8, 16, 32):
-        raise RuntimeError("GridEncoding: n_fearures must be 1, 2, 4, 8, 16 or 32.")
-    if num_dim not in (1, 2, 3):
-        raise RuntimeError("GridEncoding: num_dim must be 1, 2, 3.")
+    _check_encoder_call([("inputs", inputs), ("bits", bits), ("offsets_list", offsets_list),
+                         ("resolutions_list", resolutions_list), ("outputs", outputs)], n_features, num_dim, bits=bits)
     if binary_vxl is not None:
         binary_vxl = binary_vxl.contiguous()
     rc = _lib.lib().cnc_grid_encode_forward_bits(

@@ -59,14 +59,10 @@ inline bool layout_ok(FeatLayout lay, uint32_t F, uint32_t L)
     return lay.col + L * F <= lay.ld && lay.ld % V == 0 && lay.col % V == 0;
 }
 
-// grid_encode.hip / grid_encode_merge.hip: the coarse call of the overlapped entry (grid_encode_overlap.hip)
-int grid_encode_backward_with_scratch(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
-                                      const int32_t* resolutions, float* grad_embeddings, uint32_t N, uint32_t D, uint32_t F,
-                                      uint32_t L, uint32_t Rb, const float* dy_dx, float* grad_inputs,
-                                      const uint8_t* binary_vxl, const int32_t* min_level_id, uint32_t flags,
-                                      const uint32_t* ste_clip_count, const int32_t* occ_sat, const uint32_t* vertex_bits,
-                                      const int32_t* vertex_bit_offsets, uint32_t grad_ld, uint32_t grad_col, void* stream,
-                                      uint16_t* tile_order);
+// grid_encode.hip / grid_encode_merge.hip: cnc_grid_encode_backward on a checked call (EncoderCall: encoder_common.hpp),
+// also the coarse call of the binned and the overlapped entries
+struct EncoderCall;
+int grid_encode_backward_with_scratch(const EncoderCall& c);
 uint64_t merge_tile_order_bytes(uint32_t N);
 
 inline int launch_status()

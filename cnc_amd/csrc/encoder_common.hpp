@@ -1,5 +1,6 @@
 // encoder_common.hpp — device code shared by the hash-grid encoder translation units:
-// vector load/store helpers, the per-(point, level) corner set-up and the point loader.
+// vector load/store helpers, the per-(point, level) corner set-up and the point loader; and, host side (at the end),
+// the one descriptor of an encoder call with its validator, level ranges and the scratch split of the binned routes.
 #pragma once
 
 #include "common.hpp"
@@ -623,23 +624,6 @@ __device__ __forceinline__ void unit_features_fast(const float (&x)[D], bool ins
     unit_finish_fast<D, F>(u, acc);
 }
 
-// One backward call as the cell-merging scatter (grid_encode_cells.hip) takes it.
-struct CellsArgs {
-    const float*    grad;
-    const float*    inputs;
-    const float*    emb;
-    const int32_t*  offsets;
-    const int32_t*  resolutions;
-    float*          grad_emb;
-    const uint8_t*  vxl;
-    const int32_t*  mli;
-    const uint32_t* clip_count;
-    const int32_t*  sat;
-    FeatLayout      lay;
-    uint32_t        N, L, Rb;
-    uint32_t        carry;           // != 0: shared vertices of x-neighbour cells go out once (CNC_FLAG_CELL_CARRY)
-};
-
 template <uint32_t D>
 __device__ __forceinline__ bool load_point(const float* __restrict__ inputs, uint32_t b,
                                            float (&x)[D])
@@ -652,5 +636,141 @@ __device__ __forceinline__ bool load_point(const float* __restrict__ inputs, uin
     }
     return !oob;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Host side: one encoder call between the C ABI and the launches.  Never a kernel parameter: the kernels take its
+// members, or a struct built from it next to the kernel (CellsArgs, BinnedArgs).
+// ---------------------------------------------------------------------------------------------
+struct EncoderCall {
+    // an entry point's raw arguments, in the order the backward entries list them
+    const float*    grad;            // backward only
+    const float*    inputs;
+    const float*    emb;
+    const int32_t*  offsets;
+    const int32_t*  resolutions;
+    float*          out;             // forward: outputs; backward: grad_embeddings
+    uint32_t        N, D, F, L, Rb;
+    const float*    dy_dx;           // backward only, with grad_inputs: both or neither
+    float*          grad_inputs;
+    const uint8_t*  vxl;
+    const int32_t*  mli;
+    uint32_t        flags;
+    const uint32_t* clip_count;      // backward + STE only
+    const int32_t*  sat;             // optional summed-volume table of the occupancy grid: kept only with vxl
+    const uint32_t* vbits;           // optional vertex bit planes: attached to `lay` only with vxl and both pointers
+    const int32_t*  vboff;
+    FeatLayout      lay;             // {ld, col} where outputs (forward) / gradients (backward) live
+    hipStream_t     stream;
+    const uint8_t*  bits = nullptr;  // forward_bits: the table's sign bit plane, in the place of emb
+    // scratch of merge_tile_order_bytes(N) a caller inside the library lends k_grid_encode_bwd_merge for the segment
+    // order of its depth-ranked tiles (nullptr: consecutive samples)
+    uint16_t*       tile_order = nullptr;
+
+    bool empty() const { return N == 0 || L == 0; }
+    bool ste() const { return (flags & CNC_FLAG_STE_BINARY) != 0; }
+    // what kernel_input_backward and the binned passes take: where the gradients live, nothing else
+    FeatLayout plain_layout() const { return FeatLayout{lay.ld, lay.col}; }
+};
+
+// forward: cnc_grid_encode_forward, _forward_bits.  backward: cnc_grid_encode_backward, whose layout
+// grid_encode_backward_with_scratch checks (for the library's own sub-calls too).  routed: _backward_ordered, _binned,
+// _overlapped, which have checks of their own in front of the layout's (they call layout_ok where they always did) and
+// fix the order of the level slots themselves.
+enum class EncoderEntry { forward, backward, routed };
+
+// The checks the entry points share, in the order each of them makes them; completes the descriptor.  CNC_OK on an
+// empty call too: `if (rc != CNC_OK || c.empty()) return rc;`
+inline int validate(EncoderCall& c, EncoderEntry e)
+{
+    const bool bwd = e != EncoderEntry::forward;
+    if (bwd && (c.dy_dx == nullptr) != (c.grad_inputs == nullptr)) return CNC_ERR_INVALID_VALUE;   // both or neither
+    if (c.empty()) return CNC_OK;
+    if ((bwd && !c.grad) || !c.inputs || !(c.emb || c.bits) || !c.offsets || !c.resolutions || !c.out)
+        return CNC_ERR_INVALID_VALUE;
+    if (!c.vxl) c.sat = nullptr;
+    if (e == EncoderEntry::backward) c.lay.finest_first = (c.flags & CNC_FLAG_LEVELS_FINEST_FIRST) ? 1u : 0u;
+    if (!bwd && !layout_ok(c.lay, c.F, c.L)) return CNC_ERR_INVALID_VALUE;
+    if (c.vxl && c.vbits && c.vboff) { c.lay.vbits = c.vbits; c.lay.vboff = c.vboff; }
+    return CNC_OK;
+}
+
+// Levels [first, first + count) of a call as a call of its own (the binned routes: no mask, no per-point level windows).
+inline EncoderCall levels(const EncoderCall& c, uint32_t first, uint32_t count)
+{
+    EncoderCall s = c;
+    s.offsets += first;
+    s.resolutions += first;
+    s.L = count;
+    // level-major [L, N, F]: the levels start first * N * F floats in; point-major: first * F columns to the right
+    if (c.lay.ld == 0) s.grad += (uint64_t)first * c.N * c.F;
+    else s.lay.col += first * c.F;
+    return s;
+}
+
+// The coarse half of a binned call: levels [0, count) on the atomic kernels, finest first.
+inline EncoderCall coarse_levels(const EncoderCall& c, uint32_t count, uint16_t* tile_order)
+{
+    EncoderCall s = levels(c, 0, count);
+    s.flags |= CNC_FLAG_LEVELS_FINEST_FIRST;
+    s.lay.finest_first = 1;
+    s.tile_order = tile_order;
+    return s;
+}
+
+// Scratch of the binned routes: the bins first, the merge kernel's tile order (2 KB per window) in the aligned tail.
+constexpr uint64_t kScratchAlign = 256;
+inline uint64_t scratch_round_up(uint64_t v) { return (v + kScratchAlign - 1) / kScratchAlign * kScratchAlign; }
+
+// Bytes a caller brings for both.  `groups` (the overlapped entry): two groups pad their shares to kScratchAlign; every
+// split of the levels in two needs the same amount (a level's bytes do not depend on its group) and one group needs
+// less, so this covers whatever split the call chooses; the serial fallback (small N, no coarse levels) needs the
+// whole set of bins in one piece.
+inline uint64_t scratch_bytes(uint32_t N, uint32_t n_binned, uint32_t level_rows, bool groups)
+{
+    uint64_t bins = cnc_grid_encode_backward_binned_workspace(N, n_binned, level_rows);
+    if (groups && n_binned >= 2) {
+        const uint64_t two = scratch_round_up(cnc_grid_encode_backward_binned_workspace(N, 1, level_rows))
+                             + scratch_round_up(cnc_grid_encode_backward_binned_workspace(N, n_binned - 1, level_rows));
+        if (two > bins) bins = two;
+    }
+    return scratch_round_up(bins) + merge_tile_order_bytes(N);
+}
+
+// The tile order's place in a workspace of that size or more, `bins_bytes` (in: the workspace's) cut down to what is
+// in front of it; nullptr and all of it for the bins when the caller brought less.
+inline uint16_t* split_scratch(uint32_t N, uint32_t n_binned, uint32_t level_rows, bool groups, void* workspace,
+                               uint64_t& bins_bytes)
+{
+    if (!workspace || (uintptr_t)workspace % 16 != 0 || bins_bytes < scratch_bytes(N, n_binned, level_rows, groups))
+        return nullptr;
+    bins_bytes = (bins_bytes - merge_tile_order_bytes(N)) / kScratchAlign * kScratchAlign;
+    return reinterpret_cast<uint16_t*>((char*)workspace + bins_bytes);
+}
+
+// The F ladder of the launchers: CALL with FF = F as a constant
+#define CNC_F_SWITCH(F, CALL)                             \
+    switch (F) {                                          \
+    case 1: { constexpr uint32_t FF = 1; CALL; } break;   \
+    case 2: { constexpr uint32_t FF = 2; CALL; } break;   \
+    case 4: { constexpr uint32_t FF = 4; CALL; } break;   \
+    case 8: { constexpr uint32_t FF = 8; CALL; } break;   \
+    case 16: { constexpr uint32_t FF = 16; CALL; } break; \
+    case 32: { constexpr uint32_t FF = 32; CALL; } break; \
+    default: return CNC_ERR_INVALID_VALUE;                \
+    }
+
+// (grid_encode.hip's grid_encode_backward_with_scratch: common.hpp)
+// grid_encode_cells.hip; false = not built for this shape (the caller keeps its own kernel)
+bool launch_bwd_cells(const EncoderCall& c);
+// grid_encode_merge.hip
+void launch_bwd_merge(const EncoderCall& c);
+// grid_encode_binned.hip: cnc_grid_encode_backward_binned on a checked call
+int grid_encode_backward_binned(const EncoderCall& c, uint32_t n_binned, uint32_t level_rows, void* workspace,
+                                uint64_t workspace_bytes);
+// grid_input_grad.hip
+int launch_dy_dx(const float* inputs, const float* emb, const int32_t* offsets, const int32_t* resolutions,
+                 float* dy_dx, uint32_t N, uint32_t D, uint32_t F, uint32_t L, const int32_t* mli, bool ste,
+                 hipStream_t s);
+int launch_input_backward(const EncoderCall& c);
 
 }  // namespace cnc

@@ -795,28 +795,8 @@ __global__ __launch_bounds__(256) void k_cnt_np_embed_bwd(
 // ---------------------------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------------------------
-struct EncArgs {
-    const float*   inputs;
-    const float*   emb;
-    const int32_t* offsets;
-    const int32_t* resolutions;
-    float*         out;        // forward: outputs; backward: grad_embeddings
-    const float*   grad;       // backward only
-    uint32_t       N, L, Rb;
-    const uint8_t* vxl;
-    const int32_t* mli;
-    hipStream_t    stream;
-    const uint32_t* clip_count = nullptr;   // backward + STE only
-    const int32_t*  sat = nullptr;          // optional summed-volume table of the occupancy grid
-    FeatLayout      lay{0, 0};              // where outputs (forward) / gradients (backward) live
-    // k_grid_encode_bwd_merge (grid_encode_merge.hip): CNC_FLAG_MERGE_CONSECUTIVE, and scratch of merge_tile_order_bytes(N)
-    // for the segment order of its depth-ranked tiles (nullptr: consecutive samples)
-    bool            merge_consecutive = false;
-    uint16_t*       tile_order = nullptr;
-};
-
 template <uint32_t D, uint32_t F, bool VXL, bool STE>
-static void launch_fwd(const EncArgs& a)
+static void launch_fwd(const EncoderCall& a)
 {
     constexpr uint32_t V = F < 4 ? F : 4, G = F / V;
     const dim3 grid(div_up(a.N * G, 256), a.L, 1);
@@ -824,23 +804,13 @@ static void launch_fwd(const EncArgs& a)
                        a.inputs, a.emb, a.offsets, a.resolutions, a.out, a.N, a.Rb, a.vxl, a.mli, a.sat, a.lay);
 }
 
-// grid_encode_cells.hip (CellsArgs: encoder_common.hpp)
-bool launch_bwd_cells(const CellsArgs& a, uint32_t D, uint32_t F, bool ste, hipStream_t s);
-
-// grid_encode_merge.hip
-void launch_bwd_merge(const float* grad, const float* inputs, const float* emb, const int32_t* offsets,
-                      const int32_t* resolutions, float* grad_emb, uint32_t N, uint32_t L,
-                      const uint32_t* clip_count, FeatLayout lay, bool ste, bool consecutive, uint16_t* tile_order,
-                      hipStream_t s);
-
 template <uint32_t D, uint32_t F, bool VXL, bool STE>
-static void launch_bwd(const EncArgs& a)
+static void launch_bwd(const EncoderCall& a)
 {
     if constexpr (D == 3 && F == 8 && !VXL) {
         // coarse half of a binned call: runs merged across the rays of a 1024-sample block
         if (a.lay.finest_first && !a.mli && (uint64_t)div_up(a.N, 256) * a.L < (1ull << 31)) {
-            launch_bwd_merge(a.grad, a.inputs, a.emb, a.offsets, a.resolutions, a.out, a.N, a.L, a.clip_count,
-                             a.lay, STE, a.merge_consecutive, a.tile_order, a.stream);
+            launch_bwd_merge(a);
             return;
         }
     }
@@ -869,8 +839,9 @@ static void launch_bwd(const EncArgs& a)
 
 
 template <bool BWD, uint32_t D, uint32_t F>
-static void dispatch_flags(const EncArgs& a, bool ste)
+static void dispatch_flags(const EncoderCall& a)
 {
+    const bool ste = a.ste();
     const bool vxl = a.vxl != nullptr;
 #define CNC_GO(VX, ST)                                   \
     do {                                                 \
@@ -885,37 +856,22 @@ static void dispatch_flags(const EncArgs& a, bool ste)
 }
 
 template <bool BWD, uint32_t D>
-static int dispatch_F(const EncArgs& a, uint32_t F, bool ste)
+static int dispatch_F(const EncoderCall& a)
 {
-    switch (F) {
-    case 1: dispatch_flags<BWD, D, 1>(a, ste); break;
-    case 2: dispatch_flags<BWD, D, 2>(a, ste); break;
-    case 4: dispatch_flags<BWD, D, 4>(a, ste); break;
-    case 8: dispatch_flags<BWD, D, 8>(a, ste); break;
-    case 16: dispatch_flags<BWD, D, 16>(a, ste); break;
-    case 32: dispatch_flags<BWD, D, 32>(a, ste); break;
-    default: return CNC_ERR_INVALID_VALUE;   // "n_fearures must be 1, 2, 4, 8, 16 or 32"
-    }
+    CNC_F_SWITCH(a.F, (dispatch_flags<BWD, D, FF>(a)))   // default: "n_fearures must be 1, 2, 4, 8, 16 or 32"
     return CNC_OK;
 }
 
 template <bool BWD>
-static int dispatch_D(const EncArgs& a, uint32_t D, uint32_t F, bool ste)
+static int dispatch_D(const EncoderCall& a)
 {
-    switch (D) {
-    case 1: return dispatch_F<BWD, 1>(a, F, ste);
-    case 2: return dispatch_F<BWD, 2>(a, F, ste);
-    case 3: return dispatch_F<BWD, 3>(a, F, ste);
+    switch (a.D) {
+    case 1: return dispatch_F<BWD, 1>(a);
+    case 2: return dispatch_F<BWD, 2>(a);
+    case 3: return dispatch_F<BWD, 3>(a);
     default: return CNC_ERR_INVALID_VALUE;   // "num_dim must be 1, 2, 3"
     }
 }
-
-// grid_input_grad.hip
-int launch_dy_dx(const float* inputs, const float* emb, const int32_t* offsets, const int32_t* resolutions,
-                 float* dy_dx, uint32_t N, uint32_t D, uint32_t F, uint32_t L, const int32_t* mli, bool ste,
-                 hipStream_t s);
-int launch_input_backward(const float* grad, const float* dy_dx, float* grad_inputs, uint32_t N, uint32_t D,
-                          uint32_t F, uint32_t L, FeatLayout lay, hipStream_t s);
 
 }  // namespace cnc
 
@@ -931,56 +887,25 @@ extern "C" int cnc_grid_encode_forward(const float* inputs, const float* embeddi
                                        uint32_t out_ld, uint32_t out_col, void* stream)
 {
     (void)PV;
-    if (N == 0 || L == 0) return CNC_OK;
-    if (!inputs || !embeddings || !offsets || !resolutions || !outputs) return CNC_ERR_INVALID_VALUE;
-    EncArgs a{inputs, embeddings, offsets, resolutions, outputs, nullptr, N, L, Rb,
-              binary_vxl, min_level_id, (hipStream_t)stream, nullptr, binary_vxl ? occ_sat : nullptr,
-              FeatLayout{out_ld, out_col}};
-    if (!layout_ok(a.lay, F, L)) return CNC_ERR_INVALID_VALUE;
-    if (binary_vxl && vertex_bits && vertex_bit_offsets) { a.lay.vbits = vertex_bits; a.lay.vboff = vertex_bit_offsets; }
-    int rc = dispatch_D<false>(a, D, F, (flags & CNC_FLAG_STE_BINARY) != 0);
+    EncoderCall c{nullptr, inputs, embeddings, offsets, resolutions, outputs, N, D, F, L, Rb, nullptr, nullptr, binary_vxl,
+                  min_level_id, flags, nullptr, occ_sat, vertex_bits, vertex_bit_offsets, FeatLayout{out_ld, out_col},
+                  (hipStream_t)stream};
+    int rc = validate(c, EncoderEntry::forward);
+    if (rc != CNC_OK || c.empty()) return rc;
+    rc = dispatch_D<false>(c);
     if (rc == CNC_OK && dy_dx)   // the dy_dx branch of kernel_grid, as its own launch (not a hot path)
-        rc = launch_dy_dx(inputs, embeddings, offsets, resolutions, dy_dx, N, D, F, L, min_level_id,
-                          (flags & CNC_FLAG_STE_BINARY) != 0, (hipStream_t)stream);
+        rc = launch_dy_dx(inputs, embeddings, offsets, resolutions, dy_dx, N, D, F, L, min_level_id, c.ste(), c.stream);
     return rc != CNC_OK ? rc : launch_status();
 }
 
-// cnc_grid_encode_backward, plus the scratch a caller inside the library may lend the merge kernel
-// (merge_tile_order_bytes(N) bytes for the segment order of the depth-ranked tiles, or nullptr)
-int cnc::grid_encode_backward_with_scratch(const float* grad, const float* inputs,
-                                           const float* embeddings, const int32_t* offsets,
-                                           const int32_t* resolutions, float* grad_embeddings,
-                                           uint32_t N, uint32_t D, uint32_t F, uint32_t L,
-                                           uint32_t Rb, const float* dy_dx, float* grad_inputs,
-                                           const uint8_t* binary_vxl, const int32_t* min_level_id,
-                                           uint32_t flags, const uint32_t* ste_clip_count,
-                                           const int32_t* occ_sat, const uint32_t* vertex_bits,
-                                           const int32_t* vertex_bit_offsets, uint32_t grad_ld,
-                                           uint32_t grad_col, void* stream, uint16_t* tile_order)
+// cnc_grid_encode_backward behind its checks; a caller inside the library hands it sub-calls (levels()) and may lend
+// the merge kernel scratch (EncoderCall::tile_order)
+int cnc::grid_encode_backward_with_scratch(const EncoderCall& c)
 {
-    if ((dy_dx == nullptr) != (grad_inputs == nullptr)) return CNC_ERR_INVALID_VALUE;   // both or neither
-    if (N == 0 || L == 0) return CNC_OK;
-    if (!grad || !inputs || !embeddings || !offsets || !resolutions || !grad_embeddings)
-        return CNC_ERR_INVALID_VALUE;
-    EncArgs a{inputs, embeddings, offsets, resolutions, grad_embeddings, grad, N, L, Rb,
-              binary_vxl, min_level_id, (hipStream_t)stream, ste_clip_count,
-              binary_vxl ? occ_sat : nullptr,
-              FeatLayout{grad_ld, grad_col, (flags & CNC_FLAG_LEVELS_FINEST_FIRST) ? 1u : 0u}};
-    if (!layout_ok(a.lay, F, L)) return CNC_ERR_INVALID_VALUE;
-    a.merge_consecutive = (flags & CNC_FLAG_MERGE_CONSECUTIVE) != 0;
-    a.tile_order = tile_order;
-    if (binary_vxl && vertex_bits && vertex_bit_offsets) { a.lay.vbits = vertex_bits; a.lay.vboff = vertex_bit_offsets; }
+    if (!layout_ok(c.lay, c.F, c.L)) return CNC_ERR_INVALID_VALUE;
     int rc = CNC_OK;
-    bool done = false;
-    if ((flags & CNC_FLAG_CELL_MERGE) && !dy_dx) {
-        const CellsArgs ca{grad, inputs, embeddings, offsets, resolutions, grad_embeddings, binary_vxl, min_level_id,
-                           ste_clip_count, a.sat, a.lay, N, L, Rb, (flags & CNC_FLAG_CELL_CARRY) ? 1u : 0u};
-        done = launch_bwd_cells(ca, D, F, (flags & CNC_FLAG_STE_BINARY) != 0, (hipStream_t)stream);
-    }
-    if (!done) rc = dispatch_D<true>(a, D, F, (flags & CNC_FLAG_STE_BINARY) != 0);
-    if (rc == CNC_OK && dy_dx)   // kernel_input_backward (gridencoder.cu:588-614)
-        rc = launch_input_backward(grad, dy_dx, grad_inputs, N, D, F, L, FeatLayout{grad_ld, grad_col},
-                                   (hipStream_t)stream);
+    if (!((c.flags & CNC_FLAG_CELL_MERGE) && !c.dy_dx && launch_bwd_cells(c))) rc = dispatch_D<true>(c);
+    if (rc == CNC_OK && c.dy_dx) rc = launch_input_backward(c);
     return rc != CNC_OK ? rc : launch_status();
 }
 
@@ -995,21 +920,12 @@ extern "C" int cnc_grid_encode_backward(const float* grad, const float* inputs,
                                         const int32_t* vertex_bit_offsets, uint32_t grad_ld,
                                         uint32_t grad_col, void* stream)
 {
-    return grid_encode_backward_with_scratch(grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F, L, Rb,
-                                             dy_dx, grad_inputs, binary_vxl, min_level_id, flags, ste_clip_count, occ_sat,
-                                             vertex_bits, vertex_bit_offsets, grad_ld, grad_col, stream, nullptr);
+    EncoderCall c{grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F, L, Rb, dy_dx, grad_inputs,
+                  binary_vxl, min_level_id, flags, ste_clip_count, occ_sat, vertex_bits, vertex_bit_offsets,
+                  FeatLayout{grad_ld, grad_col}, (hipStream_t)stream};
+    const int rc = validate(c, EncoderEntry::backward);
+    return rc != CNC_OK || c.empty() ? rc : grid_encode_backward_with_scratch(c);
 }
-
-#define CNC_F_SWITCH(F, CALL)                         \
-    switch (F) {                                      \
-    case 1: { constexpr uint32_t FF = 1; CALL; } break;   \
-    case 2: { constexpr uint32_t FF = 2; CALL; } break;   \
-    case 4: { constexpr uint32_t FF = 4; CALL; } break;   \
-    case 8: { constexpr uint32_t FF = 8; CALL; } break;   \
-    case 16: { constexpr uint32_t FF = 16; CALL; } break; \
-    case 32: { constexpr uint32_t FF = 32; CALL; } break; \
-    default: return CNC_ERR_INVALID_VALUE;            \
-    }
 
 extern "C" int cnc_cnt_np_embed(const int16_t* inputs, const float* embeddings_clip,
                                 float* outputs, uint32_t N, uint32_t resolution, uint32_t F,
@@ -1056,11 +972,10 @@ extern "C" int cnc_pack_sign_bits(const float* embeddings, uint8_t* bits, uint64
 }
 
 template <uint32_t D, uint32_t F>
-static void launch_fwd_bits(const float* inputs, const uint8_t* bits, const int32_t* offsets,
-                            const int32_t* resolutions, float* outputs, uint32_t N, uint32_t L,
-                            uint32_t Rb, const uint8_t* vxl, const int32_t* mli, const int32_t* sat,
-                            FeatLayout lay, hipStream_t s)
+static void launch_fwd_bits(const EncoderCall& c)
 {
+    const uint32_t N = c.N, L = c.L;
+    FeatLayout     lay = c.lay;
     // point-major rows: several level slots per lane (see the kernel)
     uint32_t P = 1;
     if (lay.ld != 0 && L > 1) {
@@ -1072,7 +987,7 @@ static void launch_fwd_bits(const float* inputs, const uint8_t* bits, const int3
     const int tr_mode = getenv("CNC_FWD_TR") ? atoi(getenv("CNC_FWD_TR")) : 1;
     const uint32_t W = P * F, tail = (L % P) * F;
     const bool tr = tr_mode && (W == 8 || W == 16 || W == 32) && tail % 4 == 0 && lay.ld % 4 == 0 && lay.col % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(outputs) & 15u) == 0;
+                    (reinterpret_cast<uintptr_t>(c.out) & 15u) == 0;
     const uint32_t cp_log2 = W == 8 ? 1u : (W == 16 ? 2u : 3u);
     // streaming stores of the level-major outputs (a wave writes whole lines): the bit plane keeps the L2
     // (CNC_FWD_NT=0: measurement switch).  Point-major rows: only with the transposed stores — a lane's own 16-byte
@@ -1084,13 +999,14 @@ static void launch_fwd_bits(const float* inputs, const uint8_t* bits, const int3
     // paired x-neighbour gathers of the lean evaluator (CNC_FWD_PAIR: 0 off, 1 hashed levels inside the kFwdPair*Res
     // window, 2 every hashed level that qualifies: measurement switch); the words are aligned loads, so the plane has to be
     uint32_t pair_mode = getenv("CNC_FWD_PAIR") ? (uint32_t)atoi(getenv("CNC_FWD_PAIR")) : 1u;
-    if (reinterpret_cast<uintptr_t>(bits) & (CNC_FWD_PAIR_BYTES - 1u)) pair_mode = 0;
+    if (reinterpret_cast<uintptr_t>(c.bits) & (CNC_FWD_PAIR_BYTES - 1u)) pair_mode = 0;
     const dim3 grid(div_up(N, 256), div_up(L, P), 1);
     const size_t lds = tr ? (size_t)256 * W * sizeof(float) : 0;
 #define CNC_FWD_BITS(VX, TRV)                                                                                        \
-    hipLaunchKernelGGL((k_grid_encode_fwd_bits<D, F, VX, TRV>), grid, dim3(256), TRV ? lds : 0, s, inputs, bits, offsets, \
-                       resolutions, outputs, N, L, P, cp_log2, Rb, vxl, mli, VX ? sat : nullptr, lay, lut_mode, pair_mode)
-    if (vxl) { if (tr) CNC_FWD_BITS(true, true); else CNC_FWD_BITS(true, false); }
+    hipLaunchKernelGGL((k_grid_encode_fwd_bits<D, F, VX, TRV>), grid, dim3(256), TRV ? lds : 0, c.stream, c.inputs, c.bits, \
+                       c.offsets, c.resolutions, c.out, N, L, P, cp_log2, c.Rb, c.vxl, c.mli, VX ? c.sat : nullptr, lay,    \
+                       lut_mode, pair_mode)
+    if (c.vxl) { if (tr) CNC_FWD_BITS(true, true); else CNC_FWD_BITS(true, false); }
     else     { if (tr) CNC_FWD_BITS(false, true); else CNC_FWD_BITS(false, false); }
 #undef CNC_FWD_BITS
 }
@@ -1103,15 +1019,12 @@ extern "C" int cnc_grid_encode_forward_bits(const float* inputs, const uint8_t* 
                                             const uint32_t* vertex_bits, const int32_t* vertex_bit_offsets,
                                             uint32_t out_ld, uint32_t out_col, void* stream)
 {
-    if (N == 0 || L == 0) return CNC_OK;
-    if (!inputs || !bits || !offsets || !resolutions || !outputs) return CNC_ERR_INVALID_VALUE;
-    FeatLayout lay{out_ld, out_col};
-    if (!layout_ok(lay, F, L)) return CNC_ERR_INVALID_VALUE;
-    if (binary_vxl && vertex_bits && vertex_bit_offsets) { lay.vbits = vertex_bits; lay.vboff = vertex_bit_offsets; }
-    hipStream_t s = (hipStream_t)stream;
-#define CNC_BITS_D(DD)                                                                              \
-    CNC_F_SWITCH(F, (launch_fwd_bits<DD, FF>(inputs, bits, offsets, resolutions, outputs, N, L, Rb, \
-                                             binary_vxl, min_level_id, occ_sat, lay, s)))
+    EncoderCall c{nullptr, inputs, nullptr, offsets, resolutions, outputs, N, D, F, L, Rb, nullptr, nullptr, binary_vxl,
+                  min_level_id, 0, nullptr, occ_sat, vertex_bits, vertex_bit_offsets, FeatLayout{out_ld, out_col},
+                  (hipStream_t)stream, bits};
+    const int rc = validate(c, EncoderEntry::forward);
+    if (rc != CNC_OK || c.empty()) return rc;
+#define CNC_BITS_D(DD) CNC_F_SWITCH(F, (launch_fwd_bits<DD, FF>(c)))
     switch (D) {
     case 1: CNC_BITS_D(1); break;
     case 2: CNC_BITS_D(2); break;

@@ -694,6 +694,50 @@ extern "C" uint64_t cnc_grid_encode_backward_binned_workspace(uint32_t N, uint32
     return (uint64_t)n_binned * bins * (kHeadBytes + (uint64_t)default_cap(N, (uint32_t)bins) * sizeof(Item));
 }
 
+// cnc_grid_encode_backward_binned on a checked call (the overlapped entry hands its level groups in as calls of their own)
+int cnc::grid_encode_backward_binned(const EncoderCall& c, uint32_t n_binned, uint32_t level_rows, void* workspace,
+                                     uint64_t workspace_bytes)
+{
+    const uint32_t N = c.N, F = c.F, L = c.L;
+    if (n_binned > L) return CNC_ERR_INVALID_VALUE;
+    // what is not binned goes through the atomic kernel, with the same arguments
+    if (L - n_binned > 0) {
+        // scratch beyond what the bins were asked for (what cnc_grid_encode_backward_overlapped_workspace adds, when that
+        // entry hands a call on as a whole): its tail holds the segment order of the merge kernel's depth-ranked tiles
+        uint16_t* tile_order = split_scratch(N, n_binned, level_rows, false, workspace, workspace_bytes);
+        const int rc = grid_encode_backward_with_scratch(coarse_levels(c, L - n_binned, tile_order));
+        if (rc != CNC_OK) return rc;
+    }
+    if (n_binned == 0) return CNC_OK;
+    if (c.D != 3 || !(F == 2 || F == 4 || F == 8)) return CNC_ERR_UNSUPPORTED;
+    if (!layout_ok(c.lay, F, L)) return CNC_ERR_INVALID_VALUE;
+    const uint32_t bins = div_up(level_rows, kSlab);
+    if (bins == 0 || bins > kMaxBins || !workspace) return CNC_ERR_INVALID_VALUE;
+    // layout: [heads x 16 B: bin counters, padded so the items stay 16-byte aligned][heads x cap items]
+    const uint64_t heads = (uint64_t)n_binned * bins;
+    if ((uintptr_t)workspace % 16 != 0) return CNC_ERR_INVALID_VALUE;
+    if (workspace_bytes < heads * (kHeadBytes + 64 * sizeof(Item))) return CNC_ERR_INVALID_VALUE;   // one batch per bin
+    uint64_t cap = (workspace_bytes - heads * kHeadBytes) / (heads * sizeof(Item));
+    if (cap > 0x0FFFFFFFull) cap = 0x0FFFFFFFull;
+
+    uint32_t* ws = (uint32_t*)workspace;
+    if (hipMemsetAsync(ws, 0, heads * 4, c.stream) != hipSuccess) return CNC_ERR_LAUNCH;
+    const uint32_t part = owner_part(N, bins, cap), parts = div_up((uint32_t)cap, part);
+    // pairs of levels on complementary halves of the XCD labels (owner_slab); an odd level out stays on all eight
+    const uint32_t n_pairs = (c.flags & CNC_FLAG_OWNER_XCD_PAIRS) ? n_binned / 2 : 0;
+    if (owner_grid_size(n_binned, bins, parts, n_pairs) > 0x7FFFFFFFull) return CNC_ERR_INVALID_VALUE;
+    const BinnedArgs a{c.grad, c.inputs, c.emb, c.offsets, c.resolutions, c.out, N, L - n_binned,
+                       bins, (uint32_t)cap, part, parts, n_pairs, ws, (Item*)((char*)workspace + heads * kHeadBytes),
+                       c.clip_count, c.plain_layout()};
+    const bool sorted = (c.flags & CNC_FLAG_BIN_LANE_STORES) == 0;
+    switch (F) {
+    case 2: launch_binned<2>(a, n_binned, c.ste(), sorted, c.stream); break;
+    case 4: launch_binned<4>(a, n_binned, c.ste(), sorted, c.stream); break;
+    default: launch_binned<8>(a, n_binned, c.ste(), sorted, c.stream); break;
+    }
+    return launch_status();
+}
+
 extern "C" int cnc_grid_encode_backward_binned(const float* grad, const float* inputs,
                                                const float* embeddings, const int32_t* offsets,
                                                const int32_t* resolutions, float* grad_embeddings,
@@ -704,61 +748,9 @@ extern "C" int cnc_grid_encode_backward_binned(const float* grad, const float* i
                                                void* workspace, uint64_t workspace_bytes,
                                                void* stream)
 {
-    if (N == 0 || L == 0) return CNC_OK;
-    if (!grad || !inputs || !embeddings || !offsets || !resolutions || !grad_embeddings)
-        return CNC_ERR_INVALID_VALUE;
-    if (n_binned > L) return CNC_ERR_INVALID_VALUE;
-    // what is not binned goes through the atomic kernel, with the same arguments
-    if (L - n_binned > 0) {
-        // scratch beyond what the bins were asked for (what cnc_grid_encode_backward_overlapped_workspace adds, when that
-        // entry hands a call on as a whole): its tail holds the segment order of the merge kernel's depth-ranked tiles
-        uint16_t*      tile_order = nullptr;
-        const uint64_t order_bytes = merge_tile_order_bytes(N);
-        const uint64_t bins_bytes = (cnc_grid_encode_backward_binned_workspace(N, n_binned, level_rows) + 255) / 256 * 256;
-        if (workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= bins_bytes + order_bytes) {
-            workspace_bytes = (workspace_bytes - order_bytes) / 256 * 256;
-            tile_order = reinterpret_cast<uint16_t*>((char*)workspace + workspace_bytes);
-        }
-        const int rc = grid_encode_backward_with_scratch(grad, inputs, embeddings, offsets, resolutions,
-                                                         grad_embeddings, N, D, F, L - n_binned, 0, nullptr,
-                                                         nullptr, nullptr, nullptr,
-                                                         flags | CNC_FLAG_LEVELS_FINEST_FIRST, ste_clip_count,
-                                                         nullptr, nullptr, nullptr, grad_ld, grad_col, stream, tile_order);
-        if (rc != CNC_OK) return rc;
-    }
-    if (n_binned == 0) return CNC_OK;
-    if (D != 3 || !(F == 2 || F == 4 || F == 8)) return CNC_ERR_UNSUPPORTED;
-    if (grad_ld != 0) {
-        const uint32_t V = F < 4 ? F : 4;
-        if (grad_col + L * F > grad_ld || grad_ld % V || grad_col % V) return CNC_ERR_INVALID_VALUE;
-    } else if (grad_col != 0) {
-        return CNC_ERR_INVALID_VALUE;
-    }
-    const uint32_t bins = div_up(level_rows, kSlab);
-    if (bins == 0 || bins > kMaxBins || !workspace) return CNC_ERR_INVALID_VALUE;
-    // layout: [heads x 16 B: bin counters, padded so the items stay 16-byte aligned][heads x cap items]
-    const uint64_t heads = (uint64_t)n_binned * bins;
-    if ((uintptr_t)workspace % 16 != 0) return CNC_ERR_INVALID_VALUE;
-    if (workspace_bytes < heads * (kHeadBytes + 64 * sizeof(Item))) return CNC_ERR_INVALID_VALUE;   // one batch per bin
-    uint64_t cap = (workspace_bytes - heads * kHeadBytes) / (heads * sizeof(Item));
-    if (cap > 0x0FFFFFFFull) cap = 0x0FFFFFFFull;
-
-    hipStream_t s = (hipStream_t)stream;
-    uint32_t*   ws = (uint32_t*)workspace;
-    if (hipMemsetAsync(ws, 0, heads * 4, s) != hipSuccess) return CNC_ERR_LAUNCH;
-    const uint32_t part = owner_part(N, bins, cap), parts = div_up((uint32_t)cap, part);
-    // pairs of levels on complementary halves of the XCD labels (owner_slab); an odd level out stays on all eight
-    const uint32_t n_pairs = (flags & CNC_FLAG_OWNER_XCD_PAIRS) ? n_binned / 2 : 0;
-    if (owner_grid_size(n_binned, bins, parts, n_pairs) > 0x7FFFFFFFull) return CNC_ERR_INVALID_VALUE;
-    BinnedArgs a{grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, L - n_binned,
-                 bins, (uint32_t)cap, part, parts, n_pairs, ws, (Item*)((char*)workspace + heads * kHeadBytes), ste_clip_count,
-                 FeatLayout{grad_ld, grad_col}};
-    const bool ste = (flags & CNC_FLAG_STE_BINARY) != 0;
-    const bool sorted = (flags & CNC_FLAG_BIN_LANE_STORES) == 0;
-    switch (F) {
-    case 2: launch_binned<2>(a, n_binned, ste, sorted, s); break;
-    case 4: launch_binned<4>(a, n_binned, ste, sorted, s); break;
-    default: launch_binned<8>(a, n_binned, ste, sorted, s); break;
-    }
-    return launch_status();
+    EncoderCall c{grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F, L, 0, nullptr, nullptr, nullptr,
+                  nullptr, flags, ste_clip_count, nullptr, nullptr, nullptr, FeatLayout{grad_ld, grad_col},
+                  (hipStream_t)stream};
+    const int rc = validate(c, EncoderEntry::routed);
+    return rc != CNC_OK || c.empty() ? rc : grid_encode_backward_binned(c, n_binned, level_rows, workspace, workspace_bytes);
 }

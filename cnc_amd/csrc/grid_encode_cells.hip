@@ -38,6 +38,23 @@
 
 namespace cnc {
 
+// One backward call as the kernel takes it.
+struct CellsArgs {
+    const float*    grad;
+    const float*    inputs;
+    const float*    emb;
+    const int32_t*  offsets;
+    const int32_t*  resolutions;
+    float*          grad_emb;
+    const uint8_t*  vxl;
+    const int32_t*  mli;
+    const uint32_t* clip_count;
+    const int32_t*  sat;
+    FeatLayout      lay;
+    uint32_t        N, L, Rb;
+    uint32_t        carry;           // != 0: shared vertices of x-neighbour cells go out once (CNC_FLAG_CELL_CARRY)
+};
+
 template <uint32_t D, uint32_t F, bool VXL, bool STE, uint32_t MB>
 __global__ __launch_bounds__(MB) void k_grid_encode_bwd_cells(const CellsArgs a)
 {
@@ -364,13 +381,15 @@ static void launch_cells_flags(const CellsArgs& a, bool ste, hipStream_t s)
 
 // D in {2, 3}, F in {2, 4, 8} (any resolution: points on levels above kCellKeyMaxRes are scattered one by one); false =
 // not built for this shape (the caller keeps its own kernel)
-bool launch_bwd_cells(const CellsArgs& a, uint32_t D, uint32_t F, bool ste, hipStream_t s)
+bool launch_bwd_cells(const EncoderCall& c)
 {
-    if ((uint64_t)div_up(a.N, 512u) * a.L >= (1ull << 31)) return false;
-#define CNC_CELLS(DD, FF)                            \
-    if (D == DD && F == FF) {                        \
-        launch_cells_flags<DD, FF>(a, ste, s);       \
-        return true;                                 \
+    if ((uint64_t)div_up(c.N, 512u) * c.L >= (1ull << 31)) return false;
+    const CellsArgs a{c.grad, c.inputs, c.emb, c.offsets, c.resolutions, c.out, c.vxl, c.mli, c.clip_count, c.sat, c.lay,
+                      c.N, c.L, c.Rb, (c.flags & CNC_FLAG_CELL_CARRY) ? 1u : 0u};
+#define CNC_CELLS(DD, FF)                                    \
+    if (c.D == DD && c.F == FF) {                            \
+        launch_cells_flags<DD, FF>(a, c.ste(), c.stream);    \
+        return true;                                         \
     }
     CNC_CELLS(3, 8) CNC_CELLS(3, 4) CNC_CELLS(3, 2) CNC_CELLS(2, 8) CNC_CELLS(2, 4) CNC_CELLS(2, 2)
 #undef CNC_CELLS

@@ -472,23 +472,23 @@ uint64_t merge_tile_order_bytes(uint32_t N)
 }
 
 // grid_encode.hip launches this for the coarse half of a binned call (D = 3, F = 8)
-void launch_bwd_merge(const float* grad, const float* inputs, const float* emb, const int32_t* offsets,
-                      const int32_t* resolutions, float* grad_emb, uint32_t N, uint32_t L,
-                      const uint32_t* clip_count, FeatLayout lay, bool ste, bool consecutive, uint16_t* tile_order,
-                      hipStream_t s)
+void launch_bwd_merge(const EncoderCall& c)
 {
+    const uint32_t N = c.N, L = c.L;
+    const bool     ste = c.ste();
+    FeatLayout     lay = c.lay;
     lay.n_slots = L;
     // (round 3 measured this kernel with padded dynamic LDS — one block per CU, to leave room for the owner waves of
     // the binned levels: slower; the switch is gone, the library keeps no state between calls)
     const bool small = (uint64_t)div_up(N, 1024u) * L < 4096u;       // fewer than eight rounds of 1024-sample blocks
-#define CNC_MERGE_GO(ST, MBS, W, S)                                                                                \
-    hipLaunchKernelGGL((k_grid_encode_bwd_merge<ST, MBS, W, S>), dim3(div_up(N, MBS) * L), dim3(MBS), 0, s, grad, inputs, \
-                       emb, offsets, resolutions, grad_emb, N, clip_count, lay, tile_order)
+#define CNC_MERGE_GO(ST, MBS, W, S)                                                                                     \
+    hipLaunchKernelGGL((k_grid_encode_bwd_merge<ST, MBS, W, S>), dim3(div_up(N, MBS) * L), dim3(MBS), 0, c.stream, c.grad, \
+                       c.inputs, c.emb, c.offsets, c.resolutions, c.out, N, c.clip_count, lay, c.tile_order)
     if (small) {
         // training batches of unrelated short rays: consecutive samples
         if (ste) CNC_MERGE_GO(true, 512u, 0u, 0u);
         else CNC_MERGE_GO(false, 512u, 0u, 0u);
-    } else if (consecutive || tile_order == nullptr) {
+    } else if ((c.flags & CNC_FLAG_MERGE_CONSECUTIVE) || c.tile_order == nullptr) {
         // CNC_FLAG_MERGE_CONSECUTIVE (the tiling before the depth-ranked tiles, for comparisons inside one build), or a
         // caller without scratch for the segment order
         if (ste) CNC_MERGE_GO(true, 1024u, 0u, 0u);
@@ -497,7 +497,7 @@ void launch_bwd_merge(const float* grad, const float* inputs, const float* emb, 
         // same grid: block id / L = window * (tiles per window) + tile, and a tile with a sample below N exists exactly
         // where a consecutive block does
         hipLaunchKernelGGL((k_merge_tile_order<kMergeTileWindow, kMergeTileSegment>), dim3(div_up(N, kMergeTileWindow)),
-                           dim3(1024), 0, s, inputs, N, tile_order);
+                           dim3(1024), 0, c.stream, c.inputs, N, c.tile_order);
         if (ste) CNC_MERGE_GO(true, 1024u, kMergeTileWindow, kMergeTileSegment);
         else CNC_MERGE_GO(false, 1024u, kMergeTileWindow, kMergeTileSegment);
     }
@@ -506,8 +506,12 @@ void launch_bwd_merge(const float* grad, const float* inputs, const float* emb, 
     // pays for it.  On such a level the 4096 threads walk the samples grid-stride, 2^D F atomics each: slow for millions
     // of samples, but no encoder CNC builds has a level of R > 2^16, and the merge kernel keeps its speed)
     const dim3 wide(div_up(N, 256u) < 16u ? div_up(N, 256u) : 16u, L);
-    if (ste) hipLaunchKernelGGL((k_grid_encode_bwd_wide<true>), wide, dim3(256), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
-    else hipLaunchKernelGGL((k_grid_encode_bwd_wide<false>), wide, dim3(256), 0, s, grad, inputs, emb, offsets, resolutions, grad_emb, N, clip_count, lay);
+#define CNC_WIDE_GO(ST)                                                                                               \
+    hipLaunchKernelGGL((k_grid_encode_bwd_wide<ST>), wide, dim3(256), 0, c.stream, c.grad, c.inputs, c.emb, c.offsets, \
+                       c.resolutions, c.out, N, c.clip_count, lay)
+    if (ste) CNC_WIDE_GO(true);
+    else CNC_WIDE_GO(false);
+#undef CNC_WIDE_GO
 }
 
 }  // namespace cnc

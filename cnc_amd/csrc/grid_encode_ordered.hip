@@ -26,10 +26,6 @@
 
 namespace cnc {
 
-// grid_input_grad.hip
-int launch_input_backward(const float* grad, const float* dy_dx, float* grad_inputs, uint32_t N, uint32_t D,
-                          uint32_t F, uint32_t L, FeatLayout lay, hipStream_t s);
-
 namespace {
 
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;   // sorts behind every row: offsets are int32, a row is < 2^31
@@ -170,25 +166,8 @@ bool ordered_scratch(uint32_t N, uint32_t D, void* base, hipStream_t s, OrderedS
     return true;
 }
 
-struct OrderedArgs {
-    const float*    grad;
-    const float*    inputs;
-    const float*    emb;
-    const int32_t*  offsets;
-    const int32_t*  resolutions;
-    float*          grad_emb;
-    const uint8_t*  vxl;
-    const int32_t*  mli;
-    const uint32_t* clip_count;
-    const int32_t*  sat;
-    FeatLayout      lay;
-    uint32_t        N, L, Rb, key_bits;
-    bool            ste;
-    hipStream_t     stream;
-};
-
 template <uint32_t D>
-void launch_emit(const OrderedArgs& a, uint32_t slot, const OrderedScratch& o)
+void launch_emit(const EncoderCall& a, uint32_t slot, const OrderedScratch& o)
 {
     const dim3 grid(div_up(a.N, 256));
     if (a.vxl)
@@ -200,45 +179,38 @@ void launch_emit(const OrderedArgs& a, uint32_t slot, const OrderedScratch& o)
 }
 
 template <uint32_t F>
-int launch_reduce(const OrderedArgs& a, uint32_t D, uint32_t slot, const uint32_t* keys, const uint32_t* seqs,
+int launch_reduce(const EncoderCall& a, uint32_t slot, const uint32_t* keys, const uint32_t* seqs,
                   const OrderedScratch& o)
 {
     constexpr uint32_t G = F / (F < 4 ? F : 4);
-    const uint32_t M = a.N << D;
+    const uint32_t M = a.N << a.D;
     const uint64_t blocks = ((uint64_t)M * G + 255) / 256;
     if (blocks >= (1ull << 31)) return CNC_ERR_INVALID_VALUE;
     const dim3 grid((uint32_t)blocks);
-    if (a.ste)
+    if (a.ste())
         hipLaunchKernelGGL((k_ordered_reduce<F, true>), grid, dim3(256), 0, a.stream, keys, seqs, o.weights, a.grad, a.emb,
-                           a.grad_emb, a.clip_count, M, a.N, D, slot, a.lay);
+                           a.out, a.clip_count, M, a.N, a.D, slot, a.lay);
     else
         hipLaunchKernelGGL((k_ordered_reduce<F, false>), grid, dim3(256), 0, a.stream, keys, seqs, o.weights, a.grad, a.emb,
-                           a.grad_emb, a.clip_count, M, a.N, D, slot, a.lay);
+                           a.out, a.clip_count, M, a.N, a.D, slot, a.lay);
     return CNC_OK;
 }
 
-int run_ordered(const OrderedArgs& a, uint32_t D, uint32_t F, const OrderedScratch& o)
+// key_bits: the sort's, enough for every row of the tables
+int run_ordered(const EncoderCall& a, uint32_t key_bits, const OrderedScratch& o)
 {
-    const uint32_t M = a.N << D;
+    const uint32_t M = a.N << a.D;
     for (uint32_t slot = 0; slot < a.L; slot++) {
-        switch (D) {
+        switch (a.D) {
         case 1: launch_emit<1>(a, slot, o); break;
         case 2: launch_emit<2>(a, slot, o); break;
         default: launch_emit<3>(a, slot, o); break;
         }
         rocprim::double_buffer<uint32_t> k(o.keys[0], o.keys[1]), v(o.seqs[0], o.seqs[1]);
         size_t bytes = o.sort_bytes;
-        if (rocprim::radix_sort_pairs(o.sort, bytes, k, v, M, 0, a.key_bits, a.stream) != hipSuccess) return CNC_ERR_LAUNCH;
+        if (rocprim::radix_sort_pairs(o.sort, bytes, k, v, M, 0, key_bits, a.stream) != hipSuccess) return CNC_ERR_LAUNCH;
         int rc = CNC_OK;
-        switch (F) {
-        case 1: rc = launch_reduce<1>(a, D, slot, k.current(), v.current(), o); break;
-        case 2: rc = launch_reduce<2>(a, D, slot, k.current(), v.current(), o); break;
-        case 4: rc = launch_reduce<4>(a, D, slot, k.current(), v.current(), o); break;
-        case 8: rc = launch_reduce<8>(a, D, slot, k.current(), v.current(), o); break;
-        case 16: rc = launch_reduce<16>(a, D, slot, k.current(), v.current(), o); break;
-        case 32: rc = launch_reduce<32>(a, D, slot, k.current(), v.current(), o); break;
-        default: return CNC_ERR_INVALID_VALUE;
-        }
+        CNC_F_SWITCH(a.F, rc = launch_reduce<FF>(a, slot, k.current(), v.current(), o))
         if (rc != CNC_OK) return rc;
     }
     return CNC_OK;
@@ -266,25 +238,21 @@ extern "C" int cnc_grid_encode_backward_ordered(const float* grad, const float* 
                                                 uint32_t grad_ld, uint32_t grad_col, void* workspace,
                                                 uint64_t workspace_bytes, void* stream)
 {
-    if ((dy_dx == nullptr) != (grad_inputs == nullptr)) return CNC_ERR_INVALID_VALUE;   // both or neither
-    if (N == 0 || L == 0) return CNC_OK;
-    if (!grad || !inputs || !embeddings || !offsets || !resolutions || !grad_embeddings || !workspace)
-        return CNC_ERR_INVALID_VALUE;
+    EncoderCall c{grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F, L, Rb, dy_dx, grad_inputs,
+                  binary_vxl, min_level_id, flags, ste_clip_count, occ_sat, vertex_bits, vertex_bit_offsets,
+                  FeatLayout{grad_ld, grad_col}, (hipStream_t)stream};
+    int rc = validate(c, EncoderEntry::routed);
+    if (rc != CNC_OK || c.empty()) return rc;
+    if (!workspace) return CNC_ERR_INVALID_VALUE;
     if (!(F == 1 || F == 2 || F == 4 || F == 8 || F == 16 || F == 32)) return CNC_ERR_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
     OrderedScratch o;
-    if (!ordered_scratch(N, D, workspace, s, o) || workspace_bytes < o.total ||
+    if (!ordered_scratch(N, D, workspace, c.stream, o) || workspace_bytes < o.total ||
         (reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
         return CNC_ERR_INVALID_VALUE;
     uint32_t key_bits = (flags >> CNC_ORDERED_KEY_BITS_SHIFT) & 63u;
     if (key_bits == 0 || key_bits > 32) key_bits = 32;
-    OrderedArgs a{grad, inputs, embeddings, offsets, resolutions, grad_embeddings, binary_vxl, min_level_id, ste_clip_count,
-                  binary_vxl ? occ_sat : nullptr, FeatLayout{grad_ld, grad_col}, N, L, Rb, key_bits,
-                  (flags & CNC_FLAG_STE_BINARY) != 0, s};
-    if (!layout_ok(a.lay, F, L)) return CNC_ERR_INVALID_VALUE;
-    if (binary_vxl && vertex_bits && vertex_bit_offsets) { a.lay.vbits = vertex_bits; a.lay.vboff = vertex_bit_offsets; }
-    int rc = run_ordered(a, D, F, o);
-    if (rc == CNC_OK && dy_dx)   // kernel_input_backward (gridencoder.cu:588-614): per point, no atomics, already exact
-        rc = launch_input_backward(grad, dy_dx, grad_inputs, N, D, F, L, FeatLayout{grad_ld, grad_col}, s);
+    if (!layout_ok(c.lay, F, L)) return CNC_ERR_INVALID_VALUE;
+    rc = run_ordered(c, key_bits, o);
+    if (rc == CNC_OK && dy_dx) rc = launch_input_backward(c);   // per point, no atomics: already exact
     return rc != CNC_OK ? rc : launch_status();
 }

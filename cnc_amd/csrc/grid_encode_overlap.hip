@@ -15,7 +15,8 @@
 #include <new>
 
 #include "cnc_hip.h"
-#include "common.hpp"      // grid_encode_backward_with_scratch, merge_tile_order_bytes
+#include "common.hpp"
+#include "encoder_common.hpp"      // EncoderCall, levels, split_scratch
 
 struct cnc_backward_plan {
     hipStream_t side[2];
@@ -27,9 +28,6 @@ struct cnc_backward_plan {
 
 namespace {
 constexpr uint32_t kMinOverlapPoints = 1u << 16;   // below that the events cost more than the overlap returns
-constexpr uint64_t kAlign = 256;
-
-inline uint64_t round_up(uint64_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 // The finest levels run as ONE group: the bin pass of all of them, then their owner pass, on one side stream.  Until
 // round 8 four or more levels went as two halves on the two side streams (the bin pass of one next to the owner pass of
@@ -90,16 +88,7 @@ extern "C" int cnc_backward_plan_destroy(cnc_backward_plan* p)
 
 extern "C" uint64_t cnc_grid_encode_backward_overlapped_workspace(uint32_t N, uint32_t n_binned, uint32_t level_rows)
 {
-    // Two groups pad their shares to 256 bytes; every split of the levels in two needs the same amount (a level's bytes
-    // do not depend on its group) and one group needs less, so this covers whatever split the call chooses.
-    uint64_t total = 0;
-    if (n_binned >= 2)
-        total = round_up(cnc_grid_encode_backward_binned_workspace(N, 1, level_rows))
-                + round_up(cnc_grid_encode_backward_binned_workspace(N, n_binned - 1, level_rows));
-    // the serial fallback (small N, no coarse levels) needs the whole set of bins in one piece
-    const uint64_t serial = cnc_grid_encode_backward_binned_workspace(N, n_binned, level_rows);
-    // behind the bins: the segment order of the coarse call's depth-ranked tiles (k_merge_tile_order), 2 KB per window
-    return round_up(total > serial ? total : serial) + cnc::merge_tile_order_bytes(N);
+    return cnc::scratch_bytes(N, n_binned, level_rows, true);
 }
 
 extern "C" int cnc_grid_encode_backward_overlapped(cnc_backward_plan* plan, const float* grad, const float* inputs,
@@ -110,52 +99,40 @@ extern "C" int cnc_grid_encode_backward_overlapped(cnc_backward_plan* plan, cons
                                                    uint32_t n_binned, uint32_t level_rows,
                                                    void* workspace, uint64_t workspace_bytes, void* stream)
 {
-    if (N == 0 || L == 0) return CNC_OK;
+    using namespace cnc;
+    EncoderCall c{grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F, L, 0, nullptr, nullptr, nullptr,
+                  nullptr, flags, ste_clip_count, nullptr, nullptr, nullptr, FeatLayout{grad_ld, grad_col},
+                  (hipStream_t)stream};
+    int rc = validate(c, EncoderEntry::routed);
+    if (rc != CNC_OK || c.empty()) return rc;
     if (n_binned > L) return CNC_ERR_INVALID_VALUE;
     const uint32_t coarse = L - n_binned;
     if (!plan || coarse == 0 || n_binned == 0 || N < kMinOverlapPoints)
-        return cnc_grid_encode_backward_binned(grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F, L,
-                                               flags, ste_clip_count, grad_ld, grad_col, n_binned, level_rows, workspace,
-                                               workspace_bytes, stream);
-    if (!grad || !inputs || !embeddings || !offsets || !resolutions || !grad_embeddings || !workspace)
-        return CNC_ERR_INVALID_VALUE;
-    if ((uintptr_t)workspace % 16 != 0) return CNC_ERR_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
+        return grid_encode_backward_binned(c, n_binned, level_rows, workspace, workspace_bytes);
+    if (!workspace || (uintptr_t)workspace % 16 != 0) return CNC_ERR_INVALID_VALUE;
     // a caller that brought all the scratch asked for lends its tail to the coarse call; with less, the bins keep all of
     // it and the merge kernel's blocks take consecutive samples
-    uint16_t* tile_order = nullptr;
-    if (workspace_bytes >= cnc_grid_encode_backward_overlapped_workspace(N, n_binned, level_rows)) {
-        workspace_bytes = (workspace_bytes - cnc::merge_tile_order_bytes(N)) / kAlign * kAlign;
-        tile_order = reinterpret_cast<uint16_t*>((char*)workspace + workspace_bytes);
-    }
+    uint16_t* tile_order = split_scratch(N, n_binned, level_rows, true, workspace, workspace_bytes);
     uint32_t first[2], count[2];
     const int groups = split_groups(n_binned, plan->group_split, first, count);
     // each group gets a share of the caller's scratch proportional to its level count (deeper bins when the caller
     // passes more than the minimum)
-    if (hipEventRecord(plan->fork, s) != hipSuccess) return CNC_ERR_LAUNCH;
-    int rc = CNC_OK;
+    if (hipEventRecord(plan->fork, c.stream) != hipSuccess) return CNC_ERR_LAUNCH;
     uint64_t used = 0;
     for (int g = 0; g < groups; ++g) {
-        const uint32_t l0 = coarse + first[g];
-        uint64_t share = g + 1 < groups ? workspace_bytes * count[g] / n_binned / kAlign * kAlign : workspace_bytes - used;
+        uint64_t share = g + 1 < groups ? workspace_bytes * count[g] / n_binned / kScratchAlign * kScratchAlign : workspace_bytes - used;
         char* ws = (char*)workspace + used;
         used += share;
-        // level-major [L, N, F]: the group's levels start l0 * N * F floats in; point-major: l0 * F columns to the right
-        const float*   g_grad = grad_ld == 0 ? grad + (uint64_t)l0 * N * F : grad;
-        const uint32_t g_col = grad_ld == 0 ? grad_col : grad_col + l0 * F;
         if (hipStreamWaitEvent(plan->side[g], plan->fork, 0) != hipSuccess) return CNC_ERR_LAUNCH;
-        const int rg = cnc_grid_encode_backward_binned(g_grad, inputs, embeddings, offsets + l0, resolutions + l0,
-                                                       grad_embeddings, N, D, F, count[g], flags, ste_clip_count, grad_ld,
-                                                       g_col, count[g], level_rows, ws, share, plan->side[g]);
+        EncoderCall gc = levels(c, coarse + first[g], count[g]);
+        gc.stream = plan->side[g];
+        const int rg = grid_encode_backward_binned(gc, count[g], level_rows, ws, share);
         if (rg != CNC_OK && rc == CNC_OK) rc = rg;
         if (hipEventRecord(plan->join[g], plan->side[g]) != hipSuccess) return CNC_ERR_LAUNCH;
     }
     // the coarse levels fill in next to the (longer) bin + owner passes, on the caller's stream
-    const int rc0 = cnc::grid_encode_backward_with_scratch(grad, inputs, embeddings, offsets, resolutions, grad_embeddings, N, D, F,
-                                                      coarse, 0, nullptr, nullptr, nullptr, nullptr,
-                                                      flags | CNC_FLAG_LEVELS_FINEST_FIRST, ste_clip_count, nullptr, nullptr,
-                                                      nullptr, grad_ld, grad_col, stream, tile_order);
+    const int rc0 = grid_encode_backward_with_scratch(coarse_levels(c, coarse, tile_order));
     for (int g = 0; g < groups; ++g)
-        if (hipStreamWaitEvent(s, plan->join[g], 0) != hipSuccess) return CNC_ERR_LAUNCH;
+        if (hipStreamWaitEvent(c.stream, plan->join[g], 0) != hipSuccess) return CNC_ERR_LAUNCH;
     return rc0 != CNC_OK ? rc0 : rc;
 }

@@ -114,24 +114,13 @@ __global__ __launch_bounds__(256) void k_input_backward(const float* __restrict_
     grad_inputs[t] = result;
 }
 
-#define CNC_IG_F(F, CALL)                                 \
-    switch (F) {                                          \
-    case 1: { constexpr uint32_t FF = 1; CALL; } break;   \
-    case 2: { constexpr uint32_t FF = 2; CALL; } break;   \
-    case 4: { constexpr uint32_t FF = 4; CALL; } break;   \
-    case 8: { constexpr uint32_t FF = 8; CALL; } break;   \
-    case 16: { constexpr uint32_t FF = 16; CALL; } break; \
-    case 32: { constexpr uint32_t FF = 32; CALL; } break; \
-    default: return CNC_ERR_INVALID_VALUE;                \
-    }
-
 template <uint32_t D>
 static int dy_dx_D(const float* inputs, const float* emb, const int32_t* offsets, const int32_t* resolutions,
                    float* dy_dx, uint32_t N, uint32_t F, uint32_t L, const int32_t* mli, bool ste,
                    hipStream_t s)
 {
     const dim3 grid(div_up(N, 256), L);
-    CNC_IG_F(F, {
+    CNC_F_SWITCH(F, {
         if (ste) hipLaunchKernelGGL((k_grid_dy_dx<D, FF, true>), grid, dim3(256), 0, s, inputs, emb, offsets, resolutions, dy_dx, N, L, mli);
         else hipLaunchKernelGGL((k_grid_dy_dx<D, FF, false>), grid, dim3(256), 0, s, inputs, emb, offsets, resolutions, dy_dx, N, L, mli);
     });
@@ -151,21 +140,21 @@ int launch_dy_dx(const float* inputs, const float* emb, const int32_t* offsets, 
 }
 
 template <uint32_t D>
-static int input_backward_D(const float* grad, const float* dy_dx, float* grad_inputs, uint32_t N, uint32_t F,
-                            uint32_t L, FeatLayout lay, hipStream_t s)
+static int input_backward_D(const EncoderCall& c)
 {
-    const dim3 grid(div_up(N * D, 256));
-    CNC_IG_F(F, hipLaunchKernelGGL((k_input_backward<D, FF>), grid, dim3(256), 0, s, grad, dy_dx, grad_inputs, N, L, lay));
+    const dim3 grid(div_up(c.N * D, 256));
+    CNC_F_SWITCH(c.F, hipLaunchKernelGGL((k_input_backward<D, FF>), grid, dim3(256), 0, c.stream, c.grad, c.dy_dx,
+                                         c.grad_inputs, c.N, c.L, c.plain_layout()));
     return CNC_OK;
 }
 
-int launch_input_backward(const float* grad, const float* dy_dx, float* grad_inputs, uint32_t N, uint32_t D,
-                          uint32_t F, uint32_t L, FeatLayout lay, hipStream_t s)
+// kernel_input_backward (gridencoder.cu:588-614) of a backward call with dy_dx / grad_inputs
+int launch_input_backward(const EncoderCall& c)
 {
-    switch (D) {
-    case 1: return input_backward_D<1>(grad, dy_dx, grad_inputs, N, F, L, lay, s);
-    case 2: return input_backward_D<2>(grad, dy_dx, grad_inputs, N, F, L, lay, s);
-    case 3: return input_backward_D<3>(grad, dy_dx, grad_inputs, N, F, L, lay, s);
+    switch (c.D) {
+    case 1: return input_backward_D<1>(c);
+    case 2: return input_backward_D<2>(c);
+    case 3: return input_backward_D<3>(c);
     default: return CNC_ERR_INVALID_VALUE;
     }
 }
