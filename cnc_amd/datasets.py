@@ -7,11 +7,13 @@ constructor arguments, `len()`, `loader[i]` -> {"pixels", "rays", "color_bkgd"},
 attributes the drivers read (`images`, `camtoworlds`, `K`, `HEIGHT`, `WIDTH`, `training`, and for T&T the scene
 box and step size).  Images are read with PIL (imageio / cv2 are not available offline) and kept on the device as
 uint8; rays are generated on the device.  No dataset ships with this repository: without a `data_root` the
-trainer uses the procedural scene of cnc_amd.trainer.
+trainer uses the procedural scene below (`SyntheticBallDataset`); `LoaderDataset` puts a pair of loaders behind the
+three calls the Trainer makes.
 """
 from __future__ import annotations
 
 import json
+import math
 import os
 
 import numpy as np
@@ -168,3 +170,128 @@ class SubjectLoader_Tanks(_PosedImages):
         self.images = torch.from_numpy(images).to(device)
         self.camtoworlds = torch.from_numpy(poses).to(device)
         self.K = torch.from_numpy(intrinsics).to(device)
+
+
+class SyntheticBallDataset:
+    """Procedural scene: an opaque textured ball of radius 0.8 in front of a white background,
+    seen from cameras on a sphere of radius 4 (focal as nerf_synthetic, camera_angle_x=0.6911).
+    `fetch(num_rays)` returns random training pixels like SubjectLoader.fetch_data in training mode
+    (nerf_synthetic.py:164-239); `view(i)` returns a whole test image."""
+
+    RADIUS = 0.8
+
+    def __init__(self, image_size=200, n_train_views=100, device="cuda", seed=0):
+        self.H = self.W = image_size
+        self.focal = 0.5 * image_size / math.tan(0.5 * 0.6911)
+        self.device = torch.device(device)
+        self.gen = torch.Generator(device=self.device).manual_seed(seed)
+        g = torch.Generator().manual_seed(1234)
+        self.train_c2w = self._poses(n_train_views, g).to(self.device)
+        self.test_c2w = self._poses(16, torch.Generator().manual_seed(4321)).to(self.device)
+        self.num_rays = 1024
+
+    @staticmethod
+    def _poses(n, g):
+        az = torch.rand(n, generator=g) * 2 * math.pi
+        el = (torch.rand(n, generator=g) - 0.3) * 1.2
+        eye = 4.0 * torch.stack([torch.cos(el) * torch.cos(az), torch.cos(el) * torch.sin(az), torch.sin(el)], -1)
+        fwd = -eye / eye.norm(dim=-1, keepdim=True)
+        up0 = torch.tensor([0.0, 0.0, 1.0]).expand_as(fwd)
+        right = torch.linalg.cross(fwd, up0)
+        right = right / right.norm(dim=-1, keepdim=True)
+        up = torch.linalg.cross(right, fwd)
+        return torch.cat([torch.stack([right, up, -fwd], dim=-1), eye[..., None]], dim=-1)   # [n,3,4]
+
+    def update_num_rays(self, n):
+        self.num_rays = int(n)
+
+    def _rays(self, c2w, x, y):
+        cam = torch.stack([(x - self.W / 2 + 0.5) / self.focal, -(y - self.H / 2 + 0.5) / self.focal,
+                           -torch.ones_like(x)], dim=-1)
+        d = (cam[:, None, :] * c2w[:, :3, :3]).sum(-1)
+        d = d / torch.linalg.norm(d, dim=-1, keepdim=True)
+        o = c2w[:, :3, 3].expand_as(d)
+        return o.contiguous(), d.contiguous()
+
+    def _shade(self, o, d):
+        """Ground-truth pixel colour and alpha: first hit of the ball."""
+        b = (o * d).sum(-1)
+        c = (o * o).sum(-1) - self.RADIUS ** 2
+        disc = b * b - c
+        hit = disc > 0
+        t = -b - torch.sqrt(disc.clamp_min(0))
+        p = o + d * t[:, None]
+        n = p / self.RADIUS
+        if getattr(self, "_shade_consts", None) is None or self._shade_consts[0].device != p.device:
+            self._shade_consts = (torch.tensor([0.0, 2.0, 4.0], device=p.device),
+                                  torch.tensor([0.3, 0.5, 0.8], device=p.device))
+        phase, light = self._shade_consts
+        tex = 0.5 + 0.5 * torch.sin(p * 9.0 + phase)
+        lam = (0.35 + 0.65 * (n * light).sum(-1).clamp(0, 1))[:, None]
+        rgb = (tex * lam).clamp(0, 1)
+        return rgb, hit.float()[:, None]
+
+    def _train_images(self):
+        """The training views as RGBA images in device memory, as SubjectLoader holds its images
+        (nerf_synthetic.py:133-146): the analytic shading evaluated once per pixel instead of once per fetched ray."""
+        if getattr(self, "_images", None) is None:
+            ys, xs = torch.meshgrid(torch.arange(self.H, device=self.device),
+                                    torch.arange(self.W, device=self.device), indexing="ij")
+            x, y = xs.reshape(-1).float(), ys.reshape(-1).float()
+            views = []
+            for c2w in self.train_c2w:
+                o, d = self._rays(c2w[None].expand(x.shape[0], 3, 4), x, y)
+                views.append(torch.cat(self._shade(o, d), dim=-1).view(self.H, self.W, 4))
+            self._images = torch.stack(views)
+        return self._images
+
+    def fetch(self, num_rays=None):
+        n = self.num_rays if num_rays is None else num_rays
+        img = torch.randint(0, self.train_c2w.shape[0], (n,), device=self.device, generator=self.gen)
+        xi = torch.randint(0, self.W, (n,), device=self.device, generator=self.gen)
+        yi = torch.randint(0, self.H, (n,), device=self.device, generator=self.gen)
+        o, d = self._rays(self.train_c2w[img], xi.float(), yi.float())
+        rgba = self._train_images()[img, yi, xi]            # the same numbers as shading the fetched rays
+        rgb, alpha = rgba[:, :3], rgba[:, 3:]
+        bkgd = torch.rand(3, device=self.device, generator=self.gen)     # random bkgd in training
+        return {"rays": Rays(o, d), "pixels": rgb * alpha + bkgd * (1 - alpha), "color_bkgd": bkgd}
+
+    def view(self, i):
+        ys, xs = torch.meshgrid(torch.arange(self.H, device=self.device),
+                                torch.arange(self.W, device=self.device), indexing="ij")
+        x, y = xs.reshape(-1).float(), ys.reshape(-1).float()
+        c2w = self.test_c2w[i % self.test_c2w.shape[0]][None].expand(x.shape[0], 3, 4)
+        o, d = self._rays(c2w, x, y)
+        rgb, alpha = self._shade(o, d)
+        bkgd = torch.ones(3, device=self.device)
+        return {"rays": Rays(o.view(self.H, self.W, 3), d.view(self.H, self.W, 3)),
+                "pixels": (rgb * alpha + bkgd * (1 - alpha)).view(self.H, self.W, 3), "color_bkgd": bkgd}
+
+
+class LoaderDataset:
+    """`SubjectLoader` / `SubjectLoader_Tanks` behind the three calls the Trainer makes:
+    `fetch()` = one training batch as the reference draws it (`train_dataset[randint(len)]`,
+    train_CNC_nerf_synthetic.py:305-306), `view(i)` = test image i, `update_num_rays`."""
+
+    def __init__(self, train_loader, test_loader):
+        self.train, self.test = train_loader, test_loader
+        self._gen = None
+
+    def seed_sampling(self, seed: int):
+        """Per-rank stream for the image index drawn here and for the loader's pixel draws (data parallelism:
+        without it every rank would render the same batch and the all-reduce would average N copies of one
+        gradient)."""
+        self._gen = torch.Generator().manual_seed(int(seed))
+        self.train.seed_sampling(int(seed) + 1)
+
+    def update_num_rays(self, n):
+        self.train.update_num_rays(int(n))
+
+    def fetch(self):
+        return self.train[int(torch.randint(0, len(self.train), (1,), generator=self._gen).item())]
+
+    def view(self, i):
+        return self.test[i % len(self.test)]
+
+    def __len__(self):
+        return len(self.test)

@@ -139,6 +139,32 @@ class GradBucket:
         return self.flat.numel() * self.flat.element_size()
 
 
+def fold_entropy_gradients(A: GradBucket, excluded, world: int, grads=None, other: Optional[GradBucket] = None):
+    """The data-parallel step's gradient assembly behind the all-reduce, as arithmetic on tensors of any device.  `A`
+    holds the ray-loss gradient summed over the ranks; `excluded` (a list, all in the bucket) are the parameters whose
+    gradient is NOT folded into it — the tables when their optimizer kernel steps them (it takes the mean and adds the
+    pieces itself), nobody otherwise.  Every other parameter's slice of `A` becomes  sum / world + entropy gradient:
+    one in-place division per run of `A.runs_excluding(excluded)` (nothing excluded: one run, the whole gradient part),
+    then the entropy gradient added — `grads`, one tensor or None per parameter of `A` as torch.autograd.grad returned
+    them, or the bucket `other` that a backward call accumulated them into (made from the same parameter list).  The
+    tail slots are never touched.  Returns `id(parameter) -> [(entropy gradient, None)]` for the excluded parameters the
+    entropy loss reaches: the first piece behind the bucket's view in their kernel's sum (`other`: its view)."""
+    skip = {id(p) for p in excluded}
+    runs = A.runs_excluding(excluded)
+    for lo, hi in runs:
+        A.flat[lo:hi].div_(world)
+    if other is not None:
+        for lo, hi in runs:
+            A.flat[lo:hi].add_(other.flat[lo:hi])
+        grads = other.views
+    elif grads is not None:
+        pairs = [(v, g) for p, v, g in zip(A.params, A.views, grads) if g is not None and id(p) not in skip]
+        if pairs:
+            torch._foreach_add_([v for v, _ in pairs], [g for _, g in pairs])
+    return {id(p): [(g if g.is_contiguous() else g.contiguous(), None)]
+            for p, g in zip(A.params, grads or ()) if g is not None and id(p) in skip}
+
+
 def broadcast_module_buffers(module: torch.nn.Module, names: Iterable[str], src: int = 0) -> None:
     """Keep replica state (e.g. OccGridEstimator.occs / .binaries) identical to rank `src`."""
     if not _active():

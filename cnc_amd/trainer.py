@@ -3,7 +3,7 @@
 Follows the behaviour of examples/train_CNC_nerf_synthetic.py (hyper-parameters :135-186, optimisers
 and schedules :257-297, loop :302-366, evaluation / codec :384-506), not its text: the reference
 script cannot travel to the GPU box and its datasets are not available offline, so the scene here is
-a procedural one (`SyntheticBallDataset`, same `fetch`-style interface as
+a procedural one (`cnc_amd.datasets.SyntheticBallDataset`, same `fetch`-style interface as
 examples/datasets/nerf_synthetic.py:132-239).  Flag names of the reference's argparse are kept in
 `TrainConfig`.
 
@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from . import _gradsink, _repro, _step_guard, _table_adam
 from . import dist as cdist
 from .context import CNC_context_models
+from .datasets import LoaderDataset, SyntheticBallDataset  # noqa: F401  (re-exported: bench.py and the tests import them from here)
 from .field import NGPRadianceField_mygrid_2D3D
 from .nerfacc import OccGridEstimator
 from .render import Rays, render_image_with_occgrid, render_image_with_occgrid_test, set_random_seed
@@ -87,102 +88,6 @@ class TrainConfig:
     symbols_per_lane: Optional[int] = None     # of the device coder; None = cnc_amd.context.DEVICE_CODER_SYMBOLS_PER_LANE
 
 
-class SyntheticBallDataset:
-    """Procedural scene: an opaque textured ball of radius 0.8 in front of a white background,
-    seen from cameras on a sphere of radius 4 (focal as nerf_synthetic, camera_angle_x=0.6911).
-    `fetch(num_rays)` returns random training pixels like SubjectLoader.fetch_data in training mode
-    (nerf_synthetic.py:164-239); `view(i)` returns a whole test image."""
-
-    RADIUS = 0.8
-
-    def __init__(self, image_size=200, n_train_views=100, device="cuda", seed=0):
-        self.H = self.W = image_size
-        self.focal = 0.5 * image_size / math.tan(0.5 * 0.6911)
-        self.device = torch.device(device)
-        self.gen = torch.Generator(device=self.device).manual_seed(seed)
-        g = torch.Generator().manual_seed(1234)
-        self.train_c2w = self._poses(n_train_views, g).to(self.device)
-        self.test_c2w = self._poses(16, torch.Generator().manual_seed(4321)).to(self.device)
-        self.num_rays = 1024
-
-    @staticmethod
-    def _poses(n, g):
-        az = torch.rand(n, generator=g) * 2 * math.pi
-        el = (torch.rand(n, generator=g) - 0.3) * 1.2
-        eye = 4.0 * torch.stack([torch.cos(el) * torch.cos(az), torch.cos(el) * torch.sin(az), torch.sin(el)], -1)
-        fwd = -eye / eye.norm(dim=-1, keepdim=True)
-        up0 = torch.tensor([0.0, 0.0, 1.0]).expand_as(fwd)
-        right = torch.linalg.cross(fwd, up0)
-        right = right / right.norm(dim=-1, keepdim=True)
-        up = torch.linalg.cross(right, fwd)
-        return torch.cat([torch.stack([right, up, -fwd], dim=-1), eye[..., None]], dim=-1)   # [n,3,4]
-
-    def update_num_rays(self, n):
-        self.num_rays = int(n)
-
-    def _rays(self, c2w, x, y):
-        cam = torch.stack([(x - self.W / 2 + 0.5) / self.focal, -(y - self.H / 2 + 0.5) / self.focal,
-                           -torch.ones_like(x)], dim=-1)
-        d = (cam[:, None, :] * c2w[:, :3, :3]).sum(-1)
-        d = d / torch.linalg.norm(d, dim=-1, keepdim=True)
-        o = c2w[:, :3, 3].expand_as(d)
-        return o.contiguous(), d.contiguous()
-
-    def _shade(self, o, d):
-        """Ground-truth pixel colour and alpha: first hit of the ball."""
-        b = (o * d).sum(-1)
-        c = (o * o).sum(-1) - self.RADIUS ** 2
-        disc = b * b - c
-        hit = disc > 0
-        t = -b - torch.sqrt(disc.clamp_min(0))
-        p = o + d * t[:, None]
-        n = p / self.RADIUS
-        if getattr(self, "_shade_consts", None) is None or self._shade_consts[0].device != p.device:
-            self._shade_consts = (torch.tensor([0.0, 2.0, 4.0], device=p.device),
-                                  torch.tensor([0.3, 0.5, 0.8], device=p.device))
-        phase, light = self._shade_consts
-        tex = 0.5 + 0.5 * torch.sin(p * 9.0 + phase)
-        lam = (0.35 + 0.65 * (n * light).sum(-1).clamp(0, 1))[:, None]
-        rgb = (tex * lam).clamp(0, 1)
-        return rgb, hit.float()[:, None]
-
-    def _train_images(self):
-        """The training views as RGBA images in device memory, as SubjectLoader holds its images
-        (nerf_synthetic.py:133-146): the analytic shading evaluated once per pixel instead of once per fetched ray."""
-        if getattr(self, "_images", None) is None:
-            ys, xs = torch.meshgrid(torch.arange(self.H, device=self.device),
-                                    torch.arange(self.W, device=self.device), indexing="ij")
-            x, y = xs.reshape(-1).float(), ys.reshape(-1).float()
-            views = []
-            for c2w in self.train_c2w:
-                o, d = self._rays(c2w[None].expand(x.shape[0], 3, 4), x, y)
-                views.append(torch.cat(self._shade(o, d), dim=-1).view(self.H, self.W, 4))
-            self._images = torch.stack(views)
-        return self._images
-
-    def fetch(self, num_rays=None):
-        n = self.num_rays if num_rays is None else num_rays
-        img = torch.randint(0, self.train_c2w.shape[0], (n,), device=self.device, generator=self.gen)
-        xi = torch.randint(0, self.W, (n,), device=self.device, generator=self.gen)
-        yi = torch.randint(0, self.H, (n,), device=self.device, generator=self.gen)
-        o, d = self._rays(self.train_c2w[img], xi.float(), yi.float())
-        rgba = self._train_images()[img, yi, xi]            # the same numbers as shading the fetched rays
-        rgb, alpha = rgba[:, :3], rgba[:, 3:]
-        bkgd = torch.rand(3, device=self.device, generator=self.gen)     # random bkgd in training
-        return {"rays": Rays(o, d), "pixels": rgb * alpha + bkgd * (1 - alpha), "color_bkgd": bkgd}
-
-    def view(self, i):
-        ys, xs = torch.meshgrid(torch.arange(self.H, device=self.device),
-                                torch.arange(self.W, device=self.device), indexing="ij")
-        x, y = xs.reshape(-1).float(), ys.reshape(-1).float()
-        c2w = self.test_c2w[i % self.test_c2w.shape[0]][None].expand(x.shape[0], 3, 4)
-        o, d = self._rays(c2w, x, y)
-        rgb, alpha = self._shade(o, d)
-        bkgd = torch.ones(3, device=self.device)
-        return {"rays": Rays(o.view(self.H, self.W, 3), d.view(self.H, self.W, 3)),
-                "pixels": (rgb * alpha + bkgd * (1 - alpha)).view(self.H, self.W, 3), "color_bkgd": bkgd}
-
-
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
     """Uniform `digits`-bit quantisation of each MLP tensor (train_CNC_nerf_synthetic.py:30-50).
     Returns (quantised MB, original MB, quantised state)."""
@@ -208,75 +113,90 @@ def get_binary_vxl_size(binary_vxl):
     return Pg, bits.item() / 8.0 / 1024 / 1024, n
 
 
-class LoaderDataset:
-    """`SubjectLoader` / `SubjectLoader_Tanks` (cnc_amd.datasets) behind the three calls the Trainer makes:
-    `fetch()` = one training batch as the reference draws it (`train_dataset[randint(len)]`,
-    train_CNC_nerf_synthetic.py:305-306), `view(i)` = test image i, `update_num_rays`."""
-
-    def __init__(self, train_loader, test_loader):
-        self.train, self.test = train_loader, test_loader
-        self._gen = None
-
-    def seed_sampling(self, seed: int):
-        """Per-rank stream for the image index drawn here and for the loader's pixel draws (data parallelism:
-        without it every rank would render the same batch and the all-reduce would average N copies of one
-        gradient)."""
-        self._gen = torch.Generator().manual_seed(int(seed))
-        self.train.seed_sampling(int(seed) + 1)
-
-    def update_num_rays(self, n):
-        self.train.update_num_rays(int(n))
-
-    def fetch(self):
-        return self.train[int(torch.randint(0, len(self.train), (1,), generator=self._gen).item())]
-
-    def view(self, i):
-        return self.test[i % len(self.test)]
-
-    def __len__(self):
-        return len(self.test)
-
-
 _STEP_STREAMS = {}
 
 
 def reserve_streams(device):
-    """The two side streams of the training step on `device` (entropy pass; its planes' half), created — and used once —
-    NOW, one pair per process and device.  Why there is such a call: the HIP runtime deals a process's streams onto four
-    hardware queues in the order they first appear, the null stream included, and two streams on one queue run one after
-    the other.  A Trainer made first gets a queue per stream (null, entropy, planes: three of four); made after other
-    code has used streams of its own (the encoder backward's two side streams in bench.py's frame loop) its planes' stream
-    landed on the null stream's queue and the step took 9.7 ms instead of 7.5.  A process that trains creates its Trainer
-    first anyway; one that does other GPU work first calls this at start-up."""
+    """The three side streams of the training step on `device` (entropy pass; its planes' half; the look-ahead batch and
+    march), created — and used once — NOW, one set per process and device, at the default priority.  Why there is such a
+    call: the HIP runtime deals a process's streams onto four hardware queues in the order they first appear, the null
+    stream included, and two streams on one queue run one after the other.  A Trainer made first gets a queue per stream
+    (null, entropy, planes, look-ahead: four of four); made after other code has used streams of its own (the encoder
+    backward's two side streams in bench.py's frame loop) its planes' stream landed on the null stream's queue and the step
+    took 9.7 ms instead of 7.5.  A process that trains creates its Trainer first anyway; one that does other GPU work first
+    calls this at start-up."""
     dev = torch.device(device)
     if dev.type != "cuda":
         return None
     key = dev.index if dev.index is not None else torch.cuda.current_device()
     dev = torch.device("cuda", key)
     if key not in _STEP_STREAMS:
-        prio = int(os.environ.get("CNC_CTX_STREAM_PRIORITY", "0"))
-        pair = [torch.cuda.Stream(device=dev, priority=prio) for _ in range(3)]      # entropy pass, its planes' half, look-ahead
-        for st in pair:
+        streams = [torch.cuda.Stream(device=dev) for _ in range(3)]      # entropy pass, its planes' half, look-ahead
+        for st in streams:
             with torch.cuda.stream(st):
                 torch.zeros(1, device=dev)
-        _STEP_STREAMS[key] = pair
+        _STEP_STREAMS[key] = streams
     return _STEP_STREAMS[key]
+
+
+def _run_with_modes(grad_mode, autocast_on, autocast_dtype, device_type, fn, args):
+    with torch.set_grad_enabled(grad_mode), torch.autocast(device_type, dtype=autocast_dtype, enabled=autocast_on):
+        return fn(*args)
+
+
+def _settle(future, stream, behind) -> None:
+    """A worker may still be running behind an exception that is on its way up: wait for it (its own error, if any, is
+    secondary) and order `stream` after what it enqueued on the stream `behind` (None: it had no stream of its own)."""
+    if future is None:
+        return
+    try:
+        future.result()
+    except BaseException:
+        pass
+    if behind is not None:
+        stream.wait_stream(behind)
+
+
+class _StreamMismatchWarningOff:
+    """`with` block that holds PyTorch's accumulate-grad stream-mismatch warning off: leaves are accumulated on the main
+    stream, the entropy pass produces its gradients on the side stream — intended.  The switch is process-global, so it is
+    held for the duration of a train_step only and put back to what the caller had (private getter when there is one).  One
+    object per Trainer, entered once per step; `enabled=False`: does nothing."""
+
+    def __init__(self, enabled: bool):
+        self._set = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None) if enabled else None
+        self._before = True
+
+    def __enter__(self):
+        if self._set is not None:
+            self._before = bool(getattr(torch._C, "_warn_on_accumulate_grad_stream_mismatch", lambda: True)())
+            self._set(False)
+
+    def __exit__(self, *exc):
+        if self._set is not None:
+            self._set(self._before)
+        return False
 
 
 class Trainer:
     def __init__(self, cfg: TrainConfig, device="cuda", dataset=None):
-        self.cfg = cfg
+        """Built in dependency order: device, models and dataset, the guard's decision, optimizers, gradient sinks, the
+        planes' graph, streams, buckets — and then ONE look at whether the tables' Adam kernel takes what this Trainer's
+        steps will hand it (`_check_table_adam`).  Construction works on a CPU device (evaluation, the codec); a training
+        step does not."""
+        self.cfg = c = cfg
         # world > 1: join the process group (RCCL; gloo under CNC_DIST_BACKEND) and take this rank's GPU
         self.rank, self.local_rank, self.world = cdist.init()
         self.device = torch.device(device)
         self.dp = self.world > 1 or cdist.forced()       # data-parallel control flow (forced: a one-rank group, test hook)
         self._inv_world = float(torch.tensor(1.0, dtype=torch.float32) / self.world)     # 1 / world as a float32
-        if self.dp and self.device.type == "cuda":
+        on_gpu = self.device.type == "cuda"
+        if self.dp and on_gpu:
             self.device = torch.device("cuda", cdist.local_device_index())
-        elif self.device.type == "cuda" and self.device.index is None:
+        elif on_gpu and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())     # the worker threads select it by index
-        set_random_seed(cfg.seed)
-        c = cfg
+        set_random_seed(c.seed)
+        # ---- models and dataset
         aabb = torch.tensor(c.aabb, device=self.device)
         self.estimator = OccGridEstimator(roi_aabb=aabb, resolution=c.grid_resolution, levels=c.grid_nlvl).to(self.device)
         self.field = NGPRadianceField_mygrid_2D3D(
@@ -290,53 +210,46 @@ class Trainer:
         self.dataset = dataset if dataset is not None else \
             SyntheticBallDataset(c.image_size, device=self.device, seed=c.seed + 1000 * self.rank)
         self.dataset.update_num_rays(c.init_batch_size)
-
-        self.build_optimizers()
-        self.loss_scale = 2.0 ** 10          # GradScaler(2**10), never unscaled (train:211,361-362)
-
-        # the planes' half of the entropy pass as one captured graph per refresh interval (CNC_PLANES_GRAPH=0: op by op)
-        self.planes_graph = None
-        # ... in the data-parallel step as well (CNC_PLANES_GRAPH_DP=0: the joint entropy pass there), so that the step a
-        # multi-GPU run measures is the single-GPU step + the exchange
-        self.planes_graph_dp = os.environ.get("CNC_PLANES_GRAPH_DP", "1") == "1"
-        self._pool_graph = None
-        self._planes_replayed = False
-        self._fwd_enqueued = None
+        # ---- the guarded step's decision, taken here and nowhere else: `_make_optimizers` builds the verdict's buffer from
+        # it, the gradient bucket sizes its tail from it
+        self._guarded = bool(getattr(c, "guarded_step", False)) or os.environ.get("CNC_GUARDED_STEP", "0") == "1"
         # The reproducible mode fixes what is not a kernel by taking the schedule that has nothing to fix: the entropy pass
         # on the main stream from the main thread, behind the render forward (one order of random draws on the default
         # generator, ONE backward call whose engine adds the gradient pieces in the graph's order), no captured graph.
-        self.reproducible = bool(cfg.reproducible)
-        if self.device.type == "cuda" and os.environ.get("CNC_PLANES_GRAPH", "1") == "1" and not self.reproducible:
+        self.reproducible = bool(c.reproducible)
+        # ---- optimizers; per-step gradient sinks (cnc_amd._gradsink): the encoder scatters and the context heads' weight
+        # gradients add into ONE buffer per parameter and pass instead of a fresh zero-filled tensor per call
+        # (CNC_GRAD_SINK=0: off)
+        self._make_optimizers()
+        self.loss_scale = 2.0 ** 10          # GradScaler(2**10), never unscaled (train:211,361-362)
+        self._make_sinks()
+        # ---- the planes' half of the entropy pass as one captured graph per refresh interval (CNC_PLANES_GRAPH=0: op by op)
+        self.planes_graph = None
+        if on_gpu and os.environ.get("CNC_PLANES_GRAPH", "1") == "1" and not self.reproducible:
             from ._planes_graph import PlanesGraph
             self.planes_graph = PlanesGraph(self)
-        self.prefetch = os.environ.get("CNC_PREFETCH_BATCH", "1") == "1"
-        self._next_data = None
-        self._next_ready = None
-        # the next batch's draw and march on a stream of their own (CNC_PREMARCH=0: the batch only, on the main stream)
-        self.premarch = os.environ.get("CNC_PREMARCH", "1") == "1"
-        self.ahead_stream = None
-        if self.device.type == "cuda" and self.premarch:
-            self.ahead_stream = reserve_streams(self.device)[2]
-        # The entropy pass (context forward and backward) runs on its own stream next to the render pass — see train_step
-        self.ctx_stream = None
-        if self.device.type == "cuda" and os.environ.get("CNC_CTX_STREAM", "1") == "1" and not self.reproducible:
-            self.ctx_stream = reserve_streams(self.device)[0]
-        # ... and its planes' half on a third one (CNC_CTX_STREAM_2D=0: both halves on the side stream, one after the other)
-        self.ctx_stream_2D = None
-        if self.ctx_stream is not None and os.environ.get("CNC_CTX_STREAM_2D", "1") == "1":
-            self.ctx_stream_2D = reserve_streams(self.device)[1]
-        # leaves are accumulated on the main stream, the entropy pass produces its gradients on the side stream: intended.
-        # The switch is process-global, so it is held only for the duration of a train_step (see there).
-        self._warn_switch = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None) \
-            if self.ctx_stream is not None else None
+        # ... in the data-parallel step as well (CNC_PLANES_GRAPH_DP=0: the joint entropy pass there), so that the step a
+        # multi-GPU run measures is the single-GPU step + the exchange
+        self.planes_graph_dp = os.environ.get("CNC_PLANES_GRAPH_DP", "1") == "1"
+        self._planes_replayed = False
+        # ---- streams and host threads.  The next batch is drawn at the end of a step (`prefetch`), with its march
+        # (`premarch`), on a stream of their own (`premarch = False`: the batch only, on the main stream)
+        self.prefetch = self.premarch = True
+        self._next_data = self._next_ready = self._fwd_enqueued = None
+        streams = reserve_streams(self.device) if on_gpu else None
+        self.ahead_stream = streams[2] if on_gpu else None
+        # The entropy pass (context forward and backward) runs on its own stream next to the render pass — see train_step —
+        # and its planes' half on a third one (`ctx_stream_2D = None`: both halves on the side stream, one after the other)
+        side = on_gpu and os.environ.get("CNC_CTX_STREAM", "1") == "1" and not self.reproducible
+        self.ctx_stream = streams[0] if side else None
+        self.ctx_stream_2D = streams[1] if side else None
+        self._warning_off = _StreamMismatchWarningOff(enabled=side)
         # ... and from its own host thread, started before the render pass (`_context_pass`): the two passes are ~300
         # launches each and the step is otherwise bound by the host issuing them one after the other.  Off = the
         # sequential schedule, which keeps the reference's order of random draws (the trajectory goldens need it).
-        self.ctx_thread = self.ctx_stream is not None and os.environ.get("CNC_CTX_THREAD", "1") == "1"
-        self._pool = None
-        # per-step gradient sinks (cnc_amd._gradsink): the encoder scatters and the context heads' weight gradients add
-        # into ONE buffer per parameter and pass instead of a fresh zero-filled tensor per call (CNC_GRAD_SINK=0: off)
-        self.build_sinks()
+        self.ctx_thread = side and os.environ.get("CNC_CTX_THREAD", "1") == "1"
+        self._workers = {}                  # name -> one-thread pool ("context", "planes"), made at first use
+        # ---- data parallel: the gradient buckets, the lagged sample count, the shared window draw
         self.bucket = None
         self.time_comm = False          # bench hook: HIP events around the wait for the gradient all-reduce
         self._comm_events = []
@@ -345,10 +258,10 @@ class Trainer:
             # ray-loss gradients (all-reduced) + ONE tail slot: this rank's sample count, so that the sum over the
             # ranks arrives with the gradients instead of through a blocking collective in the middle of the step
             # (the guarded step: one more, the range guard's trip of any rank as +inf in the sum — `_step_guard`)
-            self.bucket = cdist.GradBucket(plist, tail=2 if self.step_guard is not None else 1)
+            self.bucket = cdist.GradBucket(plist, tail=2 if self._guarded else 1)
             self.bucket_ctx = cdist.GradBucket(plist)      # entropy-loss gradients (replica-identical)
             self._count_host = torch.zeros(1, dtype=torch.float32)
-            if self.device.type == "cuda":
+            if on_gpu:
                 self._count_host = self._count_host.pin_memory()
             self._count_pending = None                     # (event, num_rays of the step the count belongs to)
             # how often the replicas had to be re-aligned (cdist.resync_parameters, every `step_update` steps)
@@ -366,12 +279,13 @@ class Trainer:
                 return r
             self._ctx_rand = None
             self.context.rand_like = synced_rand_like
-        self._check_table_adam()            # (again: the sinks, the planes' graph and the buckets exist now)
+        self._check_table_adam()
 
     def build_context(self):
         """The context models of this configuration (train:221-241).  Their vertex tables draw from the CPU
         generator (randperm of the dense levels, utils_bpp_acc.py:312), so a caller that wants a particular
-        draw seeds, calls this and assigns the result to `self.context` (then `build_optimizers()`)."""
+        draw seeds, calls this and assigns the result to `self.context` — then `build_optimizers()` and `build_sinks()`,
+        in that order; each of the two looks at the new models (`_check_table_adam`)."""
         c = self.cfg
         return CNC_context_models(
             num_dim=3, resolutions_list=c.resolutions_list, resolutions_list_2D=c.resolutions_list_2D,
@@ -384,8 +298,12 @@ class Trainer:
 
     def build_sinks(self):
         """The step's gradient sinks for the CURRENT field and context models (a caller that replaces `self.context` —
-        see `build_context` — calls this and `build_optimizers()` again: the entropy pass's sink holds one slot per
+        see `build_context` — calls `build_optimizers()` and this again: the entropy pass's sink holds one slot per
         context-head parameter, and the planes' graph refuses to record without them)."""
+        self._make_sinks()
+        self._check_table_adam()
+
+    def _make_sinks(self):
         self.sink_render = self.sink_ctx = None
         if self.device.type == "cuda" and os.environ.get("CNC_GRAD_SINK", "1") == "1":
             tables = [e.params for e in self.field.mlp_base._encoders()]
@@ -393,10 +311,14 @@ class Trainer:
             self.sink_ctx = _gradsink.GradSink(tables, list(self.context.parameters()))
 
     def build_optimizers(self):
-        """Both Adam groups and their chained schedules (train:257-297)."""
+        """Both Adam groups and their chained schedules (train:257-297), for the CURRENT field and context models."""
+        self._make_optimizers()
+        self._check_table_adam()
+
+    def _make_optimizers(self):
         c = self.cfg
         # one kernel per parameter list instead of the ~9 passes of the foreach implementation (0.8 -> 0.2 ms per step)
-        one_pass = self.device.type == "cuda" and os.environ.get("CNC_FUSED_ADAM", "1") == "1"
+        one_pass = self.device.type == "cuda"
         # the four tables as a parameter group of their own (same hyper-parameters, same schedule): what `_table_adam` steps
         tables = [e.params for e in self.field.mlp_base._encoders()]
         tids = {id(p) for p in tables}
@@ -412,13 +334,12 @@ class Trainer:
         if one_pass and os.environ.get("CNC_TABLE_ADAM", "1") == "1" and all(t.numel() % 4 == 0 for t in tables):
             self.table_adam = _table_adam.TableAdam(self.opt, tables, self.field.mlp_base._encoders())
         self.fused_table_adam = self.table_adam is not None
-        self._check_table_adam()
         # the guarded step: the verdict's buffer, seeded with the step count of the optimizer as it stands
         self.step_guard = None
-        if bool(getattr(c, "guarded_step", False)) or os.environ.get("CNC_GUARDED_STEP", "0") == "1":
+        if self._guarded:
             if not one_pass:
-                raise RuntimeError("the guarded step needs the fused Adam (a GPU, CNC_FUSED_ADAM=1): the library's other "
-                                   "forms take no device-side `found_inf`")
+                raise RuntimeError("the guarded step needs a GPU: it hands the verdict to the library's fused Adam, the only "
+                                   "form that takes a device-side `found_inf`")
             b1, b2 = self.opt.param_groups[1]["betas"]
             self.step_guard = _step_guard.StepGuard(self.device, b1, b2, self._table_steps_taken())
 
@@ -434,28 +355,27 @@ class Trainer:
         return int(float(st["step"])) if len(st) else 0
 
     def _check_table_adam(self) -> None:
-        """Once, not in the middle of a step: what cnc_table_adam would refuse of the pieces this Trainer's schedules can
-        hand it — then the steps take the `.grad` path (`fused_table_adam = False`), with one warning."""
+        """Once per construction or rebuild, not in the middle of a step: what cnc_table_adam would refuse of the pieces this
+        Trainer's schedules can hand it — then the steps take the `.grad` path (`fused_table_adam = False`), with one
+        warning."""
         ta = self.table_adam
         if ta is None or not self.fused_table_adam:
             return
         # the one piece that is not table-sized: the 3-D table's finest level out of the planes' graph (_planes_graph.capture)
         off3 = getattr(self.context, "_off3_host", None)
         rows = {} if off3 is None or len(off3) < 2 else {id(ta.tables[0]): [(int(off3[-2]), int(off3[-1]))]}
-        # the most pieces a step of THIS Trainer hands over for one table (what is not built yet counts as present).  Single
-        # process: `.grad`, the render sink, the entropy sink, the planes' graph; data parallel: `.grad` (the bucket: the
-        # render sink is flushed into it), the entropy pass's returned gradient, the entropy sink, the planes' graph
-        bucket = getattr(self, "bucket", None)
-        sinks = [getattr(self, "sink_render", True) is not None, getattr(self, "sink_ctx", True) is not None]
-        graph = getattr(self, "planes_graph", True) is not None
+        # the most pieces a step of THIS Trainer hands over for one table.  Single process: `.grad`, the render sink, the
+        # entropy sink, the planes' graph; data parallel: `.grad` (the bucket: the render sink is flushed into it), the
+        # entropy pass's returned gradient, the entropy sink, the planes' graph
+        graph = self.planes_graph is not None
         if self.dp:
-            pieces = 1 + 1 + sinks[1] + (graph and getattr(self, "planes_graph_dp", True))
+            pieces = 1 + 1 + (self.sink_ctx is not None) + (graph and self.planes_graph_dp)
         else:
-            pieces = 1 + sinks[0] + sinks[1] + graph
+            pieces = 1 + (self.sink_render is not None) + (self.sink_ctx is not None) + graph
         why = ta.refusal(rows, max_pieces=pieces)
-        if why is None and bucket is not None:
+        if why is None and self.bucket is not None:
             tids = {id(p) for p in ta.tables}
-            for b in (bucket, self.bucket_ctx):
+            for b in (self.bucket, self.bucket_ctx):
                 if any(v.data_ptr() % 16 for p, v in zip(b.params, b.views) if id(p) in tids):
                     why = "a table's slice of the gradient bucket is not 16-byte aligned"
         if why is not None:
@@ -474,13 +394,25 @@ class Trainer:
         if self.step_guard is not None:
             self.step_guard.seed(self._table_steps_taken())        # the running products b^t restart from the loaded count
 
-    # -------------------------------------------------------------------------------- training
-    def _context_pass_worker(self, step, fork, params, grad_mode, autocast):
-        """`_context_pass` on the worker thread with the submitting thread's grad and autocast modes (both are
-        thread-local in PyTorch and a fresh thread starts from the defaults)."""
-        enabled, dtype = autocast
-        with torch.set_grad_enabled(grad_mode), torch.autocast(self.device.type, dtype=dtype, enabled=enabled):
-            return self._context_pass(step, fork, params)
+    # -------------------------------------------------------------------------------- training: the entropy pass
+    def _submit(self, worker: str, fn, *args):
+        """`fn(*args)` on the one-thread pool `worker` (made at first use) under the SUBMITTING thread's grad and autocast
+        modes: both are thread-local in PyTorch and a pool thread starts from the defaults."""
+        pool = self._workers.get(worker)
+        if pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            pool = self._workers[worker] = ThreadPoolExecutor(max_workers=1, thread_name_prefix="cnc-" + worker)
+        kind = self.device.type
+        return pool.submit(_run_with_modes, torch.is_grad_enabled(), torch.is_autocast_enabled(kind),
+                           torch.get_autocast_dtype(kind), kind, fn, args)
+
+    def _entropy_forward(self, step: int, stream_2D=None, planes=None):
+        """The entropy loss forward with the entropy pass's sink active on the calling thread -> (bits per parameter, MB)."""
+        e = self.field.mlp_base
+        with _gradsink.activate(self.sink_ctx):
+            return self.context.forward_binary_vxl_mixPg_3D2D(
+                e.encoding_xyz, e.encoding_xy, e.encoding_xz, e.encoding_yz, self.estimator.binaries,
+                sample_num=None, step=step, sync_MB=False, stream_2D=stream_2D, planes=planes)
 
     def _planes_thread_step(self, step: int, params) -> bool:
         """The planes' half of this step's entropy pass runs apart from the 3-D half (its own root, its own thread)."""
@@ -498,42 +430,23 @@ class Trainer:
         """... as a replay of the recorded graph: every such step but the occupancy-refresh ones."""
         return self._planes_thread_step(step, params) and step % self.cfg.step_update != 0
 
-    def _on_planes_thread(self, fn, *args):
-        """Submit `fn(*args)` to the planes' thread under the SUBMITTING thread's grad and autocast modes (thread-local in
-        PyTorch; a pool thread starts from the defaults)."""
-        if self._pool_graph is None:
-            from concurrent.futures import ThreadPoolExecutor
-            self._pool_graph = ThreadPoolExecutor(max_workers=1, thread_name_prefix="cnc-planes")
-        grad_mode = torch.is_grad_enabled()
-        enabled, dtype = torch.is_autocast_enabled(self.device.type), torch.get_autocast_dtype(self.device.type)
-
-        def job():
-            with torch.set_grad_enabled(grad_mode), torch.autocast(self.device.type, dtype=dtype, enabled=enabled):
-                return fn(*args)
-        return self._pool_graph.submit(job)
-
-    def _planes_refresh_job(self, after, step: int) -> None:
-        """On the planes' thread, an occupancy-refresh step: rebuild what the planes' half is built on (vote plan, projections,
-        vertex lists: host round trips on the planes' stream only) and run that half op by op — next to the 3-D half, which
-        needs none of it, instead of in front of it on one thread (the entropy pass's thread was the long pole of a refresh
-        step: 14 ms against 7.5; 12 this way).  The graph for the steps that follow is recorded by the next step, in front
-        of its fork: recording it here, behind this job, was built too — the 2.5 ms of host time it takes moved from the next
-        step into this one (whose long pole is this thread), the sum did not change."""
-        torch.cuda.set_device(self.device)
-        e = self.field.mlp_base
-        with torch.cuda.stream(self.ctx_stream_2D), _gradsink.activate(self.sink_ctx):
-            self.ctx_stream_2D.wait_event(after)
-            self.context.refresh_planes(self.estimator.binaries, step, e.encoding_xy.params)
-            if self.planes_graph.ready():          # the grid did not change: the recorded graph still stands
-                self.planes_graph.replay()
-            else:
-                self.planes_graph.run_eager()
-
-    def _replay_planes(self, after) -> None:
-        """On the planes' thread: the graph launch on the planes' stream, ordered after the event `after`."""
+    def _planes_job(self, after, step: int, refresh: bool) -> None:
+        """On the planes' thread: the planes' half on the planes' stream, ordered after the event `after` — one graph launch.
+        On an occupancy-refresh step (`refresh`) first rebuild what that half is built on (vote plan, projections, vertex
+        lists: host round trips on the planes' stream only) and, unless the grid did not change and the recorded graph still
+        stands, run it op by op — next to the 3-D half, which needs none of it, instead of in front of it on one thread (the
+        entropy pass's thread was the long pole of a refresh step: 14 ms against 7.5; 12 this way).  The graph for the steps
+        that follow is recorded by the next step, in front of its fork: recording it here, behind this job, was built too —
+        the 2.5 ms of host time it takes moved from the next step into this one (whose long pole is this thread), the sum did
+        not change."""
         torch.cuda.set_device(self.device)
         with torch.cuda.stream(self.ctx_stream_2D), _gradsink.activate(self.sink_ctx):
             self.ctx_stream_2D.wait_event(after)
+            if refresh:
+                self.context.refresh_planes(self.estimator.binaries, step, self.field.mlp_base.encoding_xy.params)
+                if not self.planes_graph.ready():
+                    self.planes_graph.run_eager()
+                    return
             self.planes_graph.replay()
 
     def _ensure_planes_graph(self, step: int, params) -> None:
@@ -560,24 +473,21 @@ class Trainer:
         Returns (bits_per_param, estimated MB, event that marks the end of the pass, gradients or None)."""
         c, side = self.cfg, self.ctx_stream
         torch.cuda.set_device(self.device)
-        e = self.field.mlp_base
         side.wait_event(fork)
-        with torch.cuda.stream(side), _gradsink.activate(self.sink_ctx):
-            # The planes' half as ONE graph launch (cnc_amd._planes_graph): between occupancy refreshes, single-process
-            # steps (the data-parallel step wants the gradients returned).  Captured at the first step after a refresh.
-            pg, planes, replay = self.planes_graph, None, None
+        with torch.cuda.stream(side):
+            # The planes' half as ONE graph launch (cnc_amd._planes_graph), between occupancy refreshes.  Captured at the
+            # first step after a refresh (by train_step already when this is the worker thread).
+            pg, planes, job = self.planes_graph, None, None
             self._planes_replayed = False
-            if self._planes_graph_step(step, params):
-                self._ensure_planes_graph(step, params)    # (captured by train_step already when this is the worker thread)
-            if self._planes_graph_step(step, params):      # (still: a failed capture switches the graph off)
+            self._ensure_planes_graph(step, params)
+            if self._planes_thread_step(step, params):     # (asked behind the capture: a failed one switches the graph off)
                 # The graph launch itself is ~2 ms of HOST time (the runtime enqueues the ~110 nodes one by one, outside the
-                # interpreter lock): from a thread of its own, so that this one goes straight on to the 3-D half.
-                replay = self._on_planes_thread(self._replay_planes, side.record_event())
-                planes = (None, pg.n_params)               # the bits join the totals below, behind the backward
-                self._planes_replayed = True
-            elif self._planes_thread_step(step, params):   # an occupancy-refresh step: rebuilt and run op by op over there
-                replay = self._on_planes_thread(self._planes_refresh_job, side.record_event(), step)
-                planes = (None, sum(t.params.numel() for t in e._encoders()[1:]))
+                # interpreter lock): from a thread of its own, so that this one goes straight on to the 3-D half.  An
+                # occupancy-refresh step: rebuilt and run op by op over there.
+                refresh = not self._planes_graph_step(step, params)
+                job = self._submit("planes", self._planes_job, side.record_event(), step, refresh)
+                # the bits join the totals below, behind the backward
+                planes = (None, sum(t.params.numel() for t in self.field.mlp_base._encoders()[1:]) if refresh else pg.n_params)
                 self._planes_replayed = True
             # the planes' half of the pass on a stream of its own, next to the 3-D half (both directions: autograd runs a
             # node's backward on its forward's stream)
@@ -585,9 +495,7 @@ class Trainer:
             # before the 3-D half is launched — was built and measured: 8.25 -> 8.95 ms.  The first half of the step is bound
             # by the two host threads' launches, and the extra call sits in front of the 3-D forward's.)
             try:
-                bits_per_param, mb = self.context.forward_binary_vxl_mixPg_3D2D(
-                    e.encoding_xyz, e.encoding_xy, e.encoding_xz, e.encoding_yz, self.estimator.binaries,
-                    sample_num=None, step=step, sync_MB=False, stream_2D=self.ctx_stream_2D, planes=planes)
+                bits_per_param, mb = self._entropy_forward(step, stream_2D=self.ctx_stream_2D, planes=planes)
                 # issued from the side stream: the root gradient of a backward call is created on the ambient stream and
                 # every node waits for it
                 root = c.lmbda * bits_per_param * self.loss_scale
@@ -597,43 +505,76 @@ class Trainer:
                 else:
                     grads = torch.autograd.grad(root, params, allow_unused=True)
             except BaseException:
-                # the planes' job writes the sink and the graph's static gradients: wait for it (its own error, if any, is
-                # secondary) and order this stream after what it enqueued before the error travels on
-                if replay is not None:
-                    try:
-                        replay.result()
-                    except BaseException:
-                        pass
-                    if self.ctx_stream_2D is not None:
-                        side.wait_stream(self.ctx_stream_2D)
+                # the planes' job writes the sink and the graph's static gradients: never leave it running behind the error
+                _settle(job, side, self.ctx_stream_2D)
                 raise
-            if replay is not None:
-                replay.result()                            # the graph launch has been enqueued (and did not fail)
+            if job is not None:
+                job.result()                               # the graph launch has been enqueued (and did not fail)
             if self.ctx_stream_2D is not None:
                 side.wait_stream(self.ctx_stream_2D)       # the planes' backward kernels: part of what `done` marks
             if planes is not None:                         # the reported totals: + the planes' bits (no gradient here)
-                e_ = self.field.mlp_base
-                n_all = sum(t.params.numel() for t in e_._encoders())
+                n_all = sum(t.params.numel() for t in self.field.mlp_base._encoders())
                 bits_per_param = bits_per_param.detach() + pg.step_bits / n_all
                 mb = mb + pg.step_bits * (1.0 / 8388608.0)         # / 8 / 1024 / 1024 (a power of two: same value)
             done = side.record_event()
         return bits_per_param, mb, done, grads
 
+    def _join_entropy_pass(self, result):
+        """Order the main stream after the entropy pass; its outputs were allocated on the side stream."""
+        bits_per_param, mb, done, grads = result
+        main = torch.cuda.current_stream(self.device)
+        main.wait_event(done)
+        for t in (bits_per_param, mb) + tuple(g for g in (grads or ()) if g is not None):
+            if isinstance(t, torch.Tensor):
+                t.record_stream(main)
+        return bits_per_param, mb, grads
+
+    # -------------------------------------------------------------------------------- training: the step, phase by phase
     def train_step(self, step: int, want_stats: bool = True) -> Optional[Dict[str, float]]:
         """One optimisation step.  `want_stats=False` leaves mse / psnr / bpp / embed_bits_MB out of the result
         (reading them back is a device->host sync per step; the reference only looks at them every 200 steps,
-        train:368-381) — `n_rendering_samples` and `num_rays` are always there."""
-        c = self.cfg
+        train:368-381) — `n_rendering_samples` and `num_rays` are always there.
+
+        The phases: take the batch, refresh (occupancy, range guard, broadcast), clear the sinks, start the entropy pass
+        (the threaded schedule: now; the other two: behind the render forward, `_backward_*`), render forward and loss,
+        backward and gradient assembly, the guard's verdict, update, stats.  The schedule is chosen per step from
+        `ctx_thread` / `ctx_stream` / `cfg.lmbda`."""
+        if self.device.type != "cuda":
+            raise RuntimeError(f"Trainer.train_step needs a GPU: this Trainer is on {self.device}, and the step's kernels "
+                               "have no CPU form (a CPU Trainer evaluates, encodes and decodes only)")
         if self.reproducible and not _repro.explicitly_enabled():
             with _repro.reproducible(True):         # process-wide for the step: the backward kernels run on autograd's thread
                 return self.train_step(step, want_stats)
+        c = self.cfg
         self.field.train(); self.estimator.train(); self.context.train()
         self._planes_replayed = False       # (set by this step's entropy pass if the planes' half runs apart from it)
-        # the batch: drawn at the end of the step before (`_prefetch`), while that step's backward kept the GPU busy
+        # do the tables go through their Adam kernel this step (`fused_table_adam` is settable between steps): asked once
+        tables_fused = self.table_adam is not None and self.fused_table_adam
+        data = self._take_batch()
+        self._refresh(step)
+        for sink in (self.sink_render, self.sink_ctx):      # before either pass forks off: both are ordered after this
+            if sink is not None:
+                sink.zero()
+        ctx_future = None
+        with self._warning_off:
+            try:
+                if self.ctx_thread and self.ctx_stream is not None and c.lmbda > 0:
+                    ctx_future = self._fork_entropy_pass(step)
+                return self._render_and_update(step, want_stats, data, ctx_future, tables_fused)
+            except BaseException:
+                # Never leave the worker running behind an exception: it writes `.grad` and reads the tables.  Order the main
+                # stream after whatever it enqueued, and drop the window draw that was made for it.
+                _settle(ctx_future, torch.cuda.current_stream(self.device), self.ctx_stream)
+                if self.bucket is not None:
+                    self._ctx_rand = None
+                raise
+
+    def _take_batch(self):
+        """The batch: drawn at the end of the step before (`_prefetch`), while that step's backward kept the GPU busy."""
         data, self._next_data = self._next_data, None
         if data is None:
-            data = self.dataset.fetch()
-        elif self._next_ready is not None:          # drawn on the look-ahead stream: join it, hand the tensors over
+            return self.dataset.fetch()
+        if self._next_ready is not None:          # drawn on the look-ahead stream: join it, hand the tensors over
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(self._next_ready)
             self._next_ready = None
@@ -641,6 +582,10 @@ class Trainer:
                 for t in (v if isinstance(v, tuple) else (v,)):
                     if isinstance(t, torch.Tensor) and t.is_cuda:
                         t.record_stream(cur)
+        return data
+
+    def _refresh(self, step: int) -> None:
+        c = self.cfg
         self.estimator.update_every_n_steps(
             step=step, occ_eval_fn=lambda x: self.field.query_density(x) * c.render_step_size,
             occ_thre=1e-2, n=c.step_update)
@@ -650,62 +595,36 @@ class Trainer:
             self.field.check_range_guard()
         if self.dp and step % c.step_update == 0:
             cdist.broadcast_module_buffers(self.estimator, ["occs", "binaries"])
-        ctx_future = None
-        for sink in (self.sink_render, self.sink_ctx):      # before either pass forks off: both are ordered after this
-            if sink is not None:
-                sink.zero()
-        warn_before = True
-        if self._warn_switch is not None:
-            # process-global: held for this step only and put back to what the caller had (private getter when there is one)
-            warn_before = bool(getattr(torch._C, "_warn_on_accumulate_grad_stream_mismatch", lambda: True)())
-            self._warn_switch(False)
-        try:
-            if self.ctx_thread and self.ctx_stream is not None and c.lmbda > 0:
-                # The ray loss and the entropy loss share nothing but the parameters and the occupancy grid (just
-                # updated above).  The entropy pass starts NOW, on the side stream and from a second host thread, next
-                # to the whole render pass.  What both passes read through a cache — the sign bit planes of the tables
-                # — is made current on the main stream first; gradients are cleared before either backward.  Data
-                # parallel: the worker returns its gradient instead of accumulating it (`.grad` = the bucket that is
-                # all-reduced), and the window draw that every rank must share is made and broadcast here, on the main
-                # thread.
-                for enc in self.field.mlp_base._encoders():
-                    if enc.ste_binary and enc.bitplane:
-                        enc._bit_plane(enc.params)
-                if self.bucket is None:
-                    self.opt.zero_grad(set_to_none=True)
-                    self.opt2.zero_grad(set_to_none=True)
-                else:
-                    self.bucket.zero()
-                    self.bucket.bind(force=True)
-                    self._ctx_rand = None
-                    self._ctx_rand = self.context.rand_like(self.context.utils_rand)
-                    self._ctx_rand.record_stream(self.ctx_stream)      # allocated here, read by the side stream
-                if self._pool is None:
-                    from concurrent.futures import ThreadPoolExecutor
-                    self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="cnc-context")
-                autocast = (torch.is_autocast_enabled(self.device.type), torch.get_autocast_dtype(self.device.type))
-                self._ensure_planes_graph(step, None if self.bucket is None else self.bucket.params)
-                ctx_future = self._pool.submit(self._context_pass_worker, step,
-                                               torch.cuda.current_stream(self.device).record_event(),
-                                               None if self.bucket is None else self.bucket.params,
-                                               torch.is_grad_enabled(), autocast)
-            return self._train_step_tail(step, want_stats, data, ctx_future)
-        except BaseException:
-            # Never leave the worker running behind an exception: it writes `.grad` and reads the tables.  Wait for it
-            # (its own error, if any, is secondary), order the main stream after whatever it enqueued, and drop the
-            # window draw that was made for it.
-            if ctx_future is not None:
-                try:
-                    ctx_future.result()
-                except BaseException:
-                    pass
-                torch.cuda.current_stream(self.device).wait_stream(self.ctx_stream)
-            if self.bucket is not None:
-                self._ctx_rand = None
-            raise
-        finally:
-            if self._warn_switch is not None:
-                self._warn_switch(warn_before)
+
+    def _clear_grads(self, bucket=None) -> None:
+        """Before a backward, at each schedule's own point: `.grad` = None, or (data parallel) its slice of the zeroed `bucket`."""
+        bucket = self.bucket if bucket is None else bucket
+        if bucket is None:
+            self.opt.zero_grad(set_to_none=True)
+            self.opt2.zero_grad(set_to_none=True)
+        else:
+            bucket.zero()
+            bucket.bind(force=True)
+
+    def _fork_entropy_pass(self, step: int):
+        """The threaded schedule: the entropy pass starts NOW, from a second host thread -> its future."""
+        # The ray loss and the entropy loss share nothing but the parameters and the occupancy grid (just updated): the
+        # entropy pass runs on the side stream next to the whole render pass.  What both passes read through a cache — the
+        # sign bit planes of the tables — is made current on the main stream first; gradients are cleared before either
+        # backward.  Data parallel: the worker returns its gradient instead of accumulating it (`.grad` = the bucket that is
+        # all-reduced), and the window draw that every rank must share is made and broadcast here, on the main thread.
+        for enc in self.field.mlp_base._encoders():
+            if enc.ste_binary and enc.bitplane:
+                enc._bit_plane(enc.params)
+        self._clear_grads()
+        params = None
+        if self.bucket is not None:
+            params = self.bucket.params
+            self._ctx_rand = None
+            self._ctx_rand = self.context.rand_like(self.context.utils_rand)
+            self._ctx_rand.record_stream(self.ctx_stream)      # allocated here, read by the side stream
+        self._ensure_planes_graph(step, params)
+        return self._submit("context", self._context_pass, step, torch.cuda.current_stream(self.device).record_event(), params)
 
     def _prefetch(self, step: int = -1) -> None:
         """The NEXT step's batch, drawn now: the ray count it depends on has just been set (`update_num_rays`, from this
@@ -757,24 +676,24 @@ class Trainer:
         self._count_pending = None
         self.bucket.tail[:1].fill_(float(n_samples))    # enqueued before the backward; the bucket is zeroed before this
 
-    def _train_step_tail(self, step, want_stats, data, ctx_future):
+    def _render_and_update(self, step, want_stats, data, ctx_future, tables_fused):
+        """Render forward and loss, backward and gradient assembly, verdict, update, stats."""
         c = self.cfg
         rays, pixels, bkgd = data["rays"], data["pixels"], data["color_bkgd"]
         with _gradsink.activate(self.sink_render):
             rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
                 self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
                 render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True)
-        self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event() if self.device.type == "cuda" else None
-        if self.device.type == "cuda":
-            # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
-            # fused one is asked before the poll below can switch it off)
-            ff = self.field._field_fused
-            guard_live = self.step_guard is not None and bool(ff) and self.field.fused_train \
-                and ff._buffers is not None and getattr(ff, "_train_calls", False)
-            # the fused training forward's fp16 range guard, every step and without a wait: the words of the step before have
-            # arrived by now (the sampler has synchronised the host since), this step's are sent on their way
-            self.field.poll_range_guard()
-            self.field.snapshot_range_guard()
+        self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event()
+        # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
+        # fused one is asked before the poll below can switch it off)
+        sg, ff = self.step_guard, self.field._field_fused
+        guard_live = sg is not None and bool(ff) and self.field.fused_train \
+            and ff._buffers is not None and getattr(ff, "_train_calls", False)
+        # the fused training forward's fp16 range guard, every step and without a wait: the words of the step before have
+        # arrived by now (the sampler has synchronised the host since), this step's are sent on their way
+        self.field.poll_range_guard()
+        self.field.snapshot_range_guard()
         if not self.dp:
             if n_samples == 0:
                 if ctx_future is not None:
@@ -785,170 +704,150 @@ class Trainer:
         # world > 1: no rank leaves the step (the collective below must be entered by everyone; a rank without samples
         # adds a zero ray gradient), and the ray budget follows the all-reduced count of the step before
         mse = F.mse_loss(rgb, pixels)
-        bpp, mb = 0.0, 0.0
-        e = self.field.mlp_base
-        ctx_args = (e.encoding_xyz, e.encoding_xy, e.encoding_xz, e.encoding_yz, self.estimator.binaries)
-        main = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
-
-        def join(result):
-            """Order the main stream after the entropy pass; its outputs were allocated on the side stream."""
-            bits_per_param, mb_, done, grads = result
-            main.wait_event(done)
-            for t in (bits_per_param, mb_) + tuple(g for g in (grads or ()) if g is not None):
-                if isinstance(t, torch.Tensor):
-                    t.record_stream(main)
-            return bits_per_param, mb_, grads
-
-        table_pieces = None
-        sg = self.step_guard
-        range_guard = (ff._buffers["guard"], self.field._guard_seen, ff._pack_id) if sg is not None and guard_live else None
+        range_guard = (ff._buffers["guard"], self.field._guard_seen, ff._pack_id) if guard_live else None
         if self.bucket is None:
-            if ctx_future is not None:
-                (mse * self.loss_scale).backward()
-                self._prefetch(step)
-                bpp, mb, _ = join(ctx_future.result())
-            elif self.ctx_stream is not None and c.lmbda > 0 and mse.requires_grad:
-                # The sequential schedule of the same idea (one host thread; the reference's order of random draws):
-                #   render backward (main stream: few launches, GPU-heavy)
-                #   || context forward + context backward (side stream: ~250 launches, host-bound forward)
-                # The side stream forks BEFORE the render backward is enqueued; its host-side syncs (window bounds,
-                # nonzero) wait for the side stream only.
-                self.opt.zero_grad(set_to_none=True)
-                self.opt2.zero_grad(set_to_none=True)
-                fork = main.record_event()
-                (mse * self.loss_scale).backward()
-                bpp, mb, _ = join(self._context_pass(step, fork))
-            else:
-                loss = mse
-                if c.lmbda > 0:
-                    with _gradsink.activate(self.sink_ctx):
-                        bpp, mb = self.context.forward_binary_vxl_mixPg_3D2D(*ctx_args, sample_num=None, step=step,
-                                                                             sync_MB=False)
-                    loss = loss + c.lmbda * bpp
-                self.opt.zero_grad(set_to_none=True)
-                self.opt2.zero_grad(set_to_none=True)
-                (loss * self.loss_scale).backward()
-            # both passes are joined to this stream: what their kernels added to the sinks goes to `.grad`, once — or, for
-            # the tables, straight into their Adam update (`_table_adam`: the pieces are summed there)
-            table_pieces = {} if (self.table_adam is not None and self.fused_table_adam) else None
-            for sink in (self.sink_render, self.sink_ctx):
-                if sink is not None:
-                    sink.flush(table_pieces=table_pieces)
-            if self._planes_replayed:
-                self.planes_graph.flush(table_pieces=table_pieces)       # what autograd returned inside the planes' graph
+            bpp, mb, table_pieces = self._backward_single(step, mse, ctx_future, tables_fused)
         else:
-            # Data-parallel step.  The ray loss differs per rank, the entropy loss does not (same tables, same
-            # window draw on every rank): so only the ray-loss gradient is exchanged, and its all-reduce runs
-            # on the communicator's stream WHILE the entropy pass is still under way.  The entropy gradient is equal
-            # across ranks only up to the order of its float atomics (~1e-9 relative), so the replicas are
-            # compared at every occupancy refresh and re-aligned to rank 0 where they differ (below).
-            A, B = self.bucket, self.bucket_ctx
-            if ctx_future is None:
-                if c.lmbda > 0:
-                    with _gradsink.activate(self.sink_ctx):
-                        bpp, mb = self.context.forward_binary_vxl_mixPg_3D2D(*ctx_args, sample_num=None, step=step,
-                                                                             sync_MB=False)
-                A.zero()
-                A.bind(force=True)
-            self._lagged_sample_count(len(pixels), n_samples)
-            if mse.requires_grad:          # a rank whose rays met no sample has nothing to add (its peers do): the
-                (mse * self.loss_scale).backward()     # collective below must still be entered by everyone
-            if self.sink_render is not None:
-                self.sink_render.flush()               # `.grad` = the bucket's views: the encoder scatters join it here
-            if sg is not None:
-                # this rank's range-guard trip as +inf (else 0) in the second tail slot: every rank reads it in the sum
-                sg.scan((), range_guard=range_guard, poison=A.tail[1:2])
-            work = A.allreduce(average=False, async_op=True)
-            ctx_grads = None
-            if ctx_future is not None:
-                bpp, mb, ctx_grads = join(ctx_future.result())
-            elif c.lmbda > 0:
-                B.zero()
-                B.bind(force=True)
-                (c.lmbda * bpp * self.loss_scale).backward()
-                if self.sink_ctx is not None:
-                    self.sink_ctx.flush()              # into `.grad` = B's views
-            if work is not None:
-                if self.time_comm:      # how long the compute stream stalls for the collective (what was NOT hidden
-                    e0 = torch.cuda.Event(enable_timing=True)        # behind the entropy pass)
-                    e0.record()
-                work.wait()
-                if self.time_comm:
-                    e1 = torch.cuda.Event(enable_timing=True)
-                    e1.record()
-                    self._comm_events.append((e0, e1))
-            # the summed sample count goes to the host behind the collective; nobody waits for it before the next step
-            self._count_host.copy_(A.tail[:1], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._count_pending = (ev, len(pixels))
-            if self.table_adam is not None and self.fused_table_adam:
-                # The tables' share of the bucket stays the SUM the collective left: it is the first piece of their Adam
-                # update, times 1 / world inside the kernel; the entropy gradient follows as further pieces, in the order and
-                # grouping in which the branch below adds them.  Only the rest of the bucket is averaged and added to here.
-                tids = {id(p) for p in self.table_adam.tables}
-                runs = A.runs_excluding(self.table_adam.tables)
-                table_pieces = {}
-                for lo, hi in runs:
-                    A.flat[lo:hi].div_(self.world)
-                if ctx_grads is not None:
-                    pairs = [(v, g) for p, v, g in zip(A.params, A.views, ctx_grads) if g is not None and id(p) not in tids]
-                    if pairs:
-                        torch._foreach_add_([v for v, _ in pairs], [g for _, g in pairs])
-                    for p, g in zip(A.params, ctx_grads):
-                        if g is not None and id(p) in tids:
-                            table_pieces[id(p)] = [(g if g.is_contiguous() else g.contiguous(), None)]
-                    if self.sink_ctx is not None:      # the heads' gradients into `.grad` = A's views, the tables' buffers listed
-                        self.sink_ctx.flush(table_pieces=table_pieces)
-                    if self._planes_replayed:
-                        self.planes_graph.flush(table_pieces=table_pieces)
-                elif c.lmbda > 0:
-                    for lo, hi in runs:
-                        A.flat[lo:hi].add_(B.flat[lo:hi])
-                    for p, v in zip(B.params, B.views):
-                        if id(p) in tids:              # autograd's gradient + the entropy sink's flush, as ONE piece
-                            table_pieces[id(p)] = [(v, None)]
-            else:
-                A.grads.div_(self.world)
-                if ctx_grads is not None:
-                    pairs = [(v, g) for v, g in zip(A.views, ctx_grads) if g is not None]
-                    torch._foreach_add_([v for v, _ in pairs], [g for _, g in pairs])
-                    if self.sink_ctx is not None:
-                        self.sink_ctx.flush()              # `.grad` = A's views (bound before the fork): after the mean
-                    if self._planes_replayed:
-                        self.planes_graph.flush()
-                elif c.lmbda > 0:
-                    A.grads.add_(B.flat)
-            A.bind(force=True)
+            bpp, mb, table_pieces = self._backward_dp(step, mse, ctx_future, tables_fused, len(pixels), n_samples, range_guard)
         if sg is not None:
-            # The step's verdict, on the device and before any update: every gradient the two library optimizers will read
-            # (the tables' pieces are not scanned: DESIGN.md §13) and the loss scalars; data parallel: what every rank holds
-            # alike — the bucket's summed non-table runs with the entropy gradient added, and the all-reduced guard slot.
-            if self.bucket is None:
-                scan = [p.grad for o in (self.opt, self.opt2) for g in o.param_groups for p in g["params"]
-                        if p.grad is not None and id(p) not in self._table_ids]
-                scan += [t.detach().reshape(-1) for t in (mse, bpp) if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
-                sg.scan(scan, range_guard=range_guard)
-            else:
-                A = self.bucket
-                sg.scan([A.flat[lo:hi] for lo, hi in A.runs_excluding(self._tables)] + [A.tail[1:2]])
-            grp = self.opt.param_groups[1]
-            sg.seal(grp["lr"], grp["eps"], grp["weight_decay"],
-                    self.table_adam.clip_counters() if (self.table_adam is not None and table_pieces is not None) else ())
-            self.opt.found_inf = self.opt2.found_inf = sg.found_inf
-            sg.poll()
-        if self.table_adam is not None:
-            if table_pieces is not None:
-                # leaves the tables' `.grad` None: the library's step skips them.  Data parallel: `.grad` is the bucket's view
-                # with the sum over the ranks (bound just above), the first piece; 1 / world as a float32
-                scale = 1.0 if self.bucket is None else self._inv_world
-                self.table_adam.step(table_pieces, grad_scale=scale, guard=sg)
-            else:
-                self.table_adam.steps_done += 1            # the library steps them below
+            self._verdict(mse, bpp, range_guard, tables_fused)
+        self._update(step, table_pieces, tables_fused)
+        if not want_stats:
+            return {"n_rendering_samples": n_samples, "num_rays": len(pixels)}
+        # the step's scalars in one device->host copy
+        mse_f, bpp_f, mb_f = torch.stack([mse.detach(), torch.as_tensor(bpp, device=mse.device).detach().float(),
+                                          torch.as_tensor(mb, device=mse.device).detach().float()]).tolist()
+        return {"mse": mse_f, "psnr": -10.0 * math.log10(max(mse_f, 1e-12)), "bpp": bpp_f,
+                "embed_bits_MB": mb_f, "n_rendering_samples": n_samples, "num_rays": len(pixels)}
+
+    def _backward_single(self, step, mse, ctx_future, tables_fused):
+        """Single process: both backward passes in this step's schedule -> (bits per parameter, MB, the tables' pieces)."""
+        c = self.cfg
+        bpp, mb = 0.0, 0.0
+        if ctx_future is not None:
+            (mse * self.loss_scale).backward()
+            self._prefetch(step)
+            bpp, mb, _ = self._join_entropy_pass(ctx_future.result())
+        elif self.ctx_stream is not None and c.lmbda > 0 and mse.requires_grad:
+            # The sequential schedule of the same idea (one host thread; the reference's order of random draws):
+            #   render backward (main stream: few launches, GPU-heavy)
+            #   || context forward + context backward (side stream: ~250 launches, host-bound forward)
+            # The side stream forks BEFORE the render backward is enqueued; its host-side syncs (window bounds,
+            # nonzero) wait for the side stream only.
+            self._clear_grads()
+            fork = torch.cuda.current_stream(self.device).record_event()
+            (mse * self.loss_scale).backward()
+            bpp, mb, _ = self._join_entropy_pass(self._context_pass(step, fork))
+        else:
+            # The plain schedule: one stream, one thread, ONE backward call over the joint loss (the reproducible mode and the
+            # trajectory goldens are this)
+            loss = mse
+            if c.lmbda > 0:
+                bpp, mb = self._entropy_forward(step)
+                loss = loss + c.lmbda * bpp
+            self._clear_grads()
+            (loss * self.loss_scale).backward()
+        # both passes are joined to this stream: what their kernels added to the sinks goes to `.grad`, once — or, for
+        # the tables, straight into their Adam update (`_table_adam`: the pieces are summed there, in this order)
+        table_pieces = {} if tables_fused else None
+        for sink in (self.sink_render, self.sink_ctx):
+            if sink is not None:
+                sink.flush(table_pieces=table_pieces)
+        if self._planes_replayed:
+            self.planes_graph.flush(table_pieces=table_pieces)       # what autograd returned inside the planes' graph
+        return bpp, mb, table_pieces
+
+    def _backward_dp(self, step, mse, ctx_future, tables_fused, num_rays, n_samples, range_guard):
+        """Data parallel: the backward passes around the ray-loss gradient's all-reduce -> what `_backward_single` returns."""
+        # The ray loss differs per rank, the entropy loss does not (same tables, same window draw on every rank): so only
+        # the ray-loss gradient is exchanged, and its all-reduce runs on the communicator's stream WHILE the entropy pass is
+        # still under way.  The entropy gradient is equal across ranks only up to the order of its float atomics (~1e-9
+        # relative), so the replicas are compared at every occupancy refresh and re-aligned to rank 0 where they differ
+        # (`_update`).
+        c, sg = self.cfg, self.step_guard
+        A, B = self.bucket, self.bucket_ctx
+        bpp, mb = 0.0, 0.0
+        if ctx_future is None:
+            if c.lmbda > 0:
+                bpp, mb = self._entropy_forward(step)
+            self._clear_grads()
+        self._lagged_sample_count(num_rays, n_samples)
+        if mse.requires_grad:          # a rank whose rays met no sample has nothing to add (its peers do): the
+            (mse * self.loss_scale).backward()     # collective below must still be entered by everyone
+        if self.sink_render is not None:
+            self.sink_render.flush()               # `.grad` = the bucket's views: the encoder scatters join it here
+        if sg is not None:
+            # this rank's range-guard trip as +inf (else 0) in the second tail slot: every rank reads it in the sum
+            sg.scan((), range_guard=range_guard, poison=A.tail[1:2])
+        work = A.allreduce(average=False, async_op=True)
+        ctx_grads = None
+        if ctx_future is not None:
+            bpp, mb, ctx_grads = self._join_entropy_pass(ctx_future.result())
+        elif c.lmbda > 0:
+            self._clear_grads(B)
+            (c.lmbda * bpp * self.loss_scale).backward()
+            if self.sink_ctx is not None:
+                self.sink_ctx.flush()              # into `.grad` = B's views
+        if work is not None:
+            if self.time_comm:      # how long the compute stream stalls for the collective (what was NOT hidden
+                e0 = torch.cuda.Event(enable_timing=True)        # behind the entropy pass)
+                e0.record()
+            work.wait()
+            if self.time_comm:
+                e1 = torch.cuda.Event(enable_timing=True)
+                e1.record()
+                self._comm_events.append((e0, e1))
+        # the summed sample count goes to the host behind the collective; nobody waits for it before the next step
+        self._count_host.copy_(A.tail[:1], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._count_pending = (ev, num_rays)
+        # The mean of the ray-loss gradient + the entropy gradient, in the bucket.  The tables' share, when their kernel steps
+        # them, stays the SUM the collective left: it is the first piece of their Adam update, times 1 / world inside the
+        # kernel; their entropy gradient follows as further pieces — autograd's (or B's view: autograd's + the entropy
+        # sink's flush, as ONE piece), the entropy sink's buffer, the planes' graph's.
+        pieces = cdist.fold_entropy_gradients(A, self._tables if tables_fused else (), self.world,
+                                              grads=ctx_grads, other=B if ctx_grads is None and c.lmbda > 0 else None)
+        table_pieces = pieces if tables_fused else None
+        if ctx_grads is not None:
+            if self.sink_ctx is not None:      # the heads' gradients into `.grad` = A's views (bound before the fork), behind
+                self.sink_ctx.flush(table_pieces=table_pieces)       # the mean; the tables' buffers listed
+            if self._planes_replayed:
+                self.planes_graph.flush(table_pieces=table_pieces)
+        A.bind(force=True)
+        return bpp, mb, table_pieces
+
+    def _verdict(self, mse, bpp, range_guard, tables_fused) -> None:
+        """The guarded step's verdict, on the device and before any update."""
+        # Scanned: every gradient the two library optimizers will read (the tables' pieces are not: DESIGN.md §13) and the
+        # loss scalars; data parallel: what every rank holds alike — the bucket's summed non-table runs with the entropy
+        # gradient added, and the all-reduced guard slot.
+        sg, A = self.step_guard, self.bucket
+        if A is None:
+            scan = [p.grad for o in (self.opt, self.opt2) for g in o.param_groups for p in g["params"]
+                    if p.grad is not None and id(p) not in self._table_ids]
+            scan += [t.detach().reshape(-1) for t in (mse, bpp) if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
+            sg.scan(scan, range_guard=range_guard)
+        else:
+            sg.scan([A.flat[lo:hi] for lo, hi in A.runs_excluding(self._tables)] + [A.tail[1:2]])
+        grp = self.opt.param_groups[1]
+        sg.seal(grp["lr"], grp["eps"], grp["weight_decay"], self.table_adam.clip_counters() if tables_fused else ())
+        self.opt.found_inf = self.opt2.found_inf = sg.found_inf
+        sg.poll()
+
+    def _update(self, step, table_pieces, tables_fused) -> None:
+        """Both optimizers (the tables through their kernel when `tables_fused`), the schedules, the replicas' resync."""
+        c = self.cfg
+        if tables_fused:
+            # leaves the tables' `.grad` None: the library's step skips them.  Data parallel: `.grad` is the bucket's view
+            # with the sum over the ranks (bound by `_backward_dp`), the first piece; 1 / world as a float32
+            self.table_adam.step(table_pieces, grad_scale=1.0 if self.bucket is None else self._inv_world, guard=self.step_guard)
+        elif self.table_adam is not None:
+            self.table_adam.steps_done += 1            # the library steps them below
         self.opt.step()
         if c.lmbda > 0:
             self.opt2.step()
-        if self.table_adam is not None and table_pieces is not None:
+        if tables_fused:
             self.table_adam.mark_planes_current()      # (the two steps above dropped every cache: the tables' planes stand)
         self.sched.step()
         if c.lmbda > 0:
@@ -962,13 +861,6 @@ class Trainer:
             self.resync["fired"] += 1 if n else 0
             self.resync["tensors"] += n
             self.resync["bytes"] += nbytes
-        if not want_stats:
-            return {"n_rendering_samples": n_samples, "num_rays": len(pixels)}
-        # the step's scalars in one device->host copy
-        mse_f, bpp_f, mb_f = torch.stack([mse.detach(), torch.as_tensor(bpp, device=mse.device).detach().float(),
-                                          torch.as_tensor(mb, device=mse.device).detach().float()]).tolist()
-        return {"mse": mse_f, "psnr": -10.0 * math.log10(max(mse_f, 1e-12)), "bpp": bpp_f,
-                "embed_bits_MB": mb_f, "n_rendering_samples": n_samples, "num_rays": len(pixels)}
 
     def train(self, steps: Optional[int] = None, log=print):
         steps = self.cfg.max_steps if steps is None else steps

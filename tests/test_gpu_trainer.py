@@ -353,3 +353,87 @@ def test_planes_graph_and_planes_stream_equal_the_one_stream_entropy_pass(cuda, 
     refreshes = tr.context.refresh_stats["refreshes"] - tr.context.refresh_stats["skipped"]
     assert 2 <= pg.captures <= refreshes and pg.replays >= 4 + 50 - 4            # every non-refresh step replayed
     assert all(bool(torch.isfinite(p).all()) for p in params)
+
+
+@pytest.mark.parametrize("reproducible", [False, True], ids=["threaded", "reproducible"])
+def test_a_step_without_samples_changes_nothing(cuda, tmp_path, reproducible):
+    """A batch whose rays all miss the box (origins outside it, directions pointing away): `train_step` returns None and
+    leaves every parameter, every optimizer state tensor (the `step` counts among them) and the occupancy grid bit for bit
+    as they were — on the default threaded schedule, whose entropy pass is already under way when the sample count is
+    known, and on the reproducible mode's one-stream schedule.  The ordinary step behind it trains as usual."""
+    from cnc_amd.render import Rays
+    from cnc_amd.trainer import Trainer
+    from test_gpu_reproducible_step import _bits, _state
+    tr = Trainer(_cfg(tmp_path, seed=3, reproducible=reproducible), device=cuda)
+    assert tr.ctx_thread != reproducible
+    assert tr.train_step(0) is not None                   # (the optimizers have state: moments and step counts)
+    torch.cuda.synchronize()
+    before = _state(tr)
+    assert any(k.endswith(".step") for k in before) and any(k.endswith("exp_avg_sq") for k in before)
+    n = 64
+    o = torch.tensor([4.0, 0.5, -0.25], device=cuda).expand(n, 3).contiguous()
+    d = torch.nn.functional.normalize(torch.tensor([1.0, 0.0, 0.0], device=cuda)
+                                      + 0.1 * torch.rand(n, 3, device=cuda, generator=torch.Generator(cuda).manual_seed(1)), dim=-1)
+    tr._next_data = {"rays": Rays(o, d), "pixels": torch.rand(n, 3, device=cuda), "color_bkgd": torch.rand(3, device=cuda)}
+    assert tr.train_step(1) is None
+    torch.cuda.synchronize()
+    after = _state(tr)
+    assert set(after) == set(before)
+    for k in before:
+        assert int((_bits(before[k]) != _bits(after[k])).sum()) == 0, k
+    s = tr.train_step(2)
+    torch.cuda.synchronize()
+    assert s is not None and s["n_rendering_samples"] > 0 and math.isfinite(s["mse"]) and math.isfinite(s["bpp"])
+    moved = _state(tr)
+    assert any(int((_bits(before[k]) != _bits(moved[k])).sum()) for k in before if k.startswith("field."))
+    assert any(int((_bits(before[k]) != _bits(moved[k])).sum()) for k in before if k.startswith("context."))
+
+
+_RAISING_ENTROPY_PASS = r"""
+import math, sys, torch
+sys.path.insert(0, {root!r})
+from cnc_amd.trainer import TrainConfig, Trainer
+at = {at}
+tr = Trainer(TrainConfig(**{cfg!r}), device="cuda")
+assert tr.ctx_thread and tr.ctx_stream is not None and tr.planes_graph is not None
+for s in range(at):
+    tr.train_step(s, want_stats=False)
+assert tr.planes_graph.replays == {replays}, tr.planes_graph.replays
+
+def boom(*args, **kwargs):
+    raise RuntimeError("boom")
+forward = tr.context.forward_binary_vxl_mixPg_3D2D
+tr.context.forward_binary_vxl_mixPg_3D2D = boom
+try:
+    tr.train_step(at)
+except RuntimeError as e:
+    assert str(e) == "boom", repr(e)
+else:
+    raise AssertionError("train_step did not raise")
+assert tr.planes_graph.replays == {replays_after}, tr.planes_graph.replays
+tr.context.forward_binary_vxl_mixPg_3D2D = forward
+torch.cuda.synchronize()
+s = tr.train_step(at + 1)
+torch.cuda.synchronize()
+assert s is not None and math.isfinite(s["mse"]) and math.isfinite(s["bpp"]), s
+print("PASSED", flush=True)
+"""
+
+
+@pytest.mark.parametrize("at", [2, 18])
+def test_an_entropy_pass_that_raises_leaves_a_trainer_that_trains(cuda, tmp_path, at):
+    """A Python exception inside the entropy pass on the threaded schedule — at step 2, with no planes' job in flight, and at
+    step 18, behind a planes' graph replay that the planes' thread has already been handed (toy `step_update` = 16: steps
+    17-19 replay): `train_step` raises that error and nothing else, nothing hangs (a child process under its own time
+    limit), and with the method restored the device synchronises and the next step returns finite numbers."""
+    import dataclasses
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / "worker.py"
+    replays = max(0, at - 17)
+    script.write_text(_RAISING_ENTROPY_PASS.format(root=root, at=at, cfg=dataclasses.asdict(_cfg(tmp_path, seed=3)),
+                                                   replays=replays, replays_after=replays + (1 if at > 16 else 0)))
+    env = dict(os.environ, CNC_PLANES_GRAPH_STRICT="1")
+    done = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=300)
+    assert done.returncode == 0 and "PASSED" in done.stdout, done.stderr[-3000:]

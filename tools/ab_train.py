@@ -1,5 +1,8 @@
 """Scratch: A/B of a Trainer switch inside ONE process (boxes differ by more than the effects measured here):
-alternating blocks of steps with the switch off / on, wall time per step of each block."""
+alternating blocks of steps with the switch off / on, wall time per step of each block.  The Trainer's switches are its
+attributes, flipped between steps (`ctx_thread`, `ctx_stream`, `ctx_stream_2D`, `planes_graph`, `premarch`, `prefetch`,
+`fused_table_adam`: the step reads them per step, none of them has an environment variable of its own any more); any other
+name is set as an environment variable, for the switches that are read per call."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
