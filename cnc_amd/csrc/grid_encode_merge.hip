@@ -4,8 +4,9 @@
 // a marched frame (200-400 samples per ray), so the runs it merges are runs along ONE ray.  The rays of
 // neighbouring pixels cross the same cells: of the runs in 1024 consecutive samples (3-4 rays) only 0.29
 // (level 0) to 0.46 (resolution 214) open a cell no earlier run of the block visited; in 256 samples it is
-// 0.93-0.96.  This kernel takes MB = 1024 (or 512) samples per block, chains the runs of equal cells through a
-// small LDS hash table and sends ONE set of atomics per distinct cell — the coarse levels are bound by the
+// 0.93-0.96.  This kernel takes MB = 1024 (or 512) samples per block, finds the runs of equal cells through a
+// small LDS hash table, lays the block's samples out by cell and sends ONE set of atomics per distinct cell (per
+// CNC_MERGE_UNIT_CAP samples of it) — the coarse levels are bound by the
 // memory-side atomic units (docs/engineering_log.md §4.2b), so the number of atomic instructions is what their time was
 // made of.  Which 1024 samples a block takes: consecutive ones, or (levels of R >= kMergeTileMinRes, callers with scratch
 // for the order) a depth slab of ~26 neighbouring rays, which merges as 4096 consecutive samples would: k_merge_tile_order.
@@ -26,6 +27,14 @@
 //     DPP scan (two 16-term loops before), the valid-corner mask from six per-axis flags: 154.0 M -> 122.1 M vector
 //     wave-instructions per call of the bench, 41 -> 32 vector registers, the bench frame +2.0 %
 //     (profiles/r17_backward_issue_slots.md).
+//   * a wave walked its cell's chain of run records two runs per MFMA step, a step of eight sample slots for runs of
+//     one to three samples on the fine levels, 13 vector and 35 scalar instructions per pair around it, and one wave per
+//     cell however long its chain.  Now every run takes its place in its cell with one LDS add, the samples' weights and
+//     gradients are written to LDS at those places (they wait in registers until then), and a unit is a range of places:
+//     ceil(n / 8) full steps in a counted loop, no records, no chain, units cut by arithmetic and handed to the waves
+//     from a block-wide counter.  122.1 M -> 111.2 M vector and 97.5 M -> 60.9 M scalar wave-instructions per call of the
+//     bench, the same 4.53 M atomic requests, the bench frame +3.5 % (profiles/r18_merge_wave_balance.md; balancing the
+//     waves alone, over the chains as they were, was worth nothing next to the bin / owner passes).
 //
 // D = 3, F = 8 (one cell per wave at a time: 64 lanes = 8 corners x 8 features), no occupancy mask, no
 // per-point level window: the coarse half of a binned backward call.  Everything else stays on
@@ -49,14 +58,26 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #endif
 constexpr uint32_t kMergeTileWindow = CNC_MERGE_TILE_WINDOW, kMergeTileSegment = CNC_MERGE_TILE_SEGMENT;
 // Levels below this resolution keep consecutive samples.  A tile of ~32 rays x 32 samples spans a handful of their
-// cells: fewer cells than the block has waves, each a chain of hundreds of samples that ONE wave walks while the others
-// idle.  Ten copies of one level of the bench grid, middle chunk, ms consecutive -> ranked (order from
-// k_merge_tile_order): R = 18 0.224 -> 0.462, 24 0.216 -> 0.420, 32 0.227 -> 0.378, 44 0.253 -> 0.333, 60 0.340 -> 0.317,
-// 82 0.376 -> 0.322, 113 0.458 -> 0.336, 155 0.619 -> 0.400, 214 0.859 -> 0.590, 296 1.190 -> 0.884.
+// cells: fewer cells than the block has waves, each of hundreds of samples.  When one wave walked a whole cell, ten copies
+// of one level of the bench grid, middle chunk, took (ms, consecutive -> ranked, order from k_merge_tile_order): R = 18
+// 0.224 -> 0.462, 24 0.216 -> 0.420, 32 0.227 -> 0.378, 44 0.253 -> 0.333, 60 0.340 -> 0.317, 82 0.376 -> 0.322,
+// 113 0.458 -> 0.336, 155 0.619 -> 0.400, 214 0.859 -> 0.590, 296 1.190 -> 0.884.  With the samples laid out by cell
+// (below) 32 and 0 were measured again: the call 1.0-2.9 % shorter on three chunks, the bench frame +0.6 % in every pair
+// of runs, which is not enough for the project's keep rule (profiles/r18_merge_wave_balance.md).
 #ifndef CNC_MERGE_TILE_MIN_RES
 #define CNC_MERGE_TILE_MIN_RES 52
 #endif
 constexpr uint32_t kMergeTileMinRes = CNC_MERGE_TILE_MIN_RES;
+// Most samples of one work unit of phase B.  A wave sums one unit at a time and takes the next from a block-wide
+// counter, so a cell of hundreds of samples no longer keeps one wave busy while the others of the block, and the block's
+// LDS, wait for it.  Every unit sends its own set of atomics: on the bench frame a cap of 32 adds 15-24 % of them and
+// costs 4 % of the frame, 128 adds 10-60 % on the levels of R = 18 and 60, 512 adds none but 1.6 % on the first chunk's
+// coarsest level (tools/merge_wave_load.py, profiles/r18_merge_wave_balance.md).
+#ifndef CNC_MERGE_UNIT_CAP
+#define CNC_MERGE_UNIT_CAP 512
+#endif
+constexpr uint32_t kMergeUnitCap = CNC_MERGE_UNIT_CAP;
+static_assert(kMergeUnitCap >= 8 && kMergeUnitCap % 8 == 0, "whole steps of eight samples");
 
 // Depth-ranked sample tiles.  Two samples of one ray never share a cell beyond one run: all merging beyond runs happens
 // ACROSS rays, and 1024 consecutive samples are the full depth of only 3-4 rays.  So a block of the merge kernel need not
@@ -175,30 +196,33 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     constexpr uint32_t kMB = MB;
     constexpr uint32_t kMW = kMB / 64;        // waves per block
     constexpr uint32_t kMSlots = kMB <= 512 ? 1024 : 2048;   // hash slots, power of two, >= 2 x the most runs a block can have
-    constexpr uint32_t D = 3, F = 8, END = 0x7FFu;
-    static_assert(kMB <= 1024, "run records pack start (10 bits) / end (11) / next (11)");
+    constexpr uint32_t kCap = kMergeUnitCap;
+    constexpr uint32_t D = 3, F = 8;
+    static_assert(kMB <= 1024, "run records pack representative run / place in the cell / first thread, 10 bits each");
     // the three fractional positions and 1 / (sum of valid weights): the lane rebuilds its corner's
-    // weight from them (same products, same order as Corners::setup) — half the LDS of 8 stored weights
+    // weight from them (same products, same order as Corners::setup) — half the LDS of 8 stored weights.
+    // Both arrays are indexed by the sample's PLACE in the block's cell order (below), not by its thread.
     __shared__ __attribute__((aligned(16))) float s_w4[kMB][4];
     __shared__ float    s_g[kMB][F];
     // 16 bytes per thread, used twice: the sample keys (first half) and the hash table (second half)
-    // until the runs are chained, then one record per distinct cell {first run record, key, validity}
+    // until the runs are counted, then one record per unit {first place | end place << 16, key, validity}
     __shared__ __attribute__((aligned(16))) uint4 s_u[kMB];
     uint64_t* const s_key = reinterpret_cast<uint64_t*>(s_u);
     uint32_t* const h_slot = reinterpret_cast<uint32_t*>(s_u) + 2 * kMB;
     static_assert(kMSlots * 4 <= kMB * 8, "hash table fits the second half of s_u");
     __shared__ uint16_t s_run_start[kMB + 1];
-    __shared__ uint32_t l_head[kMB];            // per representative run: last run chained to its cell
-    __shared__ uint32_t s_run_rec[kMB];         // start | end << 10 | next run of the cell << 21: one read per run
-    __shared__ uint32_t s_wave_heads[kMW], s_wave_claims[kMW];
+    __shared__ uint32_t s_cell_n[kMB];          // per representative run of a cell: its samples so far, then its first place
+    __shared__ uint32_t s_run_rec[kMB];         // representative run | place of the run in its cell << 10 | first thread << 20
+    __shared__ uint32_t s_wave_heads[kMW];
+    __shared__ uint32_t s_ctr[2];               // samples placed | units made << 16; the next unit phase B hands out
 
     // (the wave index through readfirstlane: the compiler cannot see that tid >> 6 is wave-uniform, and everything that
-    // hangs on it — the prefix reads below, the cell loop of phase B — is scalar work once it can)
+    // hangs on it — the prefix reads below, the unit loop of phase B — is scalar work once it can)
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool     mask_on = STE && (clip_count == nullptr || *clip_count != 0);
-    // Exclusive prefix and total of one count per wave (s_wave_heads, s_wave_claims): lane l reads the word of wave
+    // Exclusive prefix and total of one count per wave (s_wave_heads): lane l reads the word of wave
     // l % kMW, an inclusive scan inside the 16-lane row (four DPP row shifts that shift zeros in) and two readlanes at
-    // wave-uniform lanes.  The counts of the waves in wave order, i.e. in sample order: runs and cells keep their numbers.
+    // wave-uniform lanes.  The counts of the waves in wave order, i.e. in sample order: runs keep their numbers.
     auto wave_prefix = [&](const uint32_t* counts, uint32_t& before, uint32_t& total) {
         static_assert(kMW == 8 || kMW == 16, "the counts of a block fit one DPP row");
         const uint32_t h = counts[lane & (kMW - 1)];
@@ -229,11 +253,14 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
         }
     }
     for (uint32_t i = tid; i < kMSlots; i += kMB) h_slot[i] = 0;
-    l_head[tid] = END;
+    s_cell_n[tid] = 0;
+    if (tid < 2) s_ctr[tid] = tid == 0 ? 0u : kMW;         // (the first unit of a wave is its own number)
 
-    // ---- phase A: lane = sample ----
+    // ---- phase A: lane = sample; weights and gradient stay in registers until the sample's place is known ----
     uint64_t key = ~0ull;
     uint32_t validmask = 0;
+    float4   w4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float    g0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, g1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     {
         float    x[D];
         if (b < N && load_point<D>(inputs, b, x)) {
@@ -250,16 +277,10 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
                     | (border(y1) ? 0xCCu : 0u) | (border(c.cell[2]) ? 0x0Fu : 0u) | (border(z1) ? 0xF0u : 0u);
                 validmask = inv ^ 0xFFu;
             }
-            *reinterpret_cast<float4*>(s_w4[tid]) = make_float4(c.frac[0], c.frac[1], c.frac[2], c.wn_re);
+            w4 = make_float4(c.frac[0], c.frac[1], c.frac[2], c.wn_re);
             const float* gp = grad + feat_index(lay, slot, N, b, F);
-            float        g0[4], g1[4];
             load_vec<4>(gp, g0);
             load_vec<4>(gp + 4, g1);
-#pragma unroll
-            for (uint32_t j = 0; j < 4; j++) {
-                s_g[tid][j] = g0[j];
-                s_g[tid][4 + j] = g1[j];
-            }
         }
         s_key[tid] = key;
     }
@@ -272,12 +293,15 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     __syncthreads();
     uint32_t before, total;
     wave_prefix(s_wave_heads, before, total);
-    const uint32_t my_run = before + (uint32_t)__popcll(hb & ((1ull << lane) - 1ull));
+    // the run of every thread, head or not: the heads up to and including its lane, after those of the earlier waves
+    const uint32_t my_run = before + (uint32_t)__popcll(hb & ((2ull << lane) - 1ull)) - 1u;
     if (head) s_run_start[my_run] = (uint16_t)tid;
     if (tid == 0) s_run_start[total] = (uint16_t)kMB;
     __syncthreads();
 
-    // ---- cells: chain the runs of equal cells ----
+    // ---- cells: every run takes its place among the samples of its cell ----
+    // The run that claims the cell's hash slot represents the cell.  Every run of the cell, in whatever order they arrive,
+    // adds its length to s_cell_n[representative]: what the add returns is where the run's samples start among the cell's.
     bool     claimer = false;
     if (head && key != ~0ull) {
         uint32_t sl = (((uint32_t)key ^ (uint32_t)(key >> 16) ^ (uint32_t)(key >> 32)) * 2654435761u) >> (32 - __builtin_ctz(kMSlots));
@@ -289,27 +313,46 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
             if (s_key[s_run_start[rep]] == key) break;
             sl = (sl + 1) & (kMSlots - 1);
         }
-        const uint32_t next = atomicExch(&l_head[rep], my_run);
-        s_run_rec[my_run] = tid | (uint32_t)s_run_start[my_run + 1] << 10 | next << 21;
+        const uint32_t len = (uint32_t)s_run_start[my_run + 1] - tid;
+        s_run_rec[my_run] = rep | atomicAdd(&s_cell_n[rep], len) << 10 | tid << 20;
     }
-    const uint64_t cb = __ballot(claimer);
-    if (lane == 0) s_wave_claims[wave] = (uint32_t)__popcll(cb);
     __syncthreads();
-    uint32_t g_before, n_cells;
-    wave_prefix(s_wave_claims, g_before, n_cells);
+    // ---- units: the cells laid out one after the other, each cut into units of at most kCap places ----
     // (the sync above also ends the life of the keys and the hash table: s_u is rewritten here)
-    uint4 my_cell = make_uint4(0, 0, 0, 0);
-    if (claimer) my_cell = make_uint4(s_run_rec[l_head[my_run]], (uint32_t)key, (uint32_t)(key >> 32), validmask);
-    if (claimer) s_u[g_before + (uint32_t)__popcll(cb & ((1ull << lane) - 1ull))] = my_cell;
+    // A representative takes its cell's first place and its first unit record with ONE add on a packed counter (places in
+    // the low half, records in the high half: a block has at most kMB of either, a unit holds at least one sample).
+    if (claimer) {
+        const uint32_t n = s_cell_n[my_run], units = (n + kCap - 1) / kCap;
+        const uint32_t got = atomicAdd(&s_ctr[0], n | units << 16);
+        const uint32_t first = got & 0xFFFFu, end = first + n;
+        uint32_t       at = got >> 16;
+        s_cell_n[my_run] = first;
+        for (uint32_t p = first; p < end; p += kCap, at++)
+            s_u[at] = make_uint4(p | min(p + kCap, end) << 16, (uint32_t)key, (uint32_t)(key >> 32), validmask);
+    }
     __syncthreads();
+    // ---- places: every sample moves to its cell's first place + its run's place in the cell + its place in the run ----
+    if (key != ~0ull) {
+        const uint32_t rr = s_run_rec[my_run];
+        const uint32_t at = s_cell_n[rr & 0x3FFu] + ((rr >> 10) & 0x3FFu) + (tid - (rr >> 20));
+        *reinterpret_cast<float4*>(s_w4[at]) = w4;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            s_g[at][j] = g0[j];
+            s_g[at][4 + j] = g1[j];
+        }
+    }
+    __syncthreads();
+    const uint32_t n_units = __builtin_amdgcn_readfirstlane(s_ctr[0]) >> 16;
 
-    // ---- phase B: lane = (corner, feature); each wave walks a contiguous range of cells ----
+    // ---- phase B: lane = (corner, feature); a wave sums one unit at a time and takes the next from the block ----
     const uint32_t c = lane / F, f = lane % F;
-    const uint32_t mi = lane & 15u, mk = lane >> 4;        // MFMA operand index (corner / feature of run A | B), sample slot
-    const bool     half_b = (mi & 8u) != 0;
+    const uint32_t mi = lane & 15u, mk = lane >> 4;        // MFMA operand index (corner / feature of half A | B), sample slot
     const float    sx = (mi & 1u) ? 1.0f : -1.0f, ox = (mi & 1u) ? 0.0f : 1.0f;
     const float    sy = (mi & 2u) ? 1.0f : -1.0f, oy = (mi & 2u) ? 0.0f : 1.0f;
     const float    sz = (mi & 4u) ? 1.0f : -1.0f, oz = (mi & 4u) ? 0.0f : 1.0f;
+    // my sample of a step's eight: 2 * slot + half, so that the eight gradient rows a step reads are 64 consecutive words
+    const uint32_t mine = 2u * mk + ((mi >> 3) & 1u);
     auto flush = [&](uint32_t row, float v) {
         const size_t at = (size_t)row * F + f;
         if (mask_on) {
@@ -348,53 +391,40 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
     // made of, and the match (cell delta, partner lane, one more cross-lane read per cell) cost more issue
     // slots than the saved requests: 0.330 -> 0.305 ms for the 9 coarse levels, 1.091 -> 1.060 ms for the
     // whole backward call next to the bin / owner passes.
-    for (uint32_t g = wave; g < n_cells; g += kMW) {
-        const uint4 cell = s_u[g];                         // {first run of the chain, key, valid corners}
-        // The chain is the wave's, not the lane's: the records go through readfirstlane, so their fields, the lone-run
-        // split, the step count and both loop conditions live in scalar registers behind scalar branches.  Per lane
-        // stays what depends on the lane: which run of the pair it feeds, its sample slot, the two LDS reads, the weight.
-        uint32_t    rec = __builtin_amdgcn_readfirstlane(cell.x);
+    for (uint32_t g = wave; g < n_units;) {
+        const uint4 cell = s_u[g];                         // {first place | end place << 16, key, valid corners}
+        // The unit is the wave's, not the lane's: its bounds and the cell go through readfirstlane, the step loop is a
+        // counted scalar loop.
+        const uint32_t span = __builtin_amdgcn_readfirstlane(cell.x);
         const uint32_t k_lo = __builtin_amdgcn_readfirstlane(cell.y);
         const uint32_t k_hi = __builtin_amdgcn_readfirstlane(cell.z);
-        // S[corner][feature] = sum over the chain's samples of w[corner] * g[feature]: a K = n product of
+        const uint32_t p_end = span >> 16;
+        // S[corner][feature] = sum over the unit's samples of w[corner] * g[feature]: a K = n product of
         // an 8 x n and an n x 8 matrix on v_mfma_f32_16x16x4_f32.  Lane l feeds sample slot l / 16 with
         // operand index l % 16: its corner's weight (rebuilt from the 3 fractions — once per (corner, sample)
         // instead of once per (corner, feature, sample) as a lane-per-output loop would) and its feature's
-        // gradient.  Two runs per step: operand rows / columns 0..7 carry run A, 8..15 run B (the next run
-        // of the chain, or the second half of a lone run), so the tile's two diagonal 8 x 8 blocks are two
-        // partial sums and every lane has work (8 samples per instruction; the off-diagonal A x B cross
-        // terms are dropped).  The loop is wave-uniform: every lane walks the same chain.
+        // gradient.  Eight samples per step: operand rows / columns 0..7 carry the even places, 8..15 the odd ones,
+        // so the tile's two diagonal 8 x 8 blocks are two partial sums and every lane has work (the off-diagonal
+        // cross terms are dropped).  The samples of a cell lie side by side whatever runs they came in: no run
+        // records, no chain, ceil(n / 8) steps.
         f32x4 S = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (;;) {
-            uint32_t a0 = rec & 0x3FFu, a1 = (rec >> 10) & 0x7FFu, b0, b1, nxt = rec >> 21;
-            if (nxt != END) {
-                const uint32_t rb = __builtin_amdgcn_readfirstlane(s_run_rec[nxt]);
-                b0 = rb & 0x3FFu, b1 = (rb >> 10) & 0x7FFu, nxt = rb >> 21;
-            } else {
-                b1 = a1;
-                a1 = b0 = min(a1, a0 + ((((a1 - a0 + 1u) >> 1) + 3u) & ~3u));
+        for (uint32_t p = span & 0xFFFFu; p < p_end; p += 8) {
+            const uint32_t ps = p + mine;
+            float          a = 0.0f, bv = 0.0f;
+            if (ps < p_end) {
+                const float4 q = *reinterpret_cast<const float4*>(s_w4[ps]);
+                // bit ? frac : 1 - frac, as one fma with (+1, 0) or (-1, 1): exact either way
+                const float wx = __builtin_fmaf(q.x, sx, ox), wy = __builtin_fmaf(q.y, sy, oy),
+                            wz = __builtin_fmaf(q.z, sz, oz);
+                a = ((wx * wy) * wz) * q.w;
+                bv = s_g[ps][mi & 7u];
             }
-            const uint32_t steps = max(a1 - a0, b1 - b0);
-            const uint32_t m0 = half_b ? b0 : a0, m1 = half_b ? b1 : a1;
-            // the next pair's first record, asked for before the step loop and taken after it (END & (kMB - 1) is a slot
-            // of the array like any other: read and not used)
-            const uint32_t ahead = s_run_rec[nxt & (kMB - 1)];
-            for (uint32_t p = 0; p < steps; p += 4) {
-                const uint32_t ps = m0 + p + mk;
-                float          a = 0.0f, bv = 0.0f;
-                if (ps < m1) {
-                    const float4 q = *reinterpret_cast<const float4*>(s_w4[ps]);
-                    // bit ? frac : 1 - frac, as one fma with (+1, 0) or (-1, 1): exact either way
-                    const float wx = __builtin_fmaf(q.x, sx, ox), wy = __builtin_fmaf(q.y, sy, oy),
-                                wz = __builtin_fmaf(q.z, sz, oz);
-                    a = ((wx * wy) * wz) * q.w;
-                    bv = s_g[ps][mi & 7u];
-                }
-                S = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, S, 0, 0, 0);
-            }
-            if (nxt == END) break;
-            rec = __builtin_amdgcn_readfirstlane(ahead);
+            S = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, S, 0, 0, 0);
         }
+        // the next unit: one lane asks the block's counter (before the epilogue, whose cross-lane reads wait on the same
+        // LDS queue), the answer is the wave's through readfirstlane: the loop keeps its scalar control
+        uint32_t taken = 0;
+        if (lane == 0) taken = atomicAdd(&s_ctr[1], 1u);
         // tile element (row, col) sits in lane col + 16 * (row / 4), register row % 4; block B is 8 rows
         // and 8 columns further on = 40 lanes
         const int   src = (int)(f + 16u * (c >> 2));
@@ -402,6 +432,7 @@ __global__ __launch_bounds__(MB) void k_grid_encode_bwd_merge(
                     e2 = __shfl(S[2], src) + __shfl(S[2], src + 40), e3 = __shfl(S[3], src) + __shfl(S[3], src + 40);
         if ((cell.w >> c) & 1u)
             flush(row_of(k_lo, k_hi), (c & 2u) ? ((c & 1u) ? e3 : e2) : ((c & 1u) ? e1 : e0));
+        g = __builtin_amdgcn_readfirstlane(taken);
     }
 }
 
