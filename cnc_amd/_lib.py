@@ -184,6 +184,7 @@ SIGNATURES = {
     "cnc_level_stats_forward": [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
     "cnc_level_stats_backward": [_vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _vp, _vp],
     "cnc_field_prepare": [_vp, _vp, _u32, _vp, _vp, _vp],
+    "cnc_field_prepare_contracted": [_vp, _vp, _u32, _vp, _vp, _vp],
     "cnc_field_pack_all": [C.POINTER(FieldPack), _vp],
     "cnc_field_backward_chain_ordered_workspace": [C.POINTER(FieldBwd)],
     "cnc_field_backward_chain_ordered": [C.POINTER(FieldBwd), _vp, C.c_uint64, _vp],
@@ -243,6 +244,7 @@ CNC_ORDERED_KEY_BITS_SHIFT = 24
 CNC_FIELD_SH_FP16 = 1
 CNC_FIELD_MFMA_F16X3 = 2
 CNC_FIELD_WAVES4 = 8
+CNC_FIELD_CONTRACT = 16
 CNC_PACK_TRANSPOSE = 1
 CNC_PACK_ZERO_FIRST = 2
 CNC_VOLREND_ACCUMULATE = 1
@@ -263,7 +265,13 @@ def lib() -> C.CDLL:
                 "Build it with `python -m cnc_amd.build`.")
         L = C.CDLL(LIB_PATH)
         for name, argtypes in SIGNATURES.items():
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                # entries added without a signature change leave the version number alone (include/cnc_hip.h): a library
+                # built before them passes the version check below and is told by the symbol it lacks
+                raise RuntimeError(f"{LIB_PATH} does not export {name}: it was built from older sources; "
+                                   "rebuild it with `python -m cnc_amd.build`") from None
             fn.argtypes = argtypes
             fn.restype = RESTYPES.get(name, C.c_int)
         L.cnc_error_string.argtypes = [C.c_int]

@@ -25,6 +25,41 @@ __device__ __forceinline__ float4 sh4_quad(uint32_t q, float x, float y, float z
     }
 }
 
+// World position -> the position the encoders see, + the selector: the ONE definition behind cnc_field_prepare,
+// cnc_field_prepare_contracted and every form of cnc_field_fused_forward (the arithmetic is spelled out in
+// include/cnc_hip.h, CNC_FIELD_CONTRACT; tests/contract_twin.py restates it in NumPy).  `pw`: the sample's three world
+// coordinates in memory; `aext` = max - min.
+// contract = false: x = (p - min) / (max - min) (ngp.py:516-521).  contract = true: contract_to_unisphere (ngp.py:337-361,
+// ord = 2) on top of it.  Nothing fuses (-ffp-contract=off); `/` and sqrtf are correctly rounded under the build's flags
+// (hipcc's default; __fsqrt_rn is NOT: it is the native square root, 1 ulp).
+__device__ __forceinline__ bool field_unit_position(const float* __restrict__ pw, const float (&amin)[3], const float (&aext)[3],
+                                                    bool contract, float (&x)[3])
+{
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        x[a] = (pw[a] - amin[a]) / aext[a];
+        if (!contract) in = in && x[a] > 0.0f && x[a] < 1.0f;
+    }
+    if (contract) {
+        float c[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) c[a] = x[a] * 2.0f - 1.0f;
+        const float mag = sqrtf((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+        if (mag > 1.0f) {
+            const float k = 2.0f - 1.0f / mag;
+#pragma unroll
+            for (int a = 0; a < 3; a++) c[a] = k * (c[a] / mag);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            x[a] = c[a] / 4.0f + 0.5f;
+            in = in && x[a] > 0.0f && x[a] < 1.0f;
+        }
+    }
+    return in;
+}
+
 // tiny-cuda-nn stores its encodings as half (CNC_FIELD_SH_FP16, include/cnc_hip.h)
 __device__ __forceinline__ float round_through_half(float v) { return __half2float(__float2half_rn(v)); }
 

@@ -31,7 +31,9 @@
 
 namespace cnc {
 
-template <uint32_t F, int NT, bool RGB>
+// CONTRACT (CNC_FIELD_CONTRACT): the unbounded field's map of the position.  A template parameter, not a run-time test: the
+// test cost the bounded kernels registers (profiles/unbounded_field.md).
+template <uint32_t F, int NT, bool RGB, bool CONTRACT = false>
 __global__ __launch_bounds__(64, 2) void k_field_fused(FusedFieldArgs p)
 {
     extern __shared__ float lds[];
@@ -51,17 +53,10 @@ __global__ __launch_bounds__(64, 2) void k_field_fused(FusedFieldArgs p)
     for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const uint32_t row0 = tile * 32, row = row0 + i;
         const bool     live = row < n_rows;
-        // unit-cube position and selector of sample i (k_field_prepare: same expression)
+        // unit-cube position and selector of sample i (k_field_prepare: same helper)
         float xu[3] = {-1.0f, -1.0f, -1.0f};
         bool  sel = live;
-        if (live) {
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                const float v = (p.pos[(size_t)row * 3 + a] - amin[a]) / aext[a];
-                xu[a] = v;
-                sel = sel && v > 0.0f && v < 1.0f;
-            }
-        }
+        if (live) sel = field_unit_position(p.pos + (size_t)row * 3, amin, aext, CONTRACT, xu);
         [[maybe_unused]] const uint64_t selmask = __ballot(sel);          // bit r (< 32) = selector of sample r
 
         // ---- layer 1, chunk by chunk ----
@@ -188,8 +183,9 @@ __global__ __launch_bounds__(64, 2) void k_field_fused(FusedFieldArgs p)
 using FieldKernel = void (*)(FusedFieldArgs);
 
 template <uint32_t F, int NT>
-static FieldKernel exact_kernel(bool rgb)
+static FieldKernel exact_kernel(bool rgb, bool contract)
 {
+    if (contract) return rgb ? k_field_fused<F, NT, true, true> : k_field_fused<F, NT, false, true>;
     return rgb ? k_field_fused<F, NT, true> : k_field_fused<F, NT, false>;
 }
 
@@ -242,6 +238,7 @@ extern "C" int cnc_field_fused_forward(const cnc_fused_field_t* f, const float* 
     }
     p.density = density; p.rgb = rgb;
     p.sh_fp16 = (f->flags & CNC_FIELD_SH_FP16) ? 1u : 0u;
+    const bool contract = (f->flags & CNC_FIELD_CONTRACT) != 0;
     // the fp16 form is the two-wave kernel (field_fused2.hip): 16x16x32 fragments, head input [SH4 | raw density | geo]
     const bool f16x3 = (f->flags & CNC_FIELD_MFMA_F16X3) != 0;
     p.nk16_1 = p.nkb1 / 2;
@@ -273,19 +270,19 @@ extern "C" int cnc_field_fused_forward(const cnc_fused_field_t* f, const float* 
     }
     hipStream_t s = (hipStream_t)stream;
     if (f16x3) {
-        const int rc = launch_field_fused_w2(p, want_rgb, F, H, (f->flags & CNC_FIELD_WAVES4) ? 4 : 3, s);
+        const int rc = launch_field_fused_w2(p, want_rgb, contract, F, H, (f->flags & CNC_FIELD_WAVES4) ? 4 : 3, s);
         if (rc != CNC_OK || saving) return rc;              // the saving variant saturates: nothing runs behind it
     }
     // the exact form: the whole call without the fp16 flag, the guard's conditional fallback with it
     p.only_if_flagged = f16x3 ? 1u : 0u;
     FieldKernel kern = nullptr;
     switch (F * 10 + NT) {
-    case 85: kern = exact_kernel<8, 5>(want_rgb); break;
-    case 82: kern = exact_kernel<8, 2>(want_rgb); break;
-    case 45: kern = exact_kernel<4, 5>(want_rgb); break;
-    case 42: kern = exact_kernel<4, 2>(want_rgb); break;
-    case 25: kern = exact_kernel<2, 5>(want_rgb); break;
-    default: kern = exact_kernel<2, 2>(want_rgb); break;
+    case 85: kern = exact_kernel<8, 5>(want_rgb, contract); break;
+    case 82: kern = exact_kernel<8, 2>(want_rgb, contract); break;
+    case 45: kern = exact_kernel<4, 5>(want_rgb, contract); break;
+    case 42: kern = exact_kernel<4, 2>(want_rgb, contract); break;
+    case 25: kern = exact_kernel<2, 5>(want_rgb, contract); break;
+    default: kern = exact_kernel<2, 2>(want_rgb, contract); break;
     }
     const size_t lds_bytes = (want_rgb ? 32 * (H + kPadH) : 32 * kChunkPitch) * sizeof(float);
     // The grid is what is RESIDENT at once (the waves loop over the tiles): registers allow 8 one-wave workgroups per

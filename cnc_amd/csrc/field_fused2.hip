@@ -97,7 +97,8 @@ __device__ __forceinline__ void acc_to_planes(half_t* __restrict__ d_hi, half_t*
 // MODE 0: the gradient-free evaluator.  1 (density, test hook): + the first layer's input rows into p.dbg_features.
 // 2 (colour): the gradient pass's forward — + everything the backward reads into p.save (FieldSave), rows [n_live, N)
 // evaluated as points outside the box, values beyond fp16's range saturated instead of recomputed.
-template <uint32_t F, int NT, bool RGB, int WPE, int MODE = 0>
+// CONTRACT (CNC_FIELD_CONTRACT): the unbounded field's map of the position, in every MODE.
+template <uint32_t F, int NT, bool RGB, int WPE, int MODE = 0, bool CONTRACT = false>
 __global__ __launch_bounds__(128, WPE) void k_field_fused16w2(FusedFieldArgs p)
 {
     constexpr bool DUMP = MODE == 1, SAVE = MODE == 2;
@@ -146,14 +147,7 @@ __global__ __launch_bounds__(128, WPE) void k_field_fused16w2(FusedFieldArgs p)
         const bool     live_in = SAVE ? frow < p.save.n_live : live;         // ... and has a position / direction
         float xu[3] = {-1.0f, -1.0f, -1.0f};
         bool  sel = live_in;
-        if (live_in) {
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                const float v = (p.pos[(size_t)frow * 3 + a] - amin[a]) / aext[a];
-                xu[a] = v;
-                sel = sel && v > 0.0f && v < 1.0f;
-            }
-        }
+        if (live_in) sel = field_unit_position(p.pos + (size_t)frow * 3, amin, aext, CONTRACT, xu);
         if constexpr (SAVE) {
             if (live && fq == 0) {                                           // what k_field_prepare writes, + the plane pairs
                 p.save.selector[frow] = sel ? 1 : 0;
@@ -413,7 +407,8 @@ __global__ __launch_bounds__(256) void k_field_pack_all(PackAllArgs a)
 
 // Launch of the two-wave kernels (called by cnc_field_fused_forward, field_fused.hip).  waves_per_simd: 3 or 4 (the
 // register budget the variant was compiled for; the caller's choice, measured in DESIGN.md §4.5).
-int launch_field_fused_w2(const FusedFieldArgs& p, bool rgb, uint32_t F, uint32_t H, uint32_t waves_per_simd, hipStream_t s)
+int launch_field_fused_w2(const FusedFieldArgs& p, bool rgb, bool contract, uint32_t F, uint32_t H, uint32_t waves_per_simd,
+                          hipStream_t s)
 {
     const uint32_t NT = H / 32, tiles = (p.N + 31u) / 32u;
     if (p.n_units > kMaxUnits) return CNC_ERR_UNSUPPORTED;
@@ -426,27 +421,33 @@ int launch_field_fused_w2(const FusedFieldArgs& p, bool rgb, uint32_t F, uint32_
         rc = resident_grid(kern, 128, lds_bytes, 16, &resident);
         if (rc == CNC_OK) hipLaunchKernelGGL(kern, dim3(tiles < resident ? tiles : resident), dim3(128), lds_bytes, s, p);
     };
-#define CNC_W2_W(FV, NTV, RGBV)                                                \
-    do {                                                                       \
-        if (waves_per_simd >= 4) launch(k_field_fused16w2<FV, NTV, RGBV, 4>); \
-        else launch(k_field_fused16w2<FV, NTV, RGBV, 3>);                      \
+#define CNC_W2_W(FV, NTV, RGBV, CV)                                                  \
+    do {                                                                             \
+        if (waves_per_simd >= 4) launch(k_field_fused16w2<FV, NTV, RGBV, 4, 0, CV>); \
+        else launch(k_field_fused16w2<FV, NTV, RGBV, 3, 0, CV>);                     \
     } while (0)
-#define CNC_W2_RGB(FV, NTV)                                                       \
-    do {                                                                          \
-        if (p.dbg_features) launch(k_field_fused16w2<FV, NTV, false, 3, 1>);      \
-        else if (p.save.feat) launch(k_field_fused16w2<FV, NTV, true, 3, 2>);     \
-        else if (rgb) CNC_W2_W(FV, NTV, true);                                    \
-        else CNC_W2_W(FV, NTV, false);                                            \
+#define CNC_W2_RGB(FV, NTV, CV)                                                       \
+    do {                                                                              \
+        if (p.dbg_features) launch(k_field_fused16w2<FV, NTV, false, 3, 1, CV>);      \
+        else if (p.save.feat) launch(k_field_fused16w2<FV, NTV, true, 3, 2, CV>);     \
+        else if (rgb) CNC_W2_W(FV, NTV, true, CV);                                    \
+        else CNC_W2_W(FV, NTV, false, CV);                                            \
     } while (0)
-#define CNC_W2_NT(FV)                   \
-    do {                                \
-        if (NT == 5) CNC_W2_RGB(FV, 5); \
-        else CNC_W2_RGB(FV, 2);         \
+#define CNC_W2_C(FV, NTV)                         \
+    do {                                          \
+        if (contract) CNC_W2_RGB(FV, NTV, true);  \
+        else CNC_W2_RGB(FV, NTV, false);          \
+    } while (0)
+#define CNC_W2_NT(FV)                 \
+    do {                              \
+        if (NT == 5) CNC_W2_C(FV, 5); \
+        else CNC_W2_C(FV, 2);         \
     } while (0)
     if (F == 8) CNC_W2_NT(8);
     else if (F == 4) CNC_W2_NT(4);
     else CNC_W2_NT(2);
 #undef CNC_W2_NT
+#undef CNC_W2_C
 #undef CNC_W2_RGB
 #undef CNC_W2_W
     if (rc != CNC_OK) return rc;

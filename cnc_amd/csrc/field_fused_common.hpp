@@ -648,6 +648,7 @@ static int resident_grid(Kern kern, uint32_t block, size_t lds_bytes, uint32_t c
 }
 
 // field_fused2.hip: the two-waves-per-tile kernels
-int launch_field_fused_w2(const FusedFieldArgs& p, bool rgb, uint32_t F, uint32_t H, uint32_t waves_per_simd, hipStream_t s);
+int launch_field_fused_w2(const FusedFieldArgs& p, bool rgb, bool contract, uint32_t F, uint32_t H, uint32_t waves_per_simd,
+                          hipStream_t s);
 
 }  // namespace cnc

@@ -5,7 +5,7 @@
 //   :527-535  density_before_activation, base_mlp_out = split(h, [1, geo]);  density = trunc_exp(d - 1) * selector
 //   :540-547  d = SH4((dir + 1) / 2)  [tiny-cuda-nn, restated in closed form];  h = cat([d, base_mlp_out])
 //   :583-599  embed(x) = [x | sin(2^k x) | cos(2^k x)], k = 0..9  (the Embedder's loop over frequencies and functions)
-// Here:  k_field_prepare  positions -> unit-cube positions + selector
+// Here:  k_field_prepare  positions -> unit-cube positions + selector (<true>: through the unisphere contraction, :337-361)
 //        k_field_sinusoid [x | sin(f_k x) | cos(f_k x) | zero padding] into columns of the base MLP's input matrix
 //        k_field_post     base MLP output [N, 1 + geo] (+ view directions) -> density [N], head input [N, ld]
 //                         ( = [SH4(dir) | geo features | zero padding], no cat, no split)
@@ -17,19 +17,23 @@
 
 namespace cnc {
 
+// CONTRACT: the unbounded field's map of the position (field_unit_position, field_common.hpp)
+template <bool CONTRACT>
 __global__ __launch_bounds__(256) void k_field_prepare(const float* __restrict__ pos, const float* __restrict__ aabb,
                                                        uint32_t N, float* __restrict__ x_unit,
                                                        uint8_t* __restrict__ selector)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    bool in = true;
+    float amin[3], aext[3], x[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        const float v = (pos[(size_t)i * 3 + a] - aabb[a]) / (aabb[3 + a] - aabb[a]);
-        x_unit[(size_t)i * 3 + a] = v;
-        in = in && v > 0.0f && v < 1.0f;
+        amin[a] = aabb[a];
+        aext[a] = aabb[3 + a] - aabb[a];
     }
+    const bool in = field_unit_position(pos + (size_t)i * 3, amin, aext, CONTRACT, x);
+#pragma unroll
+    for (int a = 0; a < 3; a++) x_unit[(size_t)i * 3 + a] = x[a];
     selector[i] = in ? 1 : 0;
 }
 
@@ -224,7 +228,17 @@ extern "C" int cnc_field_prepare(const float* positions, const float* aabb, uint
 {
     if (N == 0) return CNC_OK;
     if (!positions || !aabb || !x_unit || !selector) return CNC_ERR_INVALID_VALUE;
-    hipLaunchKernelGGL(k_field_prepare, dim3(div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, positions, aabb, N,
+    hipLaunchKernelGGL(k_field_prepare<false>, dim3(div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, positions, aabb, N,
+                       x_unit, selector);
+    return launch_status();
+}
+
+extern "C" int cnc_field_prepare_contracted(const float* positions, const float* aabb, uint32_t N, float* x_unit,
+                                            uint8_t* selector, void* stream)
+{
+    if (N == 0) return CNC_OK;
+    if (!positions || !aabb || !x_unit || !selector) return CNC_ERR_INVALID_VALUE;
+    hipLaunchKernelGGL(k_field_prepare<true>, dim3(div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, positions, aabb, N,
                        x_unit, selector);
     return launch_status();
 }

@@ -44,11 +44,25 @@ trunc_exp = _TruncExp.apply
 
 
 def contract_to_unisphere(x, aabb, ord: Union[str, int] = 2, eps: float = 1e-6, derivative: bool = False):
-    """mip-NeRF-360 contraction of unbounded space into [0,1]^3 (ngp.py:337-361)."""
+    """mip-NeRF-360 contraction of unbounded space into [0,1]^3 (ngp.py:337-361).
+
+    For ord = 2 on positions that carry no gradient the norm is spelled sqrt((x0 x0 + x1 x1) + x2 x2), the kernels' order
+    (include/cnc_hip.h, CNC_FIELD_CONTRACT): every step is then one float32 operation in the order the kernels use, and
+    this op chain (`fused_unbounded=False`, host tensors) sees the coordinates they see.  `torch.linalg.norm` sums the
+    squares in its own order and lands up to 2 ulp away (1.2e-7) — nothing for the outputs, but the sinusoids multiply
+    a coordinate by up to 2^9 and a ReLU of the first layer within that of zero then flips: about one sample in 4101 at
+    H = 160, 1 % of its gradient rows' scale (tests/test_gpu_field_unbounded.py::test_against_the_op_chain)."""
     aabb_min, aabb_max = torch.split(aabb, 3, dim=-1)
     x = (x - aabb_min) / (aabb_max - aabb_min)
     x = x * 2 - 1
-    mag = torch.linalg.norm(x, ord=ord, dim=-1, keepdim=True)
+    if ord == 2 and not (torch.is_grad_enabled() and x.requires_grad):
+        sq = x * x
+        s = sq[..., 0:1]
+        for a in range(1, x.shape[-1]):
+            s = s + sq[..., a:a + 1]
+        mag = torch.sqrt(s)
+    else:       # (with gradients: linalg.norm's subgradient at the box centre, where sqrt's is 0 / 0)
+        mag = torch.linalg.norm(x, ord=ord, dim=-1, keepdim=True)
     mask = mag.squeeze(-1) > 1
     if derivative:
         dev = (2 * mag - 1) / mag ** 2 + 2 * x ** 2 * (1 / mag ** 3 - (2 * mag - 1) / mag ** 4)
@@ -345,13 +359,20 @@ class FusedFieldForward:
 
     @staticmethod
     def supported(field) -> bool:
+        """The BOUNDED shape table: `shapes_ok` for a field with a box.  (The routes ask `shapes_ok`: an unbounded field
+        takes the same kernels with CNC_FIELD_CONTRACT.)"""
+        return FusedFieldForward.shapes_ok(field) and not field.unbounded
+
+    @staticmethod
+    def shapes_ok(field) -> bool:
+        """The model's shapes are ones the fused kernels are built for, bounded or not."""
         mb = field.mlp_base
         encs = mb._encoders()
         F_ = encs[0].n_features
         H = mb.network[0].out_features
         geo = field.geo_feat_dim
         nt2 = 3 if H == 160 else 2
-        return (field.use_viewdirs and geo > 0 and not field.unbounded and field.num_dim == 3
+        return (field.use_viewdirs and geo > 0 and field.num_dim == 3
                 and field.density_activation is _default_density_activation
                 and mb.embed_fn is not None and mb._freqs is not None
                 and all(e.ste_binary and e.fused_ste and e.bitplane and e.n_features == F_ for e in encs)
@@ -467,6 +488,8 @@ class FusedFieldForward:
             waves = f.fused_field_waves or (3 if want_rgb else 4)
             if waves >= 4:
                 flags |= _lib.CNC_FIELD_WAVES4
+        if f.unbounded:
+            flags |= _lib.CNC_FIELD_CONTRACT       # contract_to_unisphere inside the kernel (include/cnc_hip.h)
         st.flags = flags
         self._call_id = self._call_id % 0xFFFFFFF0 + 1
         st.guard, st.call_id, st.pack_id = buf["guard"].data_ptr(), self._call_id, self._pack_id
@@ -760,6 +783,10 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         self.fused_chain = fused_features and os.environ.get("CNC_FUSED_CHAIN", "1") == "1"
         # ... and its forward as the fused evaluator in its saving form (`_FieldTrain`; CNC_FUSED_TRAIN=0: library GEMMs)
         self.fused_train = self.fused_chain and os.environ.get("CNC_FUSED_TRAIN", "1") == "1"
+        # an unbounded field (`unbounded=True`: contract_to_unisphere, ngp.py:337-361) on the same kernels, the contraction
+        # applied inside them (CNC_FIELD_CONTRACT, cnc_field_prepare_contracted); CNC_FUSED_UNBOUNDED=0 / False: the torch op
+        # chain for the contraction and everything behind it, as before — for A/B timing and as the tests' baseline
+        self.fused_unbounded = os.environ.get("CNC_FUSED_UNBOUNDED", "1") == "1"
         self._guard_seen = 1
         self._guard_host = self._guard_evt = self._guard_ids = None       # `snapshot_range_guard`
         # the five weight gradients as one kernel (cnc_field_weight_grads; CNC_FUSED_WGRAD=0: split-K library GEMMs)
@@ -807,7 +834,8 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         print("embedding_params updated!")
 
     def _glue_ok(self, x):
-        return (self.fused_glue and x.is_cuda and x.dtype == torch.float32 and not self.unbounded and self.num_dim == 3
+        return (self.fused_glue and x.is_cuda and x.dtype == torch.float32 and self.num_dim == 3
+                and (self.fused_unbounded or not self.unbounded)
                 and self.density_activation is _default_density_activation and 1 + self.geo_feat_dim <= 128)
 
     def invalidate_caches(self):
@@ -819,7 +847,7 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         if not (self.fused_chain and torch.is_grad_enabled() and x_unit.is_cuda and self.mlp_base._can_fuse(x_unit)):
             return False
         if self._chain_supported is None:
-            self._chain_supported = bool(FusedFieldForward.supported(self)
+            self._chain_supported = bool(FusedFieldForward.shapes_ok(self)
                                          and sum(e.n_output_dims for e in self.mlp_base._encoders()) % 4 == 0
                                          and sum(e.n_output_dims for e in self.mlp_base._encoders()) <= 192
                                          and (1 + self.geo_feat_dim + 31) // 32 * 32 <= self.mlp_base.network[0].out_features
@@ -844,7 +872,7 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         if not self._chain_ok(positions.reshape(-1, 3)):
             return False
         if self._field_fused is None:
-            self._field_fused = FusedFieldForward(self) if FusedFieldForward.supported(self) else False
+            self._field_fused = FusedFieldForward(self) if FusedFieldForward.shapes_ok(self) else False
         return bool(self._field_fused)
 
     def check_range_guard(self) -> bool:
@@ -946,16 +974,18 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         return (n + g - 1) // g * g
 
     def _prepare(self, x):
-        """(unit-cube positions [N,3], selector u8 [Np], Np) of N world positions: one kernel.  Np =
-        `_bucket_rows(N)` (when the base network can take extra rows); the selector of the rows of padding is 0."""
+        """(unit-cube positions [N,3] — contracted for an unbounded field —, selector u8 [Np], Np) of N world positions:
+        one kernel.  Np = `_bucket_rows(N)` (when the base network can take extra rows); the selector of the rows of
+        padding is 0."""
         from . import _lib
         p = x.reshape(-1, 3).contiguous()
         N = p.shape[0]
         Np = self._bucket_rows(N) if self.mlp_base._can_fuse(p) else N
         x_unit = torch.empty_like(p)
         selector = torch.empty(Np, dtype=torch.uint8, device=p.device)
-        _lib.check(_lib.lib().cnc_field_prepare(p.data_ptr(), self.aabb.contiguous().data_ptr(), N, x_unit.data_ptr(),
-                                                selector.data_ptr(), _lib.stream(p.device)), "field_prepare")
+        prepare = _lib.lib().cnc_field_prepare_contracted if self.unbounded else _lib.lib().cnc_field_prepare
+        _lib.check(prepare(p.data_ptr(), self.aabb.contiguous().data_ptr(), N, x_unit.data_ptr(),
+                           selector.data_ptr(), _lib.stream(p.device)), "field_prepare")
         if Np != N:
             selector[N:].zero_()
         return x_unit, selector, Np
@@ -966,7 +996,7 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         if torch.is_grad_enabled() or not self.fused_field or not self._glue_ok(x):
             return None
         if self._field_fused is None:
-            self._field_fused = FusedFieldForward(self) if FusedFieldForward.supported(self) else False
+            self._field_fused = FusedFieldForward(self) if FusedFieldForward.shapes_ok(self) else False
         return self._field_fused or None
 
     def query_density(self, x, return_feat: bool = False):

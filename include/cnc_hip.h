@@ -925,6 +925,23 @@ int cnc_level_stats_backward(const double* sums, const int64_t* offsets_host, ui
  * positions, x_unit [N,3]; aabb 6 floats on the device; selector u8 [N].                             */
 int cnc_field_prepare(const float* positions, const float* aabb, uint32_t N, float* x_unit,
                       uint8_t* selector, void* stream);
+/* (ABI v33, added entry: no signature changed) The same for an UNBOUNDED field (`unbounded=True`, ngp.py:515-516):
+ * x_unit = contract_to_unisphere(positions, aabb) (ngp.py:337-361, ord = 2), selector = all(0 < x_unit < 1).
+ * Per sample, in float32, nothing fused, in exactly this order (sqrt and the divisions correctly rounded):
+ *     u_a = (p_a - min_a) / (max_a - min_a)        a = 0..2      (cnc_field_prepare's expression)
+ *     c_a = u_a * 2 - 1
+ *     s   = (c_0 c_0 + c_1 c_1) + c_2 c_2 ;  mag = sqrt(s)
+ *     if (mag > 1) { k = 2 - 1 / mag ;  c_a = k * (c_a / mag) }
+ *     x_a = c_a / 4 + 0.5
+ *     selector = all_a (0 < x_a && x_a < 1)
+ * One device function (field_unit_position, csrc/field_common.hpp) is behind both entry points and behind
+ * cnc_field_fused_forward with CNC_FIELD_CONTRACT; tests/contract_twin.py restates it in NumPy, bit for bit.  Same
+ * arguments and outputs as cnc_field_prepare.  The positions carry no gradient: nothing changes in any backward.
+ * (The version number did not move with this entry and CNC_FIELD_CONTRACT — it moves when a signature or a layout
+ * changes — so a library built before them still reports v33: the loader in cnc_amd/_lib.py tells such a library by
+ * the missing symbol and asks for a rebuild.)                                                                      */
+int cnc_field_prepare_contracted(const float* positions, const float* aabb, uint32_t N, float* x_unit,
+                                 uint8_t* selector, void* stream);
 /* base_out [N, ld_base] = [density_raw | geo features (geo_feat_dim)]  ->
  *   density [N]        = exp(density_raw - 1) * selector                          (ngp.py:527-535; nullable)
  *   head_in [N, ld_head] = [SH degree-4 (16) of dirs | geo features | zeros]       (ngp.py:540-547; nullable)
@@ -992,7 +1009,7 @@ typedef struct {
     uint32_t       n_freqs;            /* > 0 (the reference always embeds, ngp.py:433)                           */
     uint32_t       n_neurons;          /* H: 64 or 160                                                            */
     uint32_t       geo_feat_dim;       /* 1 + geo <= 64 (H = 64) / 96 (H = 160) and roundup8(16 + geo) <= H        */
-    uint32_t       flags;              /* CNC_FIELD_SH_FP16 | CNC_FIELD_MFMA_F16X3 | CNC_FIELD_WAVES4               */
+    uint32_t       flags;              /* CNC_FIELD_SH_FP16 | CNC_FIELD_MFMA_F16X3 | CNC_FIELD_WAVES4 | CNC_FIELD_CONTRACT */
     /* ---- ABI v26 ---- */
     const void*    packed_weights16q[5];/* cnc_field_pack_all's Wq16 of the same five layers (CNC_FIELD_MFMA_F16X3)  */
     uint32_t*      guard;              /* 8 zero-initialised words on the device, owned by the caller for the life of
@@ -1024,6 +1041,15 @@ typedef struct {
 #define CNC_FIELD_MFMA_F16X3 2u
 /* With CNC_FIELD_MFMA_F16X3: the variant compiled for four waves per SIMD (128 registers) instead of three (168).  */
 #define CNC_FIELD_WAVES4 8u
+/* (ABI v33, added flag: no signature or layout changed) The field is unbounded: where the kernels form the unit-cube
+ * position (p - min) / (max - min) they apply the unisphere contraction on top of it — the arithmetic of
+ * cnc_field_prepare_contracted, same device function — and the selector is taken of the contracted position.  Every
+ * form of the call: exact fp32 (the range guard's fallback included), the fp16 kernels at three and four waves per
+ * SIMD, debug_features, n_rows_dev, and the saving form, whose save.xyz / xy / xz / yz / selector then hold the
+ * CONTRACTED coordinates (what the encoders' backward reads); rows [n_live, N) stay a point outside the box.  The
+ * kernels are compiled twice, with and without the map: a run-time test of the flag cost the bounded kernels
+ * registers and spills (profiles/unbounded_field.md), and these are the kernels they were.                         */
+#define CNC_FIELD_CONTRACT 16u
 /* The fp16 range guard.  The three-product kernels split every operand into two halves; a hidden activation above
  * fp16's 65504, or a weight with |2^8 w| above it, would become inf / NaN silently.  Both are detected exactly, on the
  * device: a kernel that split such a value (or whose fragments cnc_field_pack_all stamped) writes call_id into guard[0],
