@@ -17,6 +17,9 @@ SIGNATURES = {
     "cnc_rans_encode_pm1_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
     "cnc_rans_decode_pm1_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "cnc_rans_check": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int64]),
+    # the coders' probability quantiser, for callers that store c1 themselves (occupancy_codec.py)
+    "cnc_rc_c1": (C.c_uint32, [C.c_float]),
+    "cnc_rans_c1": (C.c_uint32, [C.c_float]),
 }
 
 

@@ -223,6 +223,12 @@ SIGNATURES = {
     "cnc_rans_scratch_bytes": [C.POINTER(RansStream), _u32],
     "cnc_rans_encode_pm1": [C.POINTER(RansStream), _u32, _vp, C.c_uint64, _vp, _vp],
     "cnc_rans_decode_pm1": [C.POINTER(RansStream), _u32, _vp, _vp],
+    "cnc_occ_reduce": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "cnc_occ_rank_scratch_bytes": [_i64],
+    "cnc_occ_rank": [_vp, _i64, _i64, _vp, C.c_uint64, _vp, _vp],
+    "cnc_occ_emit": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "cnc_occ_probs": [_vp, _i64, _vp, _vp, _vp],
+    "cnc_occ_scatter": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
 }
 
 # entry points that return something other than a status code
@@ -231,7 +237,7 @@ RESTYPES = {"cnc_grid_encode_backward_binned_workspace": C.c_uint64,
             "cnc_grid_encode_backward_ordered_workspace": C.c_uint64, "cnc_bernoulli_bits_partials": C.c_uint32,
             "cnc_ctx_mlp_backward_ordered_workspace": C.c_uint64, "cnc_field_backward_chain_ordered_workspace": C.c_uint64,
             "cnc_relu_backward_bias_partials": C.c_uint32, "cnc_occupancy_coarse_words": C.c_uint32,
-            "cnc_rans_scratch_bytes": C.c_uint64}
+            "cnc_rans_scratch_bytes": C.c_uint64, "cnc_occ_rank_scratch_bytes": C.c_uint64}
 
 CNC_FLAG_STE_BINARY = 1
 CNC_FLAG_LEVELS_FINEST_FIRST = 2
@@ -252,6 +258,8 @@ CNC_VOLREND_FINALIZE = 2
 CNC_VERDICT_NONFINITE = 1
 CNC_VERDICT_RANGE_GUARD = 2
 CNC_VERDICT_MAX_TENSORS = 48
+CNC_OCC_STATUS_COUNT = 1
+CNC_OCC_STATUS_INDEX = 2
 ABI_VERSION = 33          # cnc_abi_version() of the library this table was written for
 
 

@@ -9,8 +9,9 @@ real file size:
     magic "CNC1" | u32 header_len | header JSON | payload sections (offsets in the header)
 
 sections: every arithmetic-coded table stream, the occupancy grid (arithmetic-coded with its own
-frequency), the radiance-field MLP tensors uniformly quantised to `mlp_bits` (13) bits and
-bit-packed, the context-model weights in fp32.
+frequency, or — `occupancy_coder="pyramid"`, the section then says `model: "pyramid1"` — context-coded
+from a pyramid of itself, occupancy_codec.py), the radiance-field MLP tensors uniformly quantised to
+`mlp_bits` (13) bits and bit-packed, the context-model weights in fp32.
 """
 from __future__ import annotations
 
@@ -58,8 +59,11 @@ def quantize_tensor(p: torch.Tensor, bits: int):
 
 def write_container(path: str, *, meta: Dict, table_streams: Dict[str, bytes], binaries: torch.Tensor,
                     field_mlp: Dict[str, torch.Tensor], context_state: Dict[str, torch.Tensor],
-                    mlp_bits: int = 13) -> int:
-    """Returns the file size in bytes."""
+                    mlp_bits: int = 13, occupancy_coder: str = "iid", coder: str = "host", symbols_per_lane=None) -> int:
+    """Returns the file size in bytes.  occupancy_coder: "iid" (one Bernoulli frequency, the host range coder) or
+    "pyramid" (occupancy_codec.encode_occupancy with `coder`, "host" or "device": the coder of the table streams)."""
+    if occupancy_coder not in ("iid", "pyramid"):
+        raise ValueError(f"occupancy_coder must be 'iid' or 'pyramid', got {occupancy_coder!r}")
     sections, payload = {}, io.BytesIO()
 
     def add(name, blob, **extra):
@@ -68,13 +72,25 @@ def write_container(path: str, *, meta: Dict, table_streams: Dict[str, bytes], b
 
     for name, blob in table_streams.items():
         add("table/" + name, blob)
-    # occupancy grid: Bernoulli(Pg) arithmetic code, what get_binary_vxl_size only estimates
-    occ = binaries.reshape(-1).to(torch.float32).cpu()
-    pg = float(occ.mean().clamp(1e-6, 1 - 1e-6))
-    with tempfile.TemporaryDirectory() as td:
-        f = os.path.join(td, "occ.b")
-        encoder(occ * 2 - 1, torch.full_like(occ, pg), f)
-        add("occupancy", open(f, "rb").read(), shape=list(binaries.shape), pg=pg)
+    if occupancy_coder == "pyramid":
+        from .occupancy_codec import levels_of
+        try:
+            levels_of(binaries.shape)
+        except ValueError:
+            occupancy_coder = "iid"      # a grid with an odd side has no pyramid: it keeps the Bernoulli section
+    if occupancy_coder == "pyramid":
+        from .occupancy_codec import encode_occupancy
+        blob, info = encode_occupancy(binaries, coder=coder, symbols_per_lane=symbols_per_lane)
+        info.pop("c1")                   # the payload holds the tables; the header does not repeat them
+        add("occupancy", blob, **info)
+    else:
+        # occupancy grid: Bernoulli(Pg) arithmetic code, what get_binary_vxl_size only estimates
+        occ = binaries.reshape(-1).to(torch.float32).cpu()
+        pg = float(occ.mean().clamp(1e-6, 1 - 1e-6))
+        with tempfile.TemporaryDirectory() as td:
+            f = os.path.join(td, "occ.b")
+            encoder(occ * 2 - 1, torch.full_like(occ, pg), f)
+            add("occupancy", open(f, "rb").read(), shape=list(binaries.shape), pg=pg)
     for name, p in field_mlp.items():
         q, lo, interval = quantize_tensor(p.detach().float(), mlp_bits)
         add("mlp/" + name, _pack_bits(q, mlp_bits), shape=list(p.shape), lo=lo, interval=interval, bits=mlp_bits)
@@ -87,6 +103,14 @@ def write_container(path: str, *, meta: Dict, table_streams: Dict[str, bytes], b
         fo.write(header)
         fo.write(payload.getvalue())
     return os.path.getsize(path)
+
+
+def section_sizes(path: str) -> Dict[str, int]:
+    """Bytes of every section of a container, from its header alone."""
+    with open(path, "rb") as fi:
+        assert fi.read(4) == MAGIC, "not a CNC1 container"
+        (hlen,) = struct.unpack("<I", fi.read(4))
+        return {name: int(s["size"]) for name, s in json.loads(fi.read(hlen))["sections"].items()}
 
 
 def read_container(path: str, device="cpu"):
@@ -108,6 +132,9 @@ def read_container(path: str, device="cpu"):
         data, s = get(name)
         if name.startswith("table/"):
             tables[name[6:]] = data
+        elif name == "occupancy" and "model" in s:
+            from .occupancy_codec import decode_occupancy
+            binaries = decode_occupancy(data, s, device)      # raises for a model it does not know and for device="cpu"
         elif name == "occupancy":
             n = int(np.prod(s["shape"]))
             with tempfile.TemporaryDirectory() as td:

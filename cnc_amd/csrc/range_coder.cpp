@@ -117,6 +117,8 @@ struct Interval {
 
 extern "C" int64_t cnc_rc_bound(int64_t n) { return 2 * n + 16; }
 
+extern "C" uint32_t cnc_rc_c1(float p_one) { return cdf_one(p_one); }
+
 extern "C" int64_t cnc_rc_encode_pm1(const float* p_one, const float* x_pm1, int64_t n,
                                      uint8_t* out, int64_t cap)
 {

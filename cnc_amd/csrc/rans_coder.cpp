@@ -49,6 +49,8 @@ int parse(const uint8_t* in, int64_t len, int64_t n, Header& h)
 
 }  // namespace
 
+extern "C" uint32_t cnc_rans_c1(float p_one) { return rans::c1_of(p_one); }
+
 extern "C" int64_t cnc_rans_bound(int64_t n, int64_t symbols_per_lane)
 {
     if (n < 0 || symbols_per_lane < 1) return -1;

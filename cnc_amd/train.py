@@ -59,6 +59,9 @@ def build_parser():
     ap.add_argument("--device-coder", dest="device_coder", action="store_true",
                     help="code the tables with the device entropy coder (interleaved rANS on the GPU, DESIGN.md §4.8) "
                          "instead of the host range coder; the .b files are then in the rans1 format")
+    ap.add_argument("--occupancy-coder", dest="occupancy_coder", choices=["iid", "pyramid"], default="iid",
+                    help="the container's occupancy section: one Bernoulli frequency for every cell (iid), or the grid "
+                         "coded from a pyramid of itself with the tables' coder (pyramid, DESIGN.md §4.9)")
     return ap
 
 
@@ -75,6 +78,7 @@ def make_config_and_data(args, device, rank=0, world=1):
               out_dir=args.out_dir or f"./bitstreams/{scene}", reproducible=bool(getattr(args, "reproducible", False)),
               guarded_step=bool(getattr(args, "guarded_step", False)),
               device_coder=bool(getattr(args, "device_coder", False)),
+              occupancy_coder=getattr(args, "occupancy_coder", "iid"),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0
@@ -163,6 +167,15 @@ def main(argv=None):
           f"size_codec={embed_bits_MB_codec}")
 
     sizes = tr.sizes_MB(embed_bits_MB_codec)
+    occ_note = ""
+    if tr.occupancy_coder_name() == "pyramid" and all(int(s) % 2 == 0 for s in tr.estimator.binaries.shape[1:]):
+        # the occupancy grid as the container would hold it: a coded section's size, not the reference's estimate
+        # (a grid with an odd side has no pyramid and keeps the estimate, as its container keeps the Bernoulli section)
+        from .occupancy_codec import encode_occupancy
+        blob, _ = encode_occupancy(tr.estimator.binaries, coder=tr.coder_name(), symbols_per_lane=cfg.symbols_per_lane)
+        occ_note = (f" (occupancy grid: pyramid1 section of {len(blob) / 1024:.2f} KB as coded, in place of the "
+                    f"{sizes['occupancy_grid'] * 1024:.2f} KB estimate)")
+        sizes["occupancy_grid"] = len(blob) / 1024.0 / 1024.0
     mlp = {n: p for n, p in tr.field.named_parameters() if "encoding" not in n}
     cols = [cfg.scene, r4(psnr_avg), r4(lpips_avg), r4(ssim_avg), r4(psnr_c), r4(lpips_c), r4(ssim_c),
             r4(embed_bits_MB), r4(embed_bits_MB_codec)]
@@ -174,7 +187,7 @@ def main(argv=None):
         p_q, l_q, s_q = evaluate(tr, cfg.test_views)
         total = embed_bits_MB_codec + sizes["context_models"] + sizes["occupancy_grid"] + MBs
         per_digit += [str(digit), r4(MBs), r4(p_q), r4(l_q), r4(s_q), r4(total)]
-        say(f"{digit}-bit MLP: psnr={p_q}, total size {total * 1024:.1f} KB")
+        say(f"{digit}-bit MLP: psnr={p_q}, total size {total * 1024:.1f} KB{occ_note}")
     cols += [r4(MBs_orig), r4(sizes["context_models"]), r4(sizes["occupancy_grid"])] + per_digit
     cols += [r4(elapsed), r4(encoding_time), r4(decoding_time)]
 

@@ -86,6 +86,9 @@ class TrainConfig:
     # the GPU in the "rans1" format instead of with the host range coder.  Also CNC_DEVICE_CODER=1.  Off by default.
     device_coder: bool = False
     symbols_per_lane: Optional[int] = None     # of the device coder; None = cnc_amd.context.DEVICE_CODER_SYMBOLS_PER_LANE
+    # the occupancy section of `save_container`: "iid" (one Bernoulli frequency for every cell) or "pyramid" (the grid coded
+    # from a pyramid of itself with the tables' coder, cnc_amd.occupancy_codec).  Also CNC_OCC_CODER=pyramid.
+    occupancy_coder: str = "iid"
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -904,6 +907,14 @@ class Trainer:
         on = bool(getattr(self.cfg, "device_coder", False)) or os.environ.get("CNC_DEVICE_CODER", "0") == "1"
         return "device" if on else "host"
 
+    def occupancy_coder_name(self) -> str:
+        """"pyramid" when this Trainer's containers code the occupancy grid with the pyramid model
+        (TrainConfig.occupancy_coder or CNC_OCC_CODER=pyramid), else "iid"."""
+        name = os.environ.get("CNC_OCC_CODER") or getattr(self.cfg, "occupancy_coder", "iid")
+        if name not in ("iid", "pyramid"):
+            raise ValueError(f"occupancy coder must be 'iid' or 'pyramid', got {name!r}")
+        return name
+
     @torch.no_grad()
     def encode(self, prefix: Optional[str] = None, coder: Optional[str] = None):
         os.makedirs(self.cfg.out_dir, exist_ok=True)
@@ -945,7 +956,7 @@ class Trainer:
     @torch.no_grad()
     def save_container(self, path: str) -> Dict[str, float]:
         """Encode the tables and write everything a decoder needs into one file; returns sizes in KB."""
-        from .container import write_container
+        from .container import section_sizes, write_container
         import tempfile
         with tempfile.TemporaryDirectory() as td:
             Pgs, est_MB, coded_MB, prefix = self.encode(os.path.join(td, "b"))
@@ -958,9 +969,14 @@ class Trainer:
                 "log2_hashmap_size_2D": self.cfg.log2_hashmap_size_2D}
         if self.coder_name() == "device":
             meta["coder"] = "rans1"       # the table streams' format; no key = the range coder's
+        occ = self.occupancy_coder_name()
         size = write_container(path, meta=meta, table_streams=streams, binaries=self.estimator.binaries,
-                               field_mlp=self._mlp_state(), context_state=self.context.state_dict())
-        return {"file_KB": size / 1024.0, "embeddings_KB": coded_MB * 1024.0, "estimate_KB": est_MB * 1024.0}
+                               field_mlp=self._mlp_state(), context_state=self.context.state_dict(), occupancy_coder=occ,
+                               coder=self.coder_name(), symbols_per_lane=getattr(self.cfg, "symbols_per_lane", None))
+        res = {"file_KB": size / 1024.0, "embeddings_KB": coded_MB * 1024.0, "estimate_KB": est_MB * 1024.0}
+        if occ == "pyramid":       # the section as written (the Bernoulli one still, for a grid with an odd side)
+            res["occupancy_KB"] = section_sizes(path)["occupancy"] / 1024.0
+        return res
 
     @torch.no_grad()
     def load_container(self, path: str) -> None:

@@ -23,6 +23,13 @@ extern "C" {
 /* Upper bound of the encoded size in bytes for n symbols (worst case 16 bits/symbol + tail). */
 int64_t cnc_rc_bound(int64_t n);
 
+/* The 16-bit quantity the pm1 coders derive from a probability: c1 = P(x=-1) * 2^16, what cnc_rc_encode_pm1 /
+ * cnc_rc_decode_pm1 narrow with (cnc_rc_c1) and what the rans1 coders code with (cnc_rans_c1, clamped to [1, 65535]).
+ * Exported so that a caller that stores c1 itself (the occupancy pyramid's tables) can check that the
+ * float it hands over gives that c1 back. */
+uint32_t cnc_rc_c1(float p_one);
+uint32_t cnc_rans_c1(float p_one);
+
 /* x_pm1[i] in {-1,+1} (any value > 0 codes as +1), p_one[i] = P(x=+1) in (0,1).
  * Returns the number of bytes written, or -1 if cap < cnc_rc_bound(n) was too small. */
 int64_t cnc_rc_encode_pm1(const float* p_one, const float* x_pm1, int64_t n, uint8_t* out,

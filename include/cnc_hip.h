@@ -1256,6 +1256,63 @@ int cnc_rans_encode_pm1(const cnc_rans_stream_t* streams, uint32_t n_streams, vo
  * zeros — and writes inside x[0, n).  Callers run cnc_rans_check (cnc_codec.h) on the host before they upload a file. */
 int cnc_rans_decode_pm1(const cnc_rans_stream_t* streams, uint32_t n_streams, int32_t* status_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (ABI v33, added entries: no signature changed) Context-coded occupancy grid, the "pyramid1" model
+ * (csrc/occ_pyramid.hip) — an extension: the reference estimates the grid's size under one Bernoulli
+ * frequency and stores nothing.  These entries build what the entropy coders above code; they code nothing themselves.
+ *
+ * Grids are bytes (non-zero = occupied) [n_grids, rx, ry, rz], C order.  Level k + 1 is the OR over the 2x2x2 blocks of
+ * level k.  The CANDIDATES of a level are the eight children of every occupied cell of its PARENT level, ordered by the
+ * parent's linear index, then by octant o = ox << 2 | oy << 1 | oz: candidate 8 rank(parent) + o, the rank being a
+ * prefix sum, so the order depends on the grid alone.  A candidate's context, from the parent level only (cells outside
+ * the grid are empty), d_a = +1 if the octant's bit on axis a is set, else -1:
+ *     near = occupied cells among P + d_a e_a (3), P + d_a e_a + d_b e_b (3), P + d (1)       0..7
+ *     far  = occupied cells among P - d_a e_a (3)                                             0..3
+ *     ctx  = near * 4 + far                                                                   0..31
+ * All pointers are DEVICE pointers; every call is stream-ordered, allocates nothing and keeps no state.
+ * ---------------------------------------------------------------------------------------- */
+/* bits of a status word (zeroed by the caller, OR-ed into by the calls below, read once when the caller is done) */
+#define CNC_OCC_STATUS_COUNT 1u   /* cnc_occ_rank: n_expected != 8 * occupied parents                                  */
+#define CNC_OCC_STATUS_INDEX 2u   /* cnc_occ_scatter: a candidate index outside the child level (nothing written for it) */
+
+/* Levels 1..levels (1 <= levels <= 4, every side a multiple of 2^levels) of `grid`, in one launch: a workgroup takes a
+ * 16^3 tile of level 0 into LDS and writes the tile's cells of every coarser level.  coarse: level 1, level 2, ...
+ * back to back, level k being [n_grids, rx >> k, ry >> k, rz >> k] bytes of 0 / 1.  n_grids rx ry rz < 2^31.          */
+int cnc_occ_reduce(const uint8_t* grid, int32_t n_grids, int32_t rx, int32_t ry, int32_t rz, int32_t levels,
+                   uint8_t* coarse, void* stream);
+
+/* Scratch of cnc_occ_rank for a parent level of n_parents cells (all grids): one word per 256 parents + 1; 0 for
+ * n_parents outside [1, 2^31).                                                                                       */
+uint64_t cnc_occ_rank_scratch_bytes(int64_t n_parents);
+
+/* Two launches: occupied parents per 256-parent block (ballot + popcount), then one workgroup scans the block sums.
+ * scratch (4-byte aligned) then holds the blocks' exclusive offsets and, in its last word, the number of occupied
+ * parents: the level has 8 times that many candidates.  n_expected >= 0 (a decode: the header's candidate count) is
+ * compared with it on the device and CNC_OCC_STATUS_COUNT raised in *status when they differ; n_expected < 0: no check,
+ * status may be NULL.                                                                                                */
+int cnc_occ_rank(const uint8_t* parent, int64_t n_parents, int64_t n_expected, void* scratch, uint64_t scratch_bytes,
+                 uint32_t* status, void* stream);
+
+/* One lane per (occupied parent, octant).  parent: [n_grids, px, py, pz], rank_scratch: what cnc_occ_rank left for it.
+ * Candidate i < n_cap gets idx[i] = its linear index in the child level [n_grids, 2 px, 2 py, 2 pz] (nullable) and
+ * ctx[i]; with `child` and `sym` (an encode) also sym[i] = +1.0f / -1.0f for an occupied / empty child, the coders'
+ * symbol.  Candidates at or past n_cap are dropped: nothing outside idx / ctx / sym [0, n_cap) is written whatever the
+ * grid holds.  hist (nullable, needs `child`): 64 words, zeroed by the caller, [ctx][0] += occupied children,
+ * [ctx][1] += candidates — counted per wave with ballots in LDS, one integer atomic per (workgroup, context): no float
+ * is ever added, so the sums have no order.  n_grids px py pz <= (2^31 - 1) / 8.                                     */
+int cnc_occ_emit(const uint8_t* parent, const uint8_t* child, int32_t n_grids, int32_t px, int32_t py, int32_t pz,
+                 const void* rank_scratch, int64_t n_cap, int32_t* idx, uint8_t* ctx, float* sym, uint32_t* hist,
+                 void* stream);
+
+/* p[i] = table[ctx[i] & 31], i < n: the probability the coders take for candidate i from the level's 32-entry table. */
+int cnc_occ_probs(const uint8_t* ctx, int64_t n, const float* table, float* p, void* stream);
+
+/* A decoded level: child[idx[i]] = 1 where sym[i] > 0, for i < min(n_cap, 8 * occupied parents) — the smaller of the
+ * header's count and the parent level's (rank_scratch, n_parents as given to cnc_occ_rank).  The caller zeroes `child`
+ * (n_child bytes) first.  An idx outside [0, n_child) writes nothing and raises CNC_OCC_STATUS_INDEX.                */
+int cnc_occ_scatter(const float* sym, const int32_t* idx, int64_t n_cap, const void* rank_scratch, int64_t n_parents,
+                    uint8_t* child, int64_t n_child, uint32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
