@@ -181,6 +181,8 @@ SIGNATURES = {
     "cnc_ray_window_next": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _i32, _u32, _vp],
     "cnc_interval_edges_to_samples": [_vp] * 9 + [_u32, _vp],
     "cnc_pack_bounds": [_vp, _i64, _vp, _vp, _i64, _vp],
+    "cnc_distortion_forward": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _u32, _vp],
+    "cnc_distortion_backward": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "cnc_level_stats_forward": [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
     "cnc_level_stats_backward": [_vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _vp, _vp],
     "cnc_field_prepare": [_vp, _vp, _u32, _vp, _vp, _vp],

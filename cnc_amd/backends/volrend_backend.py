@@ -110,6 +110,50 @@ def volrend_backward(starts, counts, t_starts, t_ends, rgbs, weights, trans, alp
     return g_sig, g_rgb
 
 
+def _distortion_layout(starts, counts, t_starts, t_ends, weights):
+    """Checked inputs of the two distortion entry points -> (n_rays, row_len, leading shape of the per-ray result).
+    `starts` / `counts` None: the batched layout, rows along the last axis of (..., S) tensors."""
+    _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(weights, "weights")
+    if t_starts.shape != weights.shape or t_ends.shape != weights.shape:
+        raise RuntimeError("weights, t_starts and t_ends must have the same shape")
+    if (starts is None) != (counts is None):
+        raise RuntimeError("chunk_starts and chunk_cnts go together")
+    if starts is None:
+        if weights.dim() < 1:
+            raise RuntimeError("batched weights must have shape (..., S)")
+        lead, row_len = tuple(weights.shape[:-1]), int(weights.shape[-1])
+        n_rays = 1
+        for d in lead:
+            n_rays *= int(d)
+        return n_rays, row_len, lead
+    _i64(starts, "chunk_starts"), _i64(counts, "chunk_cnts")
+    if weights.dim() != 1 or starts.shape != counts.shape or starts.dim() != 1:
+        raise RuntimeError("flattened samples are (N,) tensors with (n_rays,) chunk_starts / chunk_cnts")
+    return int(starts.shape[0]), 0, (int(starts.shape[0]),)
+
+
+def distortion_forward(starts, counts, t_starts, t_ends, weights):
+    """The distortion loss per ray (cnc_distortion_forward): float32 [n_rays] for flattened samples delimited by
+    `starts` / `counts`, or weights.shape[:-1] for batched (..., S) tensors (`starts` = `counts` = None)."""
+    n_rays, row_len, lead = _distortion_layout(starts, counts, t_starts, t_ends, weights)
+    loss = torch.empty(lead, dtype=torch.float32, device=weights.device)
+    check(_lib.lib().cnc_distortion_forward(ptr(starts), ptr(counts), row_len, _p(t_starts), _p(t_ends), _p(weights),
+                                            _p(loss), n_rays, stream(weights.device)), "distortion_forward")
+    return loss
+
+
+def distortion_backward(starts, counts, t_starts, t_ends, weights, grad_loss):
+    """dL/dweights (the shape of `weights`) from dL/dloss per ray (cnc_distortion_backward); t is a constant."""
+    n_rays, row_len, lead = _distortion_layout(starts, counts, t_starts, t_ends, weights)
+    _f32(grad_loss, "grad_loss")
+    if tuple(grad_loss.shape) != lead:
+        raise RuntimeError(f"grad_loss must have shape {lead}")
+    g_w = torch.empty_like(weights)
+    check(_lib.lib().cnc_distortion_backward(ptr(starts), ptr(counts), row_len, _p(t_starts), _p(t_ends), _p(weights),
+                                             _p(grad_loss), _p(g_w), n_rays, stream(weights.device)), "distortion_backward")
+    return g_w
+
+
 def render_visibility(starts, counts, values, t_starts=None, t_ends=None, *, from_alpha=False,
                       early_stop_eps=1e-4, alpha_thre=0.0, alpha_thre_cap=None, want_kept=True):
     """(mask uint8 [N], kept int64 [n_rays] or None)."""

@@ -89,6 +89,10 @@ class TrainConfig:
     # the occupancy section of `save_container`: "iid" (one Bernoulli frequency for every cell) or "pyramid" (the grid coded
     # from a pyramid of itself with the tables' coder, cnc_amd.occupancy_codec).  Also CNC_OCC_CODER=pyramid.
     occupancy_coder: str = "iid"
+    # the distortion regulariser (cnc_amd.nerfacc.losses.distortion): the ray loss becomes mse + this weight
+    # times the mean over the batch's rays of mip-NeRF 360's interval-distortion loss on the rendered samples.  0 = off: the
+    # step makes exactly the calls it makes without it
+    distortion_weight: float = 0.0
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -686,7 +690,8 @@ class Trainer:
         with _gradsink.activate(self.sink_render):
             rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
                 self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
-                render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True)
+                render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
+                with_samples=c.distortion_weight > 0)
         self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event()
         # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
         # fused one is asked before the poll below can switch it off)
@@ -707,31 +712,52 @@ class Trainer:
         # world > 1: no rank leaves the step (the collective below must be entered by everyone; a rank without samples
         # adds a zero ray gradient), and the ray budget follows the all-reduced count of the step before
         mse = F.mse_loss(rgb, pixels)
+        # what is back-propagated wherever the mse was: the mse alone, or + the distortion regulariser (this rank's mean over
+        # its rays, like the mse; rays without samples count as 0).  The mse itself keeps feeding the statistics
+        ray_loss, distortion = mse, None
+        if c.distortion_weight > 0:
+            distortion = self._distortion(extra, len(pixels))
+            ray_loss = mse + c.distortion_weight * distortion
         range_guard = (ff._buffers["guard"], self.field._guard_seen, ff._pack_id) if guard_live else None
         if self.bucket is None:
-            bpp, mb, table_pieces = self._backward_single(step, mse, ctx_future, tables_fused)
+            bpp, mb, table_pieces = self._backward_single(step, ray_loss, ctx_future, tables_fused)
         else:
-            bpp, mb, table_pieces = self._backward_dp(step, mse, ctx_future, tables_fused, len(pixels), n_samples, range_guard)
+            bpp, mb, table_pieces = self._backward_dp(step, ray_loss, ctx_future, tables_fused, len(pixels), n_samples, range_guard)
         if sg is not None:
-            self._verdict(mse, bpp, range_guard, tables_fused)
+            self._verdict(mse, bpp, range_guard, tables_fused, distortion)
         self._update(step, table_pieces, tables_fused)
         if not want_stats:
             return {"n_rendering_samples": n_samples, "num_rays": len(pixels)}
         # the step's scalars in one device->host copy
-        mse_f, bpp_f, mb_f = torch.stack([mse.detach(), torch.as_tensor(bpp, device=mse.device).detach().float(),
-                                          torch.as_tensor(mb, device=mse.device).detach().float()]).tolist()
-        return {"mse": mse_f, "psnr": -10.0 * math.log10(max(mse_f, 1e-12)), "bpp": bpp_f,
-                "embed_bits_MB": mb_f, "n_rendering_samples": n_samples, "num_rays": len(pixels)}
+        scalars = [mse.detach(), torch.as_tensor(bpp, device=mse.device).detach().float(),
+                   torch.as_tensor(mb, device=mse.device).detach().float()]
+        if distortion is not None:
+            scalars.append(distortion.detach())
+        mse_f, bpp_f, mb_f, *dist_f = torch.stack(scalars).tolist()
+        stats = {"mse": mse_f, "psnr": -10.0 * math.log10(max(mse_f, 1e-12)), "bpp": bpp_f,
+                 "embed_bits_MB": mb_f, "n_rendering_samples": n_samples, "num_rays": len(pixels)}
+        if distortion is not None:
+            stats["distortion"] = dist_f[0]
+        return stats
 
-    def _backward_single(self, step, mse, ctx_future, tables_fused):
+    @staticmethod
+    def _distortion(extra, num_rays: int):
+        """Mean over the batch's rays of the distortion loss on the samples the render just composited (`with_samples`
+        extras): one kernel, and one more behind the render backward's root."""
+        from .nerfacc.losses import distortion
+        per_ray = distortion(extra["weights"], extra["t_starts"], extra["t_ends"], ray_indices=extra["ray_indices"],
+                             n_rays=num_rays, packed_info=extra["packed_info"])
+        return per_ray.sum() / float(max(num_rays, 1))
+
+    def _backward_single(self, step, ray_loss, ctx_future, tables_fused):
         """Single process: both backward passes in this step's schedule -> (bits per parameter, MB, the tables' pieces)."""
         c = self.cfg
         bpp, mb = 0.0, 0.0
         if ctx_future is not None:
-            (mse * self.loss_scale).backward()
+            (ray_loss * self.loss_scale).backward()
             self._prefetch(step)
             bpp, mb, _ = self._join_entropy_pass(ctx_future.result())
-        elif self.ctx_stream is not None and c.lmbda > 0 and mse.requires_grad:
+        elif self.ctx_stream is not None and c.lmbda > 0 and ray_loss.requires_grad:
             # The sequential schedule of the same idea (one host thread; the reference's order of random draws):
             #   render backward (main stream: few launches, GPU-heavy)
             #   || context forward + context backward (side stream: ~250 launches, host-bound forward)
@@ -739,12 +765,12 @@ class Trainer:
             # nonzero) wait for the side stream only.
             self._clear_grads()
             fork = torch.cuda.current_stream(self.device).record_event()
-            (mse * self.loss_scale).backward()
+            (ray_loss * self.loss_scale).backward()
             bpp, mb, _ = self._join_entropy_pass(self._context_pass(step, fork))
         else:
             # The plain schedule: one stream, one thread, ONE backward call over the joint loss (the reproducible mode and the
             # trajectory goldens are this)
-            loss = mse
+            loss = ray_loss
             if c.lmbda > 0:
                 bpp, mb = self._entropy_forward(step)
                 loss = loss + c.lmbda * bpp
@@ -760,7 +786,7 @@ class Trainer:
             self.planes_graph.flush(table_pieces=table_pieces)       # what autograd returned inside the planes' graph
         return bpp, mb, table_pieces
 
-    def _backward_dp(self, step, mse, ctx_future, tables_fused, num_rays, n_samples, range_guard):
+    def _backward_dp(self, step, ray_loss, ctx_future, tables_fused, num_rays, n_samples, range_guard):
         """Data parallel: the backward passes around the ray-loss gradient's all-reduce -> what `_backward_single` returns."""
         # The ray loss differs per rank, the entropy loss does not (same tables, same window draw on every rank): so only
         # the ray-loss gradient is exchanged, and its all-reduce runs on the communicator's stream WHILE the entropy pass is
@@ -775,8 +801,8 @@ class Trainer:
                 bpp, mb = self._entropy_forward(step)
             self._clear_grads()
         self._lagged_sample_count(num_rays, n_samples)
-        if mse.requires_grad:          # a rank whose rays met no sample has nothing to add (its peers do): the
-            (mse * self.loss_scale).backward()     # collective below must still be entered by everyone
+        if ray_loss.requires_grad:          # a rank whose rays met no sample has nothing to add (its peers do): the
+            (ray_loss * self.loss_scale).backward()     # collective below must still be entered by everyone
         if self.sink_render is not None:
             self.sink_render.flush()               # `.grad` = the bucket's views: the encoder scatters join it here
         if sg is not None:
@@ -820,7 +846,7 @@ class Trainer:
         A.bind(force=True)
         return bpp, mb, table_pieces
 
-    def _verdict(self, mse, bpp, range_guard, tables_fused) -> None:
+    def _verdict(self, mse, bpp, range_guard, tables_fused, distortion=None) -> None:
         """The guarded step's verdict, on the device and before any update."""
         # Scanned: every gradient the two library optimizers will read (the tables' pieces are not: DESIGN.md §13) and the
         # loss scalars; data parallel: what every rank holds alike — the bucket's summed non-table runs with the entropy
@@ -829,7 +855,8 @@ class Trainer:
         if A is None:
             scan = [p.grad for o in (self.opt, self.opt2) for g in o.param_groups for p in g["params"]
                     if p.grad is not None and id(p) not in self._table_ids]
-            scan += [t.detach().reshape(-1) for t in (mse, bpp) if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
+            scan += [t.detach().reshape(-1) for t in (mse, bpp, distortion)
+                     if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
             sg.scan(scan, range_guard=range_guard)
         else:
             sg.scan([A.flat[lo:hi] for lo, hi in A.runs_excluding(self._tables)] + [A.tail[1:2]])

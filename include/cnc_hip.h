@@ -674,6 +674,30 @@ int cnc_interval_edges_to_samples(const int64_t* iv_chunk_starts, const int64_t*
 int cnc_pack_bounds(const int64_t* ray_indices, int64_t n_samples, int64_t* first, int64_t* last,
                     int64_t n_rays, void* stream);
 
+/* (ABI v33, added entries: no signature changed) The interval-distortion loss of mip-NeRF 360 (Barron et al. 2022, eq. 15)
+ * per ray, one kernel per direction (the reference has no such term):
+ *   loss[ray] = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i,   m_i = (t_start_i + t_end_i) / 2,  d_i = t_end_i - t_start_i
+ * evaluated in float32 without subtracting prefix sums from each other:
+ *   g_i = m_i - m_{i-1} = 0.5 ((t_start_i - t_start_{i-1}) + (t_end_i - t_end_{i-1})),
+ *   A_i = sum_{j<i} w_j (m_i - m_j) through A_0 = 0, A_i = A_{i-1} + g_i (w_0 + .. + w_{i-1}),  B_i = sum_{j>i} w_j (m_j - m_i)
+ *   the same way back to front,  loss = sum_i w_i (2 A_i + w_i d_i / 3),  dloss/dw_i = 2 (A_i + B_i) + (2/3) w_i d_i.
+ * Layouts: chunk_starts / chunk_cnts i64 [n_rays] delimit each ray of the flattened samples (as above; gaps between the
+ * intervals of a ray are fine); BOTH NULL = the batched layout, ray r owns samples [r row_len, (r + 1) row_len) and
+ * 0 <= row_len < 2^31 (row_len is ignored otherwise).
+ * Preconditions: w_i >= 0 and midpoints that do not decrease along a ray.  Decreasing midpoints are a caller error and are
+ * NOT checked: the signed formula above is what comes out.  A ray without samples gives loss 0 (loss[ray] is written for
+ * every ray) and none of its (zero) samples is read or written; a ray of one sample gives w^2 d / 3.
+ * No gradient to t: t_starts / t_ends are constants of the loss (every sampler of this package draws them without
+ * gradients).  cnc_distortion_backward recomputes A and B from the inputs (nothing is saved by the forward) and writes
+ * grad_weights[s] = grad_loss[ray] * dloss/dw_s exactly once per sample of every ray, and nothing else; no atomics, so equal
+ * inputs give equal bits.  Rays of more than 1024 samples cost a further back-to-front walk per 1024 samples.           */
+int cnc_distortion_forward(const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t row_len,
+                           const float* t_starts, const float* t_ends, const float* weights, float* loss /* [n_rays] */,
+                           uint32_t n_rays, void* stream);
+int cnc_distortion_backward(const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t row_len,
+                            const float* t_starts, const float* t_ends, const float* weights,
+                            const float* grad_loss /* [n_rays] */, float* grad_weights, uint32_t n_rays, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Context-model heads and the Bernoulli rate  —  replace the ATen chains of examples/utils_bpp_acc.py
  * (context MLPs :378-393 applied at :561-566 / :689-692, hash fusion :567-572 / :693-701,
