@@ -449,12 +449,12 @@ class DeviceCoder:
         return outs
 
     def check(self):
-        """One host wait for every group decoded so far: raises if a lane of any stream did not end where it began."""
-        for status, names in self._status:
-            bad = [n for n, s in zip(names, status.cpu().tolist()) if s != 0]
-            if bad:
-                raise RuntimeError(f"device coder: damaged stream(s) {bad}")
-        self._status = []
+        """One host wait for every group decoded so far: raises if a lane of any stream did not end where it began,
+        naming every such stream of every group.  The groups are forgotten either way: a verdict is given once."""
+        groups, self._status = self._status, []
+        bad = [n for status, names in groups for n, s in zip(names, status.cpu().tolist()) if s != 0]
+        if bad:
+            raise RuntimeError(f"device coder: damaged stream(s) {bad}")
 
     def shutdown(self):
         self._queued = []

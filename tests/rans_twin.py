@@ -98,6 +98,15 @@ def check(stream, n):
     return K
 
 
+def lane_starts(stream):
+    """(at, cnt) of a stream whose header and directory are sound: lane j's 4-byte state lies at at[j], its cnt[j]
+    payload bytes behind it."""
+    s = bytes(stream)
+    w, K = s[1], int.from_bytes(s[2:6], "little")
+    cnt = np.frombuffer(s[6:6 + K * w], np.uint8).reshape(K, w).astype(np.int64) @ (1 << (8 * np.arange(w, dtype=np.int64)))
+    return 6 + K * w + np.cumsum(cnt + 4) - (cnt + 4), cnt
+
+
 def decode(p, n, stream):
     """(status, x): status 0 or -3, x float32 [n] (None when the header or directory is refused)."""
     s = np.frombuffer(bytes(stream), np.uint8)

@@ -11,6 +11,7 @@ import rans_twin as tw
 from guarded import FILL, Guarded
 from test_gpu_context import setup  # noqa: F401  (the toy context model, tables and occupancy grid of that module)
 from test_gpu_trainer import _cfg
+from test_rans_twin import DAMAGE, damaged_table, extreme, twin_verdict
 
 pytestmark = pytest.mark.gpu
 
@@ -190,6 +191,193 @@ def test_malformed_streams_are_refused_on_the_host_before_any_launch(cuda, libs,
     assert not launched
     out = coder.decode_group([(pd, ok)])
     assert launched == [1] and out[0].shape == (n,)
+
+
+def _encode_equals(tab, libs, want):
+    """One encode call of the table: sizes, bytes and the fill behind them against the twin's streams."""
+    sizes = tab.encode(libs)
+    assert sizes.tolist() == [len(w) for w in want]
+    for k, w in enumerate(want):
+        got = tab.bytes[k].get()
+        assert got[:len(w)].tobytes() == w, k
+        assert np.all(got[len(w):] == FILL), k                 # nothing behind the reported size
+    return sizes
+
+
+def _decode_equals(tab, libs, lens):
+    status, xs = tab.decode(libs, lens)
+    assert not status.any()
+    for k, (_, x, _) in enumerate(tab.specs):
+        assert np.array_equal(xs[k], x), k
+
+
+def _put(tab, k, data, shift):
+    """Stream k's byte buffer holds `data` (shorter than its capacity: the rest is the fill)."""
+    assert len(data) <= tab.caps[k]
+    rest = np.full(tab.caps[k] - len(data), FILL, np.uint8)
+    tab.bytes[k] = Guarded(np.concatenate([np.frombuffer(bytes(data), np.uint8), rest]), tab.dev, shift=shift)
+
+
+@pytest.fixture(scope="module")
+def production():
+    """name -> (p, x, S) at the lane shapes of a full-size container, and the twin's stream of each (made once)."""
+    rng = np.random.default_rng(16384)
+
+    def uniform(n):
+        p = rng.uniform(1e-6, 1 - 1e-6, size=n).astype(np.float32)
+        return p, draw(rng, p, n)
+    specs = {"a": uniform(1000003) + (16384,)}                 # K = 62 lanes of 16129 / 16130 symbols, w = 2
+    specs["j"] = (np.zeros(0, np.float32), np.zeros(0, np.float32), 16384)      # empty, between two large streams
+    one = np.array([0.97], np.float32)
+    specs["b"] = (one, draw(rng, one, 200000), 16384)          # p_stride = 0: long lanes, tiny output
+    specs["c"] = extreme(100000) + (16384,)
+    specs["d"] = uniform(3 * 32768) + (32768,)                 # w = 3
+    specs["e"] = uniform(3 * 32767) + (32767,)                 # w = 2, the other side of that boundary
+    specs["f"] = uniform(313 * 128) + (128,)                   # w = 2 and K > 256: the strided directory loops of the pack
+    specs["g"] = uniform(313 * 127) + (127,)                   # w = 1 and K > 256
+    p, x = uniform(16454)                                      # K = 16454 > 256 * 64: the decoder's second round of groups
+    p[-70:], x[-70:] = extreme(70)                             # ... whose lanes emit bytes: improbable symbols among them
+    specs["h"] = (p, x, 1)
+    specs["i"] = uniform(5000) + (16,)                         # K = 313, w = 1
+    want = {k: tw.encode(*v) for k, v in specs.items()}
+    widths = {k: w[1] for k, w in want.items()}
+    assert widths == dict(a=2, j=1, b=2, c=2, d=3, e=2, f=2, g=1, h=1, i=1)
+    lanes = {k: int.from_bytes(w[2:6], "little") for k, w in want.items()}
+    assert lanes == dict(a=62, j=0, b=13, c=7, d=3, e=3, f=313, g=313, h=16454, i=313)
+    return specs, want
+
+
+def test_production_lane_shapes_equal_the_twin(cuda, libs, production):
+    """The default lane length (16384 symbols, a two-byte directory), both directory width boundaries, more lanes than
+    one pack block sums in one pass (256) and than one decode launch holds (256 blocks of 64), in one encode and one
+    decode call; then stream a across the host twin and the device, at another lane count."""
+    _lib, L, Lc = libs
+    specs, want = production
+    names = list(specs)
+    assert names[:3] == ["a", "j", "b"]
+    tab = Table(cuda, [specs[k] for k in names])
+    _encode_equals(tab, libs, [want[k] for k in names])
+    _decode_equals(tab, libs, [len(want[k]) for k in names])
+    # stream a: device-encoded -> the host twin
+    p, x, S = specs["a"]
+    n = len(x)
+    stream = np.ascontiguousarray(tab.bytes[0].get()[:len(want["a"])])
+    assert Lc.cnc_rans_check(stream.ctypes.data, stream.size, n) == tw.lanes(n, S)
+    out = np.zeros(n, np.float32)
+    assert Lc.cnc_rans_decode_pm1_host(p.ctypes.data, 1, n, stream.ctypes.data, stream.size, out.ctypes.data) == 0
+    assert np.array_equal(out, x)
+    # host-encoded at S = 4096 -> the device: K comes from the header, the decoder's blocks from n
+    buf = np.zeros(tw.bound(n, 4096), np.uint8)
+    got = Lc.cnc_rans_encode_pm1_host(p.ctypes.data, 1, x.ctypes.data, n, 4096, buf.ctypes.data, buf.size)
+    assert got > 0 and buf[1] == 2 and int.from_bytes(buf[2:6].tobytes(), "little") == tw.lanes(n, 4096) == 245
+    other = Table(cuda, [(p, x, S)])
+    _put(other, 0, buf[:got], 3)
+    _decode_equals(other, libs, [got])
+
+
+def test_a_damaged_lane_of_the_second_round_of_groups_is_refused(cuda, libs, production):
+    """Stream h has 16454 lanes and the decoder 256 blocks of 64: lanes from 16384 on are reached only by a block's
+    second turn.  One payload bit of such a lane flipped: that stream is refused, its neighbours are not."""
+    specs, want = production
+    names = ["i", "h", "g"]
+    at, cnt = tw.lane_starts(want["h"])
+    j = next(j for j in range(64 * 256, len(cnt)) if cnt[j] > 0)
+    bad = bytearray(want["h"])
+    bad[at[j] + 4] ^= 0x04
+    p, x, _ = specs["h"]
+    assert tw.check(bytes(bad), len(x)) == len(cnt) and tw.decode(p, len(x), bytes(bad))[0] == -3
+    tab = Table(cuda, [specs[k] for k in names])
+    data = [want["i"], bytes(bad), want["g"]]
+    for k, d in enumerate(data):
+        _put(tab, k, d, (1, 3)[k % 2])
+    status, xs = tab.decode(libs, [len(d) for d in data])
+    assert status.tolist() == [0, -3, 0]
+    for k in (0, 2):
+        assert np.array_equal(xs[k], specs[names[k]][1])
+    _put(tab, 1, want["h"], 3)                                 # the sound stream again: the verdict was the bit's
+    _decode_equals(tab, libs, [len(want[k]) for k in names])
+
+
+def test_launches_that_begin_and_end_on_an_empty_stream(cuda, libs):
+    """49 streams are two full launches of the table (24 each) and one more; streams 0, 23, 24 and 48 are empty, so each
+    launch begins or ends on one.  Then the 24-stream prefix: a call that is exactly one launch."""
+    rng = np.random.default_rng(49)
+    specs = []
+    for k in range(49):
+        n = 0 if k in (0, 23, 24, 48) else 40 + 13 * k
+        p = rng.uniform(0.05, 0.95, size=n).astype(np.float32)
+        specs.append((p, draw(rng, p, n), 1 + k % 19))
+    want = [tw.encode(p, x, S) for p, x, S in specs]
+    for count in (49, 24):
+        tab = Table(cuda, specs[:count])
+        _encode_equals(tab, libs, want[:count])
+        _decode_equals(tab, libs, [len(w) for w in want[:count]])
+
+
+def test_damaged_streams_are_refused_by_the_device_and_only_they(cuda, libs):
+    """Every way a stream can be damaged (test_rans_twin.DAMAGE) between sound streams, 27 streams in two launches: the
+    status words are the twin's verdicts, whether the host check would have let the stream through or not, and every
+    sound stream decodes exactly.  All streams are small (n <= 1100, S = 16: at most 69 lanes of a few bytes, w = 1) and
+    lie in guarded buffers, so no address the decoder can form from a damaged directory leaves the allocation."""
+    _lib, L, Lc = libs
+    table = damaged_table()
+    assert len(table) >= 8 and table[0][0] is None and table[-1][0] is None
+    verdict = []
+    for name, p, x, buf, length in table:                      # on the CPU first: what the twin and the host check say
+        passes, status, _ = twin_verdict(p, len(x), buf, length)
+        assert (passes, status) == ((True, 0) if name is None else DAMAGE[name]), name
+        s = np.frombuffer(buf, np.uint8).copy()
+        assert (Lc.cnc_rans_check(s.ctypes.data, length, len(x)) >= 0) == passes, name
+        assert len(x) <= 1100 and buf[1] in (0, 1, 5) and len(buf) < 2 * 1100 + 6 + 5 * 69 + 8
+        verdict.append(status)
+    assert sorted(set(verdict)) == [-3, 0] and verdict.count(-3) == len(DAMAGE) - 1
+    tab = Table(cuda, [(p, x, 16) for _, p, x, _, _ in table], caps=[len(buf) + 7 for _, _, _, buf, _ in table])
+    for k, (_, _, _, buf, _) in enumerate(table):
+        _put(tab, k, buf, (1, 3)[k % 2])
+    status, xs = tab.decode(libs, [length for _, _, _, _, length in table])       # asserts every guard
+    assert status.tolist() == verdict
+    for k, (name, _, x, _, _) in enumerate(table):
+        if verdict[k] == 0:
+            assert np.array_equal(xs[k], x), (k, name)
+
+
+def test_device_coder_at_its_default_lane_length_and_check(cuda, tmp_path):
+    """`DeviceCoder()` as the Trainer uses it: 16384 symbols per lane, files byte-equal to the twin's streams, and a
+    damaged file that passes the host check is named by `check()`, once."""
+    from cnc_amd.context import DEVICE_CODER_SYMBOLS_PER_LANE, DeviceCoder
+    assert DEVICE_CODER_SYMBOLS_PER_LANE == 16384
+    rng = np.random.default_rng(20)
+    n = 1 << 20
+    ps = [rng.uniform(1e-6, 1 - 1e-6, size=n).astype(np.float32), np.array([0.9], np.float32),
+          rng.uniform(0.3, 0.7, size=n).astype(np.float32)]
+    xs = [draw(rng, p, n) for p in ps]
+    want = [tw.encode(p, x, 16384) for p, x in zip(ps, xs)]
+    files = [str(tmp_path / f"stream{k}.b") for k in range(3)]
+    pd = [torch.from_numpy(p).to(cuda) for p in ps]
+    pd[1] = pd[1].expand(n)                                    # an expanded scalar: read with stride 0
+    coder = DeviceCoder()
+    for p, x, f in zip(pd, xs, files):
+        coder.encode(torch.from_numpy(x).to(cuda), p, f)
+    assert coder.finish() == 8 * sum(len(w) for w in want)
+    for f, w in zip(files, want):
+        assert open(f, "rb").read() == w, f
+    items = list(zip(pd, files))
+    for got, x in zip(coder.decode_group(items), xs):
+        assert got.is_cuda and np.array_equal(got.cpu().numpy(), x)
+    coder.check()
+    at, cnt = tw.lane_starts(want[1])
+    j = len(cnt) // 2
+    bad = bytearray(want[1])
+    bad[at[j] + 4 + cnt[j] // 2] ^= 0x20
+    assert cnt[j] > 0 and tw.check(bytes(bad), n) == len(cnt)
+    open(files[1], "wb").write(bytes(bad))
+    outs = coder.decode_group(items)                           # the file passes the host check: no error here
+    with pytest.raises(RuntimeError, match="damaged stream") as err:
+        coder.check()
+    assert files[1] in str(err.value) and files[0] not in str(err.value) and files[2] not in str(err.value)
+    for k in (0, 2):                                           # its neighbours in the same launch are whole
+        assert np.array_equal(outs[k].cpu().numpy(), xs[k])
+    coder.check()                                              # reported once
 
 
 def _format_overhead_bits(directory, n_features):

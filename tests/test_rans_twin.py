@@ -114,6 +114,35 @@ def test_same_bytes_and_round_trip_one_probability(lib, n, S, pg):
         assert ideal <= 8 * nbytes <= 1.002 * ideal + 40 * K + 8 * (6 + K * tw.dir_width(n, K)) + 64
 
 
+# (n, S, directory width): the default lane length, either side of both width boundaries (a lane of m symbols emits at
+# most 2 m bytes: 2 * 128 and 2 * 32768 no longer fit one and two bytes), and one symbol per lane
+LANE_CASES = [(100000, 16384, 2), (3 * 32768, 32768, 3), (3 * 32767, 32767, 2), (313 * 128, 128, 2), (313 * 127, 127, 1),
+              (16454, 1, 1)]
+
+
+@pytest.mark.parametrize("pattern", ["uniform", "worst"])
+@pytest.mark.parametrize("n,S,w", LANE_CASES)
+def test_same_bytes_and_round_trip_at_the_directory_width_boundaries(lib, n, S, w, pattern):
+    """`worst` is two bytes for every symbol: the longest lane's count is the largest value its width has to hold, so a
+    boundary one step too high would truncate the entry and the stream would not decode."""
+    if pattern == "uniform":
+        rng = np.random.default_rng(n + S)
+        p = rng.uniform(1e-6, 1 - 1e-6, size=n).astype(np.float32)
+        x = draw(rng, p, n)
+    else:
+        p, x = np.full(n, 1.0, np.float32), -np.ones(n, np.float32)
+    K = tw.lanes(n, S)
+    assert tw.dir_width(n, K) == w
+    nbytes = _both_ways(lib, p, x, S)
+    got, buf = host_encode(lib, p, x, S)
+    assert got == nbytes and buf[0] == tw.FORMAT_ID and buf[1] == w and int.from_bytes(buf[2:6].tobytes(), "little") == K
+    at, cnt = tw.lane_starts(buf[:got].tobytes())
+    assert len(cnt) == K and at[-1] + 4 + cnt[-1] == got
+    if pattern == "worst":
+        assert nbytes == tw.bound(n, S) == int(lib.cnc_rans_bound(n, S))
+        assert cnt.max() == 2 * -(-n // K) and (w == 1 or cnt.max() >= 1 << (8 * (w - 1)))
+
+
 def test_quantisation_ties(lib):
     """c1 over the sweep: the twin's and the library's streams agree symbol for symbol, so a tie rounded the other way
     (or a fused multiply-subtract) would change bytes; c1 itself against exact rational arithmetic."""
@@ -207,6 +236,122 @@ def test_malformed_streams(lib, name):
         assert rc == st
         assert rc == -3 or not np.array_equal(back, MALFORMED_X)
         assert np.array_equal(back, tback)                # zeros past a sub-stream, on both sides
+
+
+# damage -> (passes cnc_rans_check, status of the decoder): what a decoder that has only (p, n, bytes, len) must say
+DAMAGE = {"payload_bit": (True, -3), "state_high": (True, -3), "state_low": (True, -3), "directory_shift": (True, -3),
+          "trailing_bytes": (True, 0), "one_byte_short": (False, -3), "directory_only": (False, -3), "five_bytes": (False, -3),
+          "more_lanes_than_symbols": (False, -3), "no_lanes": (False, -3), "zero_width": (False, -3), "width_five": (False, -3),
+          "format_id": (False, -3)}
+
+
+def damage(name, good, n):
+    """(buffer, len) from the sound stream `good` of n symbols at w = 1: the decoder is handed buffer[:len]; the buffer is
+    never shorter than the sound stream, so a `len` below it leaves the rest in place behind the end."""
+    b = bytearray(good)
+    K, w = int.from_bytes(good[2:6], "little"), good[1]
+    at, cnt = tw.lane_starts(good)
+    assert w == 1 and K >= 8
+    length = len(good)
+    if name == "payload_bit":
+        j = next(j for j in range(K // 2, K) if cnt[j] > 0)           # a middle lane that has payload
+        b[at[j] + 4 + cnt[j] // 2] ^= 0x10
+    elif name == "state_high":
+        b[at[K // 2]:at[K // 2] + 4] = (0x80000000).to_bytes(4, "little")
+    elif name == "state_low":
+        b[at[K // 3]:at[K // 3] + 4] = (1 << 22).to_bytes(4, "little")
+    elif name == "directory_shift":
+        j = next(j for j in range(K // 2, K - 1) if cnt[j + 1] > 0)
+        b[6 + j] += 1
+        b[6 + j + 1] -= 1
+    elif name == "trailing_bytes":
+        b += bytes([0x00, 0xFF, 0x72, 0x01, 0x80])
+        length += 5
+    elif name == "one_byte_short":
+        length -= 1
+    elif name == "directory_only":
+        length = 6 + K * w
+    elif name == "five_bytes":
+        length = 5
+    elif name == "more_lanes_than_symbols":
+        b[2:6] = (n + 1).to_bytes(4, "little")
+    elif name == "no_lanes":
+        b[2:6] = (0).to_bytes(4, "little")
+    elif name == "zero_width":
+        b[1] = 0
+    elif name == "width_five":
+        b[1] = 5
+    elif name == "format_id":
+        b[0] = 0x52
+    else:
+        raise KeyError(name)
+    return bytes(b), length
+
+
+def damaged_table():
+    """[(name or None, p, x, buffer, len)]: every damage of DAMAGE between sound streams, a sound one first and last;
+    n <= 1100 at S = 16, so K <= 69 lanes of a few bytes each."""
+    rng = np.random.default_rng(1)
+    out = []
+    for name in sorted(DAMAGE):
+        for which in (None, name):
+            n = 1000 + 7 * len(out) % 101
+            p = rng.uniform(0.02, 0.98, size=n).astype(np.float32)
+            x = draw(rng, p, n)
+            good = tw.encode(p, x, 16)
+            buf, length = (good, len(good)) if which is None else damage(which, good, n)
+            out.append((which, p, x, buf, length))
+    n = 1100
+    p = rng.uniform(0.02, 0.98, size=n).astype(np.float32)
+    x = draw(rng, p, n)
+    good = tw.encode(p, x, 16)
+    return out + [(None, p, x, good, len(good))]
+
+
+def twin_verdict(p, n, buf, length):
+    """(passes the check, status, symbols or None) by the NumPy twin."""
+    st, back = tw.decode(p, n, buf[:length])
+    return tw.check(buf[:length], n) >= 0, st, back
+
+
+def test_damaged_streams_get_the_same_verdict_from_the_twin_and_the_library(lib):
+    table = damaged_table()
+    assert len(table) == 2 * len(DAMAGE) + 1 and [t[0] for t in table[::2]] == [None] * (len(DAMAGE) + 1)
+    assert sorted(t[0] for t in table[1::2]) == sorted(DAMAGE)
+    for name, p, x, buf, length in table:
+        n = x.size
+        assert n <= 1100
+        passes, status = (True, 0) if name is None else DAMAGE[name]
+        t_passes, t_status, t_back = twin_verdict(p, n, buf, length)
+        assert (t_passes, t_status) == (passes, status), name
+        s = np.frombuffer(buf, np.uint8).copy()
+        k = lib.cnc_rans_check(s.ctypes.data, length, n)
+        assert k == (tw.lanes(n, 16) if passes else -3), name
+        rc, back = host_decode(lib, p, n, buf[:length])
+        assert rc == status, name
+        if status == 0:
+            assert np.array_equal(back, x) and np.array_equal(t_back, x), name
+        elif passes:
+            assert np.array_equal(back, t_back), name      # the two wrap a damaged state alike
+
+
+def test_every_single_bit_flip_behind_the_directory_is_refused(lib):
+    """A flipped bit in a lane's state or payload leaves the header and directory sound, so only the lanes' end states and
+    byte counts can tell: the library and the twin agree on every one of them (seed fixed: each is refused)."""
+    rng = np.random.default_rng(1)
+    n = 200
+    p = rng.uniform(0.02, 0.98, size=n).astype(np.float32)
+    x = draw(rng, p, n)
+    good = tw.encode(p, x, 16)
+    first = 6 + tw.lanes(n, 16)
+    for at in range(first, len(good)):
+        for bit in range(8):
+            b = bytearray(good)
+            b[at] ^= 1 << bit
+            st, back = tw.decode(p, n, bytes(b))
+            rc, hback = host_decode(lib, p, n, bytes(b))
+            assert st == rc == -3, (at, bit)
+            assert np.array_equal(back, hback), (at, bit)
 
 
 def test_ctypes_struct_has_the_layout_of_the_header(tmp_path):
