@@ -149,9 +149,16 @@ def _transform_stot(transform_type: SamplingType, s_vals: Tensor, t_min, t_max) 
 def _pdf_loss(segments_query: RayIntervals, cdfs_query: Tensor, segments_key: RayIntervals, cdfs_key: Tensor,
               eps: float = 1e-7) -> Tensor:
     """Per interval of the query histogram: max(w - w_outer, 0)^2 / (w + eps), w its weight (CDF increment) and
-    w_outer the key histogram's weight over the key intervals that cover it (the mip-NeRF 360 proposal loss)."""
+    w_outer the key histogram's weight over the key intervals that cover it (the mip-NeRF 360 proposal loss).
+
+    A batched query ((n_rays, n) edges and CDF) takes a batched key; a flattened query (1-D, with `is_left` / `is_right`)
+    takes a flattened or a batched key, and returns one value per query interval, ray after ray."""
+    batched = segments_query.vals.ndim >= 2
+    if batched and segments_key.vals.ndim < 2:        # the ids of a batched query count from the start of its row
+        raise AssertionError(f"a batched query needs a batched key: the key's edges are "
+                             f"{tuple(segments_key.vals.shape)}, the query's {tuple(segments_query.vals.shape)}")
     left, right = searchsorted(segments_key, segments_query)
-    if segments_query.vals.ndim >= 2:
+    if batched:
         w = torch.diff(cdfs_query, dim=-1)
         lo, hi = left[..., :-1], right[..., 1:]
     else:
@@ -159,6 +166,8 @@ def _pdf_loss(segments_query: RayIntervals, cdfs_query: Tensor, segments_key: Ra
             raise AssertionError("a flattened query needs is_left and is_right")
         w = cdfs_query[segments_query.is_right] - cdfs_query[segments_query.is_left]
         lo, hi = left[segments_query.is_left], right[segments_query.is_right]
+        # the ids of a flattened query index the key's values as a whole, whether the key is flattened or batched
+        cdfs_key = cdfs_key.reshape(-1)
     w_outer = cdfs_key.gather(-1, hi) - cdfs_key.gather(-1, lo)
     excess = (w - w_outer).clamp_min(0)
     return excess * excess / (w + eps)
