@@ -346,6 +346,9 @@ def test_vote_tables_node_equals_the_op_chain(setup):
     assert torch.equal(out["node"][1], out["chain"][1]) and float(out["node"][1].abs().max()) > 0
 
 
+SEGMENT_ATOL = {0: 1e-4, 1: 1e-5, 2: 1e-5}          # cnc_segment_weighted_sum per mode, against float64 sums
+
+
 def test_segment_weighted_sum_kernel(cuda):
     from cnc_amd.backends import pack_and_align as pa
     rng = np.random.default_rng(0)
@@ -361,13 +364,13 @@ def test_segment_weighted_sum_kernel(cuda):
         ref.index_add_(0, slot, (v * w[:, None]).double())
         wsum = torch.zeros(500, device=cuda, dtype=torch.float64).index_add_(0, slot, w.double())
         got0 = pa.segment_weighted_sum(v, w, cum, 0)
-        assert torch.allclose(got0.double(), ref, atol=1e-4)
+        assert torch.allclose(got0.double(), ref, atol=SEGMENT_ATOL[0])
         got1 = pa.segment_weighted_sum(v, w, cum, 1)
         nz = torch.as_tensor(cnt, device=cuda) > 0
-        assert torch.allclose(got1[nz].double(), (ref / wsum[:, None])[nz], atol=1e-5)
+        assert torch.allclose(got1[nz].double(), (ref / wsum[:, None])[nz], atol=SEGMENT_ATOL[1])
         got2 = pa.segment_weighted_sum(v, None, cum, 2)
         plain = torch.zeros(500, F, device=cuda, dtype=torch.float64).index_add_(0, slot, v.double())
-        assert torch.allclose(got2[nz].double(), (plain / torch.as_tensor(cnt, device=cuda)[:, None])[nz], atol=1e-5)
+        assert torch.allclose(got2[nz].double(), (plain / torch.as_tensor(cnt, device=cuda)[:, None])[nz], atol=SEGMENT_ATOL[2])
 
 
 @pytest.mark.parametrize("F,sample_num", [(2, 200000), (8, 150000)])

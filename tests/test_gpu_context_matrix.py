@@ -706,6 +706,10 @@ def test_votes_dense_level(cuda, oracle):
     _check_votes(cuda, oracle, setup, 8, seed=11)
 
 
+# cnc_vote_fraction_table{,_backward} against float64, in units of U relative to the value: one division and one sum
+FRACTION_U = {"table": 4, "sums": 2, "grad": 3}
+
+
 def test_vote_fraction_tables(cuda, oracle, votes_full):
     """cnc_vote_fraction_table{,_backward} (the kernels of `_vote_tables3`) against a float64 restatement:
     c0 / ((c0 + c1) + 1e-6) on the inner pixels and a ring of zeros; back, [(1 / sum) g, 0]."""
@@ -726,8 +730,8 @@ def test_vote_fraction_tables(cuda, oracle, votes_full):
     assert float(tab[0].abs().max()) == 0 and float(tab[-1].abs().max()) == 0
     assert float(tab[:, 0].abs().max()) == 0 and float(tab[:, -1].abs().max()) == 0
     inner = tab[1:-1, 1:-1].double()
-    assert float(((inner - ref).abs() - 4 * U * ref.abs()).max()) <= 0.0
-    assert float(((sums.double() - den).abs() - 2 * U * den).max()) <= 0.0
+    assert float(((inner - ref).abs() - FRACTION_U["table"] * U * ref.abs()).max()) <= 0.0
+    assert float(((sums.double() - den).abs() - FRACTION_U["sums"] * U * den).max()) <= 0.0
     assert float(ref.max()) > 0.5 and float(ref.min()) == 0.0
     g = torch.randn(R * R, F, device=cuda)
     gos = torch.full((S, S, F, 2), float("nan"), device=cuda)
@@ -735,7 +739,7 @@ def test_vote_fraction_tables(cuda, oracle, votes_full):
             "vote_fraction_table_backward")
     g_in = g.view(R, R, F)[1:-1, 1:-1].double()
     want = g_in / sums.double()
-    assert float(((gos[..., 0].double() - want).abs() - 3 * U * want.abs()).max()) <= 0.0
+    assert float(((gos[..., 0].double() - want).abs() - FRACTION_U["grad"] * U * want.abs()).max()) <= 0.0
     assert float(gos[..., 1].abs().max()) == 0.0
 
 

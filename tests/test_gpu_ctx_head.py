@@ -85,6 +85,9 @@ def test_bernoulli_bits(cuda, with_rows):
     assert float(again) == float(got)
 
 
+SEGMENT_BWD_TOL = dict(rtol=2e-5, atol=1e-6)      # cnc_segment_weighted_sum{,_gathered}_backward against float64 autograd
+
+
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_segment_reduce_backward_kernel(cuda, mode):
     from cnc_amd.context import _cum, _segment_reduce
@@ -111,7 +114,7 @@ def test_segment_reduce_backward_kernel(cuda, mode):
     vd = v.to(cuda).requires_grad_()
     got = _segment_reduce.apply(vd, _cum(cnt.to(cuda)), None if w is None else w.to(cuda), mode)
     (got[nz.to(cuda)] * go.to(cuda)[nz.to(cuda)]).sum().backward()
-    assert torch.allclose(vd.grad.double().cpu(), v64.grad, rtol=2e-5, atol=1e-6)
+    assert torch.allclose(vd.grad.double().cpu(), v64.grad, **SEGMENT_BWD_TOL)
     # the same through a row permutation (cnc_segment_weighted_sum_gathered): ragged row r = values[order[r]]
     order = torch.randperm(T, generator=g)
     inv = torch.empty_like(order)

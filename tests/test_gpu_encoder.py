@@ -335,6 +335,11 @@ def test_error_behaviour(cuda):
         be.grid_encode_forward(x, e, o, r, out, 8, 3, 3, len(RES3), 0, 128, 0.0, None, None, None)
 
 
+def vote_backward_bound(absacc):
+    """The vote kernels' embedding gradient against the oracle's float64 sums: 64 eps of the sum of the terms' magnitudes."""
+    return 64 * np.finfo(np.float32).eps * np.abs(absacc) + 1e-30
+
+
 @pytest.mark.parametrize("axis", [0, 1, 2])
 @pytest.mark.parametrize("F", [2, 8])
 def test_cnt_np_embed_forward_backward(cuda, oracle, axis, F):
@@ -361,7 +366,7 @@ def test_cnt_np_embed_forward_backward(cuda, oracle, axis, F):
                              torch.as_tensor(s, device=dev), torch.as_tensor(grad, device=dev), ge,
                              pts.shape[0], R, F, hs, axis)
     got_g = ge.cpu().numpy()
-    bound = 64 * np.finfo(np.float32).eps * np.abs(absacc) + 1e-30
+    bound = vote_backward_bound(absacc)
     assert np.all(np.abs(got_g.astype(np.float64) - acc) <= bound)
 
 
@@ -557,7 +562,7 @@ def test_cnt_np_embed_planned_equals_oracle(cuda, oracle, axis, F, R, log2T):
     g_over_sum = (torch.reciprocal(t(s)) * t(grad)).contiguous()
     be.cnt_np_embed_planned_backward(plan, t(emb[:rows].copy()), g_over_sum, ge, F, axis)
     got = ge.cpu().numpy().astype(np.float64)
-    bound = 64 * np.finfo(np.float32).eps * np.abs(absacc[:rows]) + 1e-30
+    bound = vote_backward_bound(absacc[:rows])
     assert np.all(np.abs(got - acc[:rows]) <= bound)
     assert np.all(acc[rows:] == 0)
 

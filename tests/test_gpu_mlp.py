@@ -7,22 +7,40 @@ import torch.nn as nn
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("dims", [(255, 160, 80), (95, 160, 160, 3), (25, 32, 32, 8), (64, 16, 16), (7, 48, 33)])
-@pytest.mark.parametrize("N", [1, 15, 16, 17, 4099, 1 << 16])
-def test_fused_mlp_forward_matches_torch(cuda, dims, N):
-    from cnc_amd.mlp import FusedMLPForward, Linear
-    torch.manual_seed(len(dims) * 1000 + N)
+REL = 2e-5         # of max(1, |want|_max): fp32 round-off of a k-ordered fmaf chain
+
+
+def make_seq(dims, dev):
+    """Linear-ReLU-Linear[-ReLU-Linear] of the given widths on `dev`, with asymmetric, non-trivial weights."""
+    from cnc_amd.mlp import Linear
     layers = []
     for i in range(len(dims) - 1):
         layers.append(Linear(dims[i], dims[i + 1]))
         if i < len(dims) - 2:
             layers.append(nn.ReLU(inplace=True))
-    seq = nn.Sequential(*layers).to(cuda)
+    seq = nn.Sequential(*layers).to(dev)
     for l in seq:
         if isinstance(l, nn.Linear):   # asymmetric, non-trivial weights
             with torch.no_grad():
-                l.weight.copy_(torch.randn_like(l.weight) / dims[0] ** 0.5 + torch.arange(l.weight.shape[1], device=cuda) * 1e-3)
+                l.weight.copy_(torch.randn_like(l.weight) / dims[0] ** 0.5 + torch.arange(l.weight.shape[1], device=dev) * 1e-3)
                 l.bias.copy_(torch.randn_like(l.bias))
+    return seq
+
+
+def chain64(seq, x):
+    """The network in double precision."""
+    ref = x.double()
+    for l in seq:
+        ref = torch.relu(ref) if isinstance(l, nn.ReLU) else ref @ l.weight.double().t() + l.bias.double()
+    return ref
+
+
+@pytest.mark.parametrize("dims", [(255, 160, 80), (95, 160, 160, 3), (25, 32, 32, 8), (64, 16, 16), (7, 48, 33)])
+@pytest.mark.parametrize("N", [1, 15, 16, 17, 4099, 1 << 16])
+def test_fused_mlp_forward_matches_torch(cuda, dims, N):
+    from cnc_amd.mlp import FusedMLPForward
+    torch.manual_seed(len(dims) * 1000 + N)
+    seq = make_seq(dims, cuda)
     fused = FusedMLPForward(seq)
     x = torch.randn(N, dims[0], device=cuda)
     with torch.no_grad():
@@ -30,12 +48,10 @@ def test_fused_mlp_forward_matches_torch(cuda, dims, N):
     got = fused(x)
     assert got.shape == want.shape
     scale = want.abs().max().clamp_min(1.0)
-    assert (got - want).abs().max() <= 2e-5 * scale
+    assert (got - want).abs().max() <= REL * scale
     # a double-precision check pins both to the true value
-    ref = x.double()
-    for l in seq:
-        ref = torch.relu(ref) if isinstance(l, nn.ReLU) else ref @ l.weight.double().t() + l.bias.double()
-    assert (got.double() - ref).abs().max() <= 2e-5 * scale
+    ref = chain64(seq, x)
+    assert (got.double() - ref).abs().max() <= REL * scale
     # strided input view (columns of a wider matrix) and weight update tracking.  (At N = 2^16 and 16 columns `wide` is
     # exactly 4 MiB: in a fresh segment the window's last row ends with the allocation, and a kernel that read the padded K
     # of THAT row faulted whenever nothing was mapped behind it — behind tests/test_gpu_march.py on some boxes; round 6 took

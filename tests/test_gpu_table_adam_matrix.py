@@ -20,7 +20,7 @@ import pytest
 import torch
 
 import adam_twin as T
-from guarded import Guarded
+from guarded import FILL, FILLS, Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -71,16 +71,18 @@ def _zero_or_normal(x):
 class _Table:
     """One table's buffers on the device and the same state on the host."""
 
-    def __init__(self, dev, rng, n, slots, with_step=True, with_sign=False, zero_state=False, p=None, p_scale=(-4, 0)):
-        self.dev, self.n, self.slots = dev, n, list(slots) + [None] * (4 - len(slots))
+    def __init__(self, dev, rng, n, slots, with_step=True, with_sign=False, zero_state=False, p=None, p_scale=(-4, 0),
+                 fill=FILL):
+        """`fill`: the byte around (and, for the sign plane, inside) every buffer of this table (guarded.FILLS)."""
+        self.dev, self.n, self.slots, self.fill_byte = dev, n, list(slots) + [None] * (4 - len(slots)), fill
         self.p = _signed(rng, n, *p_scale) if p is None else np.asarray(p, f32)
         self.m = np.zeros(n, f32) if zero_state else _signed(rng, n, -6, 2)
         self.v = np.zeros(n, f32) if zero_state else np.abs(_signed(rng, n, -10, 5))
-        self.P, self.M, self.V = (Guarded(t, dev) for t in (self.p, self.m, self.v))
-        self.step = Guarded(np.zeros(1, f32), dev) if with_step else None
+        self.P, self.M, self.V = (Guarded(t, dev, fill=fill) for t in (self.p, self.m, self.v))
+        self.step = Guarded(np.zeros(1, f32), dev, fill=fill) if with_step else None
         self.steps = 0.0
-        self.bits = Guarded.empty((n // 8,), np.uint8, dev) if with_sign else None
-        self.clip = Guarded(np.array([5], u32), dev) if with_sign else None       # the kernel adds to it
+        self.bits = Guarded.empty((n // 8,), np.uint8, dev, fill=fill) if with_sign else None
+        self.clip = Guarded(np.array([5], u32), dev, fill=fill) if with_sign else None       # the kernel adds to it
         self.clipped = 5
         self.pieces, self.G = [None] * 4, [None] * 4
 
@@ -94,7 +96,7 @@ class _Table:
                 continue
             q = _grad(rng, r[1] - r[0]) if grads is None else np.asarray(grads[k], f32)
             self.pieces[k] = (q, r[0], r[1])
-            self.G[k] = Guarded(q if q.size else np.zeros(4, f32), self.dev)          # an empty range still needs an address
+            self.G[k] = Guarded(q if q.size else np.zeros(4, f32), self.dev, fill=self.fill_byte)     # an empty range still needs an address
 
     def fill(self, t):
         t.p, t.m, t.v, t.n = self.P.ptr, self.M.ptr, self.V.ptr, self.n
@@ -185,8 +187,9 @@ def test_one_table_every_layout(cuda, n):
     rng = np.random.default_rng(n)
     for name, slots in _layouts(n).items():
         for hname, hyper in HYPERS.items():
-            t = _Table(cuda, rng, n, slots, with_step=(name != "one"))
-            _step_and_check([t], hyper, 6e-3, 3, rng, what=f"{name} / {hname}")
+            for fill in FILLS:                            # the bytes around (and between) the buffers: guarded.FILLS
+                t = _Table(cuda, rng, n, slots, with_step=(name != "one"), fill=fill)
+                _step_and_check([t], hyper, 6e-3, 3, rng, what=f"{name} / {hname} / fill {fill:#x}")
 
 
 @pytest.mark.parametrize("hname", list(HYPERS))
@@ -197,10 +200,11 @@ def test_chained_calls_on_the_kernels_own_state(cuda, n, hname):
     rng = np.random.default_rng(1000 + n)
     lay = _layouts(n)
     slots = lay.get("overlap", lay["two"])
-    t = _Table(cuda, rng, n, slots, zero_state=True, with_sign=(n % 8 == 0))
-    for step in [1, 2, 3, 4, 5, 6, 1000, 20000]:
-        _step_and_check([t], HYPERS[hname], 6e-3 * (0.5 + 0.1 * (step % 7)), step, rng, what=hname)
-    assert t.steps == 8.0
+    for fill in FILLS:
+        t = _Table(cuda, rng, n, slots, zero_state=True, with_sign=(n % 8 == 0), fill=fill)
+        for step in [1, 2, 3, 4, 5, 6, 1000, 20000]:
+            _step_and_check([t], HYPERS[hname], 6e-3 * (0.5 + 0.1 * (step % 7)), step, rng, what=f"{hname} / fill {fill:#x}")
+        assert t.steps == 8.0
 
 
 SEVERAL = [(4096, 4, 8200, 12289), (5, 4096 * 3, 8, 1 << 20), (4100, 4096), (2 * 4096 + 4, 4096, 7), (8192, 8, 4096 * 5, 3)]
@@ -211,16 +215,18 @@ def test_several_tables_in_one_call(cuda, sizes):
     """Two to four tables: the block-to-table search (a one-block table between large ones, a table smaller than a block
     first and last), a different piece count per table, step words and sign planes given for some tables only."""
     rng = np.random.default_rng(sum(sizes))
-    tables = []
-    for k, n in enumerate(sizes):
-        lay = list(_layouts(n).values())
-        slots = [[W, W, W, W], [], lay[-1], [None, W]][k]
-        tables.append(_Table(cuda, rng, n, slots, with_step=(k % 2 == 0), with_sign=(n % 8 == 0 and k != 2), zero_state=True))
-    assert len({sum(s is not None for s in t.slots) for t in tables}) >= 2
-    for hyper in (TRAINER_DECAY, OTHER):
-        for step in (1, 2, 3):
-            _step_and_check(tables, hyper, 4e-3 * step, step, rng, what=str(sizes))
-    assert [t.steps for t in tables] == [6.0 if k % 2 == 0 else 0.0 for k in range(len(sizes))]
+    for fill in FILLS:
+        tables = []
+        for k, n in enumerate(sizes):
+            lay = list(_layouts(n).values())
+            slots = [[W, W, W, W], [], lay[-1], [None, W]][k]
+            tables.append(_Table(cuda, rng, n, slots, with_step=(k % 2 == 0), with_sign=(n % 8 == 0 and k != 2), zero_state=True,
+                                 fill=fill))
+        assert len({sum(s is not None for s in t.slots) for t in tables}) >= 2
+        for hyper in (TRAINER_DECAY, OTHER):
+            for step in (1, 2, 3):
+                _step_and_check(tables, hyper, 4e-3 * step, step, rng, what=f"{sizes} / fill {fill:#x}")
+        assert [t.steps for t in tables] == [6.0 if k % 2 == 0 else 0.0 for k in range(len(sizes))]
 
 
 @pytest.mark.parametrize("n", [8, 4088, 4096, 4104, 40 * 1024 + 8])
