@@ -183,6 +183,9 @@ SIGNATURES = {
     "cnc_pack_bounds": [_vp, _i64, _vp, _vp, _i64, _vp],
     "cnc_distortion_forward": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _u32, _vp],
     "cnc_distortion_backward": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "cnc_lens_undistort": [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _i64, _vp],
+    "cnc_lens_undistort_fisheye": [_vp, _vp, _i64, _f32, _i32, _vp, _i64, _vp],
+    "cnc_camera_rays": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "cnc_level_stats_forward": [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
     "cnc_level_stats_backward": [_vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _vp, _vp],
     "cnc_field_prepare": [_vp, _vp, _u32, _vp, _vp, _vp],
@@ -262,6 +265,10 @@ CNC_VERDICT_RANGE_GUARD = 2
 CNC_VERDICT_MAX_TENSORS = 48
 CNC_OCC_STATUS_COUNT = 1
 CNC_OCC_STATUS_INDEX = 2
+CNC_CAMERA_ROW = 24
+CNC_CAMERA_PINHOLE = 0
+CNC_CAMERA_OPENCV = 1
+CNC_CAMERA_FISHEYE = 2
 ABI_VERSION = 33          # cnc_abi_version() of the library this table was written for
 
 

@@ -336,14 +336,6 @@ def exclusive_prod_backward(chunk_starts, chunk_cnts, inputs, outputs, grad_outp
                      grad_outputs)
 
 
-def _not_built(name):
-    def f(*a, **k):
-        raise NotImplementedError(
-            f"{name}: outside the CNC hot path (never called by examples/train_CNC_*.py); "
-            "not built in cnc_amd")
-    return f
-
-
 def _rows(spec, name):
     """cnc_pdf_rows_t of a RaySegmentsSpec after the checks of data_spec.hpp:15-53: batched when vals has more than
     one axis (rows along the last), else flattened by chunk_starts / chunk_cnts."""
@@ -440,6 +432,52 @@ def searchsorted(query, key):
     return [ids_left, ids_right]
 
 
-# bound by the reference module but unused by CNC
-opencv_lens_undistortion = _not_built("opencv_lens_undistortion")
-opencv_lens_undistortion_fisheye = _not_built("opencv_lens_undistortion_fisheye")
+def _shared_row(params):
+    """True when `params` is one coefficient row seen through a broadcast: every axis in front of the last has stride 0
+    (or one entry), as `torch.broadcast_to(row, batch + (N,))` leaves it.  Such a tensor is handed to the kernel as ONE row
+    (param_stride 0) instead of being made contiguous."""
+    return params.stride(-1) == 1 and all(st == 0 or sz == 1 for sz, st in zip(params.shape[:-1], params.stride()[:-1]))
+
+
+def _undistort(name, uv, params, layouts):
+    """Host checks of camera.cu:114-183: CHECK_INPUT on both, equal dimensionality, uv [..., 2], the row length.
+    -> (number of points, param_stride)."""
+    check_input(uv, "uv")
+    _lib.check_cuda(params, "params")
+    shared = params.numel() > 0 and _shared_row(params)
+    if not shared:
+        check_input(params, "params")
+    if uv.dim() != params.dim():
+        raise RuntimeError(f"{name}: uv and params must have the same number of dimensions")
+    if uv.dim() < 1 or uv.shape[-1] != 2:
+        raise RuntimeError("uv must have shape [..., 2]")
+    if params.shape[-1] not in layouts:
+        raise RuntimeError(f"{name}: params must have shape [..., {' | '.join(str(n) for n in layouts)}]")
+    if uv.dtype != torch.float32 or params.dtype != torch.float32:
+        raise RuntimeError(f"{name}: uv and params must be float32")
+    n = uv.numel() // 2
+    if not shared and params.numel() != n * params.shape[-1]:
+        raise RuntimeError(f"{name}: params must hold one row per point")
+    return n, (0 if shared else params.shape[-1])
+
+
+def opencv_lens_undistortion(uv, params, eps, iters):
+    """camera.cu:114-147 -> uv_out shaped like uv.  params [..., 5 | 8 | 12]: k1 k2 p1 p2 k3 [k4 k5 k6], or k1..k6 p1 p2
+    s1..s4.  A broadcast view of one row (see `_shared_row`) is read as one row; anything else must be contiguous."""
+    n, stride = _undistort("opencv_lens_undistortion", uv, params, (5, 8, 12))
+    out = torch.empty_like(uv)
+    rc = _lib.lib().cnc_lens_undistort(ptr(uv), ptr(params), stride, params.shape[-1], float(eps), int(iters), ptr(out), n,
+                                       stream(uv.device))
+    check(rc, "opencv_lens_undistortion")
+    return out
+
+
+def opencv_lens_undistortion_fisheye(uv, params, eps, iters):
+    """camera.cu:149-183 -> uv_out shaped like uv.  params [..., 4] = k1..k4.  A point that does not converge returns its
+    input (the reference leaves that element of its output uninitialised)."""
+    n, stride = _undistort("opencv_lens_undistortion_fisheye", uv, params, (4,))
+    out = torch.empty_like(uv)
+    rc = _lib.lib().cnc_lens_undistort_fisheye(ptr(uv), ptr(params), stride, float(eps), int(iters), ptr(out), n,
+                                               stream(uv.device))
+    check(rc, "opencv_lens_undistortion_fisheye")
+    return out

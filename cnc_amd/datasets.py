@@ -1,6 +1,7 @@
 """Scene loaders for the CNC drivers: `SubjectLoader` (NeRF-synthetic: `transforms_{split}.json`
 + RGBA PNGs) and `SubjectLoader_Tanks` (Tanks&Temples in the NSVF layout: `intrinsics.txt`, `bbox.txt`,
-`pose/*.txt`, `rgb/*.png`, split by file-name prefix).
+`pose/*.txt`, `rgb/*.png`, split by file-name prefix); and, an extension, `TransformsLoader` (a capture in the
+instant-ngp / nerfstudio `transforms.json` layout, with OpenCV lens distortion: rays from one HIP launch).
 
 Interface of the reference's loaders (examples/datasets/nerf_synthetic.py:53-239, tanks.py:62-259): same
 constructor arguments, `len()`, `loader[i]` -> {"pixels", "rays", "color_bkgd"}, `update_num_rays`, the
@@ -170,6 +171,138 @@ class SubjectLoader_Tanks(_PosedImages):
         self.images = torch.from_numpy(images).to(device)
         self.camtoworlds = torch.from_numpy(poses).to(device)
         self.K = torch.from_numpy(intrinsics).to(device)
+
+
+_LENS_KEYS = ("k1", "k2", "k3", "k4", "p1", "p2")
+_IMAGE_SUFFIXES = ("", ".png", ".jpg", ".jpeg", ".PNG", ".JPG", ".JPEG")
+
+
+class TransformsLoader(_PosedImages):
+    """A capture of one's own in the instant-ngp / nerfstudio layout: `<root>/<scene>/transforms_{train,test}.json` when
+    present, else `transforms.json` with every 8th frame held out for `test`.
+
+    Keys: `fl_x fl_y cx cy w h k1 k2 k3 k4 p1 p2` at the top level, each overridable per frame; `camera_model` in
+    {PINHOLE, OPENCV, OPENCV_FISHEYE} (absent: OPENCV if any coefficient is non-zero, else PINHOLE); `camera_angle_x` when
+    there is no `fl_x`; `frames[].file_path` (looked up with and without an extension) and `frames[].transform_matrix`
+    (camera-to-world, OpenGL convention); an optional top-level `aabb` (six numbers) exposed as `.aabb` / `.scene_bbox`.
+    OPENCV reads k1 k2 p1 p2 k3 (rational-radial + tangential), OPENCV_FISHEYE k1..k4.  All images must have one size; an
+    image without alpha is opaque.
+
+    The cameras go into one table on the device (backends/camera_backend.py); a training batch is the base class's three
+    `randint` draws, the background, and ONE launch of cnc_camera_rays with the pixel fetch; a view is one launch in its
+    full-frame form.  On a host device the torch restatement runs instead."""
+
+    SPLITS = ["train", "test"]
+    NEAR, FAR = 0.0, 1e10
+    OPENGL_CAMERA = True
+    TRAIN_SPLITS = ("train",)
+    HOLD_OUT = 8
+
+    def __init__(self, subject_id: str, root_fp: str, split: str, color_bkgd_aug: str = "white",
+                 num_rays: int = None, near: float = None, far: float = None,
+                 batch_over_images: bool = True, device: torch.device = torch.device("cpu"),
+                 eps: float = 1e-6, iters: int = 10):
+        super().__init__()
+        if split not in self.SPLITS:
+            raise AssertionError(split)
+        self._configure(split, color_bkgd_aug, num_rays, near, far, batch_over_images)
+        from .backends import camera_backend
+        self.eps, self.iters = float(eps), int(iters)
+        scene_dir = os.path.join(root_fp, subject_id)
+        per_split = os.path.join(scene_dir, f"transforms_{split}.json")
+        path = per_split if os.path.exists(per_split) else os.path.join(scene_dir, "transforms.json")
+        with open(path) as fp:
+            meta = json.load(fp)
+        frames = list(meta["frames"])
+        if path != per_split:
+            frames = [fr for i, fr in enumerate(frames) if (i % self.HOLD_OUT == 0) == (split == "test")]
+        if not frames:
+            raise ValueError(f"{path}: no frames for split '{split}'")
+        images, rows, lens, models = [], [], [], set()
+        for fr in frames:
+            file = self._find_image(scene_dir, fr["file_path"])
+            img = _rgba(file)
+            if images and img.shape != images[0].shape:
+                raise ValueError(f"{file}: image is {img.shape[1]} x {img.shape[0]}, the images before it are "
+                                 f"{images[0].shape[1]} x {images[0].shape[0]} (one size per capture)")
+            images.append(img)
+            get = lambda k, default=None: fr.get(k, meta.get(k, default))
+            h, w = img.shape[:2]
+            fw = float(get("w", w))
+            if get("fl_x") is not None:
+                fx = float(get("fl_x"))
+            elif get("camera_angle_x") is not None:
+                fx = 0.5 * fw / math.tan(0.5 * float(get("camera_angle_x")))
+            else:
+                raise ValueError(f"{path}: neither fl_x nor camera_angle_x")
+            fy = float(get("fl_y", fx))
+            rows.append([fx, fy, float(get("cx", fw / 2.0)), float(get("cy", float(get("h", h)) / 2.0))])
+            k = {name: float(get(name, 0.0)) for name in _LENS_KEYS}
+            model = get("camera_model")
+            if model is None:
+                model = "OPENCV" if any(v != 0.0 for v in k.values()) else "PINHOLE"
+            if model not in camera_backend.MODELS:
+                raise ValueError(f"{path}: camera_model {model!r} is not one of {sorted(camera_backend.MODELS)}")
+            if model == "OPENCV" and k["k4"] != 0.0:
+                raise ValueError(f"{path}: the OPENCV model has no k4 (OPENCV_FISHEYE does)")
+            if model == "OPENCV_FISHEYE" and (k["p1"] != 0.0 or k["p2"] != 0.0):
+                raise ValueError(f"{path}: the OPENCV_FISHEYE model has no tangential coefficients")
+            models.add(model)
+            lens.append([k["k1"], k["k2"], k["k3"], k["k4"]] if model == "OPENCV_FISHEYE"
+                        else [k["k1"], k["k2"], k["p1"], k["p2"], k["k3"]] if model == "OPENCV" else [])
+        if len(models) != 1:
+            raise ValueError(f"{path}: one camera_model per capture, not {sorted(models)}")
+        self.camera_model = models.pop()
+        self.model = camera_backend.MODELS[self.camera_model]
+        self.HEIGHT, self.WIDTH = images[0].shape[:2]
+        self.images = torch.from_numpy(np.stack(images)).to(device)
+        poses = np.asarray([fr["transform_matrix"] for fr in frames], dtype=np.float32)
+        self.camtoworlds = torch.from_numpy(poses).to(device)
+        self.intrinsics = torch.tensor(rows, dtype=torch.float32, device=device)
+        self.lens = torch.tensor(lens, dtype=torch.float32, device=device).reshape(len(frames), len(lens[0]))
+        self.cameras = camera_backend.camera_table(self.intrinsics, self.camtoworlds, self.lens)
+        fx, fy, cx, cy = rows[0]
+        self.focal = fx
+        self.K = torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], dtype=torch.float32, device=device)
+        if meta.get("aabb") is not None:
+            box = np.asarray(meta["aabb"], dtype=np.float32).reshape(-1)
+            if box.shape[0] != 6:
+                raise ValueError(f"{path}: aabb must hold six numbers")
+            self.aabb = torch.tensor(box, dtype=torch.float32, device=device)
+            self.scene_bbox = self.aabb.view(2, 3)
+        else:
+            self.aabb = None
+
+    @staticmethod
+    def _find_image(scene_dir, file_path):
+        for suffix in _IMAGE_SUFFIXES:
+            file = os.path.join(scene_dir, file_path + suffix)
+            if os.path.isfile(file):
+                return file
+        raise FileNotFoundError(f"{os.path.join(scene_dir, file_path)}: no such image (with or without an extension)")
+
+    @torch.no_grad()
+    def __getitem__(self, index):
+        from .backends import camera_backend
+        dev = self.images.device
+        if self.training or not dev.type == "cuda":
+            ids, x, y, shape = self._pixels_to_sample(index, dev)
+        else:
+            ids, shape = None, (self.HEIGHT, self.WIDTH)
+        bkgd = self._background(dev)
+        if dev.type != "cuda":
+            o, d, pix = camera_backend.camera_rays_torch(self.cameras, self.model, self.OPENGL_CAMERA, ids.expand(x.shape[0]),
+                                                         x, y, self.images, bkgd, self.eps, self.iters)
+        elif ids is not None:
+            o, d, pix = camera_backend.camera_rays(self.cameras, self.model, self.OPENGL_CAMERA, ids, x, y, images=self.images,
+                                                   bkgd=bkgd, eps=self.eps, iters=self.iters)
+        else:
+            o, d, pix = camera_backend.camera_rays(self.cameras, self.model, self.OPENGL_CAMERA, cam0=int(index),
+                                                   width=self.WIDTH, height=self.HEIGHT, images=self.images, bkgd=bkgd,
+                                                   eps=self.eps, iters=self.iters)
+        return {"pixels": pix.reshape(*shape, 3),
+                "rays": Rays(origins=o.reshape(*shape, 3), viewdirs=d.reshape(*shape, 3)),
+                "color_bkgd": bkgd}
 
 
 class SyntheticBallDataset:

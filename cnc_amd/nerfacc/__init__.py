@@ -1,6 +1,7 @@
 """cnc_amd.nerfacc — the subset of nerfacc 0.5.3 that CNC uses (reference: nerfacc/__init__.py),
 with the CUDA extension replaced by HIP kernels for gfx950, and the proposal-network route (`PropNetEstimator`,
-`importance_sampling`, `searchsorted`) beside it.  The camera undistortion kernels are not provided."""
+`importance_sampling`, `searchsorted`) and the camera undistortion kernels (`nerfacc.cameras`, not in `__all__`, as in
+the reference) beside it."""
 from .data_specs import RayIntervals, RaySamples
 from .estimators.occ_grid import OccGridEstimator
 from .estimators.prop_net import PropNetEstimator

@@ -9,7 +9,8 @@ default of `TrainConfig`.  What runs: train -> evaluate -> encode (.b files) -> 
 
 No dataset ships with this repository (no network): `--dataset procedural` (default when --data_root does not
 exist) trains on the built-in analytic scene so the whole protocol can be exercised anywhere.
-Extensions: --max_steps, --test_views (subset of the test images), --results, --dataset.
+Extensions: --max_steps, --test_views (subset of the test images), --results, --dataset, and `--dataset transforms`
+(+ --aabb): a capture of one's own in the instant-ngp / nerfstudio transforms.json layout, lens distortion included.
 """
 from __future__ import annotations
 
@@ -25,15 +26,30 @@ import torch
 from .render import NERF_SYNTHETIC_SCENES, TANKS_SCENES, render_image_with_occgrid_test
 from .trainer import LoaderDataset, TrainConfig, Trainer, quantize_params
 
+NAMED_SCENES = NERF_SYNTHETIC_SCENES + TANKS_SCENES + ["ball"]
+
+
+class _Parser(argparse.ArgumentParser):
+    """--scene was a closed list of choices; it stays one unless the run is on a capture (`dataset_kind`)."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        try:
+            dataset_kind(ns)
+        except SystemExit as e:
+            self.error(str(e))
+        return ns
+
 
 def build_parser():
-    ap = argparse.ArgumentParser(prog="python -m cnc_amd.train")
+    ap = _Parser(prog="python -m cnc_amd.train")
     ap.add_argument("--data_root", type=str, default=str(pathlib.Path.cwd() / "data/nerf_synthetic"),
                     help="the root dir of the dataset")
     ap.add_argument("--train_split", type=str, default="train", choices=["train", "trainval"],
                     help="which train split to use")
-    ap.add_argument("--scene", type=str, default="chair", choices=NERF_SYNTHETIC_SCENES + TANKS_SCENES + ["ball"],
-                    help="which scene to use")
+    ap.add_argument("--scene", type=str, default="chair",
+                    help="which scene to use: one of " + ", ".join(NAMED_SCENES) + "; with --dataset transforms (or a "
+                         "<data_root>/<scene>/transforms*.json and no --dataset) any directory name under --data_root")
     ap.add_argument("--lmbda", type=float, default=2e-3)
     ap.add_argument("--Pg_level", type=int, default=12)
     ap.add_argument("--Pg_level_2D", type=int, default=4)
@@ -43,7 +59,11 @@ def build_parser():
     ap.add_argument("--max_context_layer_num", type=int, default=3)
     ap.add_argument("--n_features", type=int, default=4)
     # extensions
-    ap.add_argument("--dataset", choices=["nerf_synthetic", "tanks", "procedural"], default=None)
+    ap.add_argument("--dataset", choices=["nerf_synthetic", "tanks", "procedural", "transforms"], default=None,
+                    help="transforms: a capture in the instant-ngp / nerfstudio transforms.json layout, lens distortion "
+                         "included (DESIGN.md §4.11); bounded scenes only, so give the box in the file or with --aabb")
+    ap.add_argument("--aabb", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="--dataset transforms: the scene box; overrides the file's `aabb`, which overrides the default")
     ap.add_argument("--max_steps", type=int, default=20000)
     ap.add_argument("--test_views", type=int, default=None, help="evaluate this many test images (default: all)")
     ap.add_argument("--image_size", type=int, default=200, help="procedural scene only")
@@ -68,11 +88,30 @@ def build_parser():
     return ap
 
 
-def make_config_and_data(args, device, rank=0, world=1):
-    kind = args.dataset
+def _has_transforms(data_root, scene):
+    scene_dir = os.path.join(data_root, scene)
+    return os.path.isdir(scene_dir) and any(f.startswith("transforms") and f.endswith(".json") for f in os.listdir(scene_dir))
+
+
+def dataset_kind(args):
+    """--dataset, or what --data_root / --scene imply.  A scene outside the named ones is a capture: it needs
+    `--dataset transforms`, or a transforms*.json under <data_root>/<scene>."""
+    kind = getattr(args, "dataset", None)
+    named = args.scene in NAMED_SCENES
     if kind is None:
-        root_has_scene = os.path.isdir(os.path.join(args.data_root, args.scene))
-        kind = ("tanks" if args.scene in TANKS_SCENES else "nerf_synthetic") if root_has_scene else "procedural"
+        if not named and _has_transforms(args.data_root, args.scene):
+            kind = "transforms"
+        elif named:
+            root_has_scene = os.path.isdir(os.path.join(args.data_root, args.scene))
+            kind = ("tanks" if args.scene in TANKS_SCENES else "nerf_synthetic") if root_has_scene else "procedural"
+    if not named and kind != "transforms":
+        raise SystemExit(f"--scene {args.scene!r}: not one of {', '.join(NAMED_SCENES)}; a scene of another name needs "
+                         "--dataset transforms or a transforms*.json under <data_root>/<scene>")
+    return kind
+
+
+def make_config_and_data(args, device, rank=0, world=1):
+    kind = dataset_kind(args)
     scene = args.scene if kind != "procedural" else "ball"
     kw = dict(scene=scene, lmbda=args.lmbda, Pg_level=args.Pg_level, Pg_level_2D=args.Pg_level_2D,
               log2_hashmap_size=args.log2_hashmap_size, log2_hashmap_size_2D=args.log2_hashmap_size_2D,
@@ -102,6 +141,16 @@ def make_config_and_data(args, device, rank=0, world=1):
         # near_plane stays 0.0: the reference driver never hands the loader's NEAR to the sampler
         # (train_CNC_tank_temples.py:176)
         kw.update(aabb=tuple(float(v) for v in train.aabb.tolist()), render_step_size=train.render_step_size)
+        dataset = LoaderDataset(train, test)
+    elif kind == "transforms":
+        from .datasets import TransformsLoader
+        train = TransformsLoader(subject_id=scene, root_fp=args.data_root, split="train", num_rays=1024, device=device)
+        test = TransformsLoader(subject_id=scene, root_fp=args.data_root, split="test", num_rays=None, device=device)
+        box = getattr(args, "aabb", None)
+        if box is None and train.aabb is not None:
+            box = train.aabb.tolist()
+        if box is not None:                       # --aabb, else the file's, else TrainConfig's default
+            kw.update(aabb=tuple(float(v) for v in box))
         dataset = LoaderDataset(train, test)
     if dataset is not None and world > 1:
         # data parallelism: every rank draws its OWN images / pixels (the all-reduce then averages world different
@@ -199,7 +248,8 @@ def main(argv=None):
         import shutil
         shutil.rmtree(os.path.join(cfg.out_dir, f".rank{rank}"), ignore_errors=True)
         return cols
-    folder = {"nerf_synthetic": "Synthetic-NeRF", "tanks": "TanksAndTemple", "procedural": "procedural"}[kind]
+    folder = {"nerf_synthetic": "Synthetic-NeRF", "tanks": "TanksAndTemple", "procedural": "procedural",
+              "transforms": "transforms"}[kind]
     out = args.results or os.path.join("./results", folder, "output.txt")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "a") as fw:

@@ -699,6 +699,60 @@ int cnc_distortion_backward(const int64_t* chunk_starts, const int64_t* chunk_cn
                             const float* grad_loss /* [n_rays] */, float* grad_weights, uint32_t n_rays, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI v33, added entries: no signature changed) Cameras (csrc/camera.hip)  —  replace
+ * opencv_lens_undistortion / opencv_lens_undistortion_fisheye of nerfacc/cuda/csrc/camera.cu:114-183; the pixel -> ray
+ * kernel is an extension (the reference's loaders build rays with a chain of torch ops).  Written from OpenCV's published
+ * camera models.  Float32 throughout, nothing fused (contraction is off for the file as for the library), division and
+ * sqrt correctly rounded; the fisheye's Newton update and its tan are evaluated in double and rounded to float once each.
+ * tests/camera_twin.py restates the arithmetic in NumPy, operation for operation.
+ *
+ * A caller may rely on this: every element of the outputs is written exactly once, by a plain store, and nothing else is
+ * written; no atomics, so equal inputs give equal bits; the inputs are only read.  n == 0 succeeds and touches nothing.
+ * uv, uv_out: 8-byte aligned; cams: 16-byte aligned; images: 4-byte aligned; n <= 2^31 - 1.  CNC_ERR_INVALID_VALUE for a
+ * null pointer, a misaligned one, n_cams <= 0, an unknown layout or model, a param_stride between 1 and the row length - 1.
+ *
+ * cnc_lens_undistort: uv [n, 2] distorted normalised image coordinates -> uv_out [n, 2] ideal ones.  params: one row of
+ * `layout` coefficients for all points (param_stride 0: read once per wave into scalar registers — no [n, layout]
+ * broadcast is ever read) or one row per point, param_stride (>= layout) floats apart.
+ *   layout 5  k1 k2 p1 p2 k3           Newton's method on the 2x2 residual of the rational-radial + tangential model from
+ *   layout 8  k1 k2 p1 p2 k3 k4 k5 k6  (x, y) = (u, v): stops when |det J| < eps (the point keeps its current value: a point
+ *                                      whose Jacobian is singular at the start returns the start), when both step
+ *                                      components are below eps after the update, or after `iters` rounds
+ *   layout 12 k1..k6 p1 p2 s1..s4      OpenCV's fixed-point iteration with the thin-prism terms, `iters` rounds (eps is not
+ *                                      read); the input is returned unchanged when the inverse radial factor turns negative
+ * cnc_lens_undistort_fisheye: params k1..k4.  theta_d = min(|uv|, pi/2); Newton on theta from theta = theta_d, stopping
+ * when the update is below eps; uv_out = uv * tan(theta) / theta_d, and uv * 0 when theta_d <= eps.  A point that has not
+ * converged after `iters` rounds, or whose theta changed sign, returns its INPUT — a stated departure: the reference
+ * leaves such an output element uninitialised (camera.cu:170, utils_camera.cuh:190-196).                              */
+int cnc_lens_undistort(const float* uv, const float* params, int64_t param_stride, int32_t layout, float eps, int32_t iters,
+                       float* uv_out, int64_t n, void* stream);
+int cnc_lens_undistort_fisheye(const float* uv, const float* params, int64_t param_stride, float eps, int32_t iters,
+                               float* uv_out, int64_t n, void* stream);
+
+/* cnc_camera_rays: pixels -> world rays in one launch.  cams f32 [n_cams, CNC_CAMERA_ROW]: fx fy cx cy | the three rows
+ * of the 3x4 camera-to-world matrix [R | t] | eight lens coefficients (CNC_CAMERA_OPENCV: layout 8 above;
+ * CNC_CAMERA_FISHEYE: k1..k4, the rest unread; CNC_CAMERA_PINHOLE: unread).  `model` holds for the whole call.
+ * Work list: cam_ids, px, py i64 [n] (the integer type torch.randint draws: no conversion launch in front) — or
+ * cam_ids == NULL: the width x height pixels of camera cam0 in row-major order, n == width * height, no index tensors
+ * (the camera row then lives in scalar registers).  Per pixel, in this order:
+ *     u = ((px - cx) + 0.5) / fx        v = ((py - cy) + 0.5) / fy                  (the loaders' torch chain)
+ *     (u, v) <- undistorted by `model` with (eps, iters): the device functions of the two entries above
+ *     c = (u, v * flip, flip), flip = -1 with `opengl` (y up, looking down -z) else +1
+ *     w_j = (R_j0 c_0 + R_j1 c_1) + R_j2 c_2 ;  viewdirs = w / sqrt((w_0^2 + w_1^2) + w_2^2) ;  origins = t
+ * images != NULL (u8 [n_cams, height, width, 4] RGBA, with bkgd = 3 floats on the DEVICE): pixels [n, 3] =
+ * (rgb / 255) * (a / 255) + bkgd * (1 - a / 255).  A cam_id outside [0, n_cams) is clamped into it, and px / py are
+ * clamped into the image for the FETCH only (the ray is computed from the px, py given): no load leaves the table or the
+ * images whatever the list holds.  origins, viewdirs, pixels: [n, 3], written as 12-byte rows.                         */
+#define CNC_CAMERA_ROW     24
+#define CNC_CAMERA_PINHOLE 0
+#define CNC_CAMERA_OPENCV  1
+#define CNC_CAMERA_FISHEYE 2
+int cnc_camera_rays(const float* cams, int32_t n_cams, int32_t model, int32_t opengl, const int64_t* cam_ids,
+                    const int64_t* px, const int64_t* py, int32_t cam0, int32_t width, int32_t height, int64_t n,
+                    float eps, int32_t iters, const uint8_t* images, const float* bkgd, float* origins, float* viewdirs,
+                    float* pixels, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Context-model heads and the Bernoulli rate  —  replace the ATen chains of examples/utils_bpp_acc.py
  * (context MLPs :378-393 applied at :561-566 / :689-692, hash fusion :567-572 / :693-701,
  * Bernoulli_entropy :1002-1013); SURVEY.md §7 item 6 / north_star: "the small context MLP ... as fused HIP
