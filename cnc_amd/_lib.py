@@ -234,6 +234,12 @@ SIGNATURES = {
     "cnc_occ_emit": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "cnc_occ_probs": [_vp, _i64, _vp, _vp, _vp],
     "cnc_occ_scatter": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "cnc_mlp_tree_hist": [_vp, _i64, _vp, _i32, _i32, _vp, _vp],
+    "cnc_mlp_tree_emit": [_vp, _i64, _vp, _i32, _i32, _vp, _i64, C.POINTER(_i64), _vp, _vp, _i64, _vp],
+    "cnc_mlp_tree_probs": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp],
+    "cnc_mlp_tree_fold": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp],
+    "cnc_mlp_tree_pack_low": [_vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp],
+    "cnc_mlp_tree_unpack": [_vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp],
 }
 
 # entry points that return something other than a status code
@@ -265,6 +271,7 @@ CNC_VERDICT_RANGE_GUARD = 2
 CNC_VERDICT_MAX_TENSORS = 48
 CNC_OCC_STATUS_COUNT = 1
 CNC_OCC_STATUS_INDEX = 2
+CNC_MLP_TREE_DESC = 16
 CNC_CAMERA_ROW = 24
 CNC_CAMERA_PINHOLE = 0
 CNC_CAMERA_OPENCV = 1

@@ -11,7 +11,9 @@ real file size:
 sections: every arithmetic-coded table stream, the occupancy grid (arithmetic-coded with its own
 frequency, or — `occupancy_coder="pyramid"`, the section then says `model: "pyramid1"` — context-coded
 from a pyramid of itself, occupancy_codec.py), the radiance-field MLP tensors uniformly quantised to
-`mlp_bits` (13) bits and bit-packed, the context-model weights in fp32.
+`mlp_bits` (13) bits and bit-packed (`mlp/<name>` sections) or — `mlp_coder="tree"`, one `mlp` section that says
+`model: "tree1"` — the same indices entropy-coded with a per-tensor bit-tree model (mlp_codec.py) whenever that is smaller,
+the context-model weights in fp32.
 """
 from __future__ import annotations
 
@@ -59,11 +61,19 @@ def quantize_tensor(p: torch.Tensor, bits: int):
 
 def write_container(path: str, *, meta: Dict, table_streams: Dict[str, bytes], binaries: torch.Tensor,
                     field_mlp: Dict[str, torch.Tensor], context_state: Dict[str, torch.Tensor],
-                    mlp_bits: int = 13, occupancy_coder: str = "iid", coder: str = "host", symbols_per_lane=None) -> int:
+                    mlp_bits: int = 13, occupancy_coder: str = "iid", coder: str = "host", symbols_per_lane=None,
+                    mlp_coder: str = "packed") -> int:
     """Returns the file size in bytes.  occupancy_coder: "iid" (one Bernoulli frequency, the host range coder) or
-    "pyramid" (occupancy_codec.encode_occupancy with `coder`, "host" or "device": the coder of the table streams)."""
+    "pyramid" (occupancy_codec.encode_occupancy with `coder`, "host" or "device": the coder of the table streams).
+    mlp_coder: "packed" (the `mlp/<name>` sections) or "tree" (mlp_codec.encode_mlp with `coder`; the packed sections
+    still, byte for byte, when the tree1 section would not be smaller than their sum)."""
     if occupancy_coder not in ("iid", "pyramid"):
         raise ValueError(f"occupancy_coder must be 'iid' or 'pyramid', got {occupancy_coder!r}")
+    if mlp_coder not in ("packed", "tree"):
+        raise ValueError(f"mlp_coder must be 'packed' or 'tree', got {mlp_coder!r}")
+    if mlp_coder == "tree":
+        from .mlp_codec import check_bits
+        check_bits(mlp_bits)
     sections, payload = {}, io.BytesIO()
 
     def add(name, blob, **extra):
@@ -91,9 +101,19 @@ def write_container(path: str, *, meta: Dict, table_streams: Dict[str, bytes], b
             f = os.path.join(td, "occ.b")
             encoder(occ * 2 - 1, torch.full_like(occ, pg), f)
             add("occupancy", open(f, "rb").read(), shape=list(binaries.shape), pg=pg)
-    for name, p in field_mlp.items():
-        q, lo, interval = quantize_tensor(p.detach().float(), mlp_bits)
-        add("mlp/" + name, _pack_bits(q, mlp_bits), shape=list(p.shape), lo=lo, interval=interval, bits=mlp_bits)
+    tree = None
+    if mlp_coder == "tree" and field_mlp:
+        from .mlp_codec import encode_mlp
+        blob, info = encode_mlp(field_mlp, bits=mlp_bits, coder=coder, symbols_per_lane=symbols_per_lane)
+        packed = sum((int(p.numel()) * mlp_bits + 7) // 8 for p in field_mlp.values())
+        if len(blob) < packed:           # never larger: a section that saves nothing leaves the packed ones in place
+            tree = (blob, info)
+    if tree is not None:
+        add("mlp", tree[0], **tree[1])
+    else:
+        for name, p in field_mlp.items():
+            q, lo, interval = quantize_tensor(p.detach().float(), mlp_bits)
+            add("mlp/" + name, _pack_bits(q, mlp_bits), shape=list(p.shape), lo=lo, interval=interval, bits=mlp_bits)
     for name, p in context_state.items():
         add("ctx/" + name, p.detach().float().cpu().numpy().tobytes(), shape=list(p.shape))
     header = json.dumps(dict(meta=meta, sections=sections)).encode()
@@ -142,6 +162,9 @@ def read_container(path: str, device="cpu"):
                 open(f, "wb").write(data)
                 x = decoder(torch.full((n,), s["pg"], dtype=torch.float32), f)
             binaries = (x > 0).view(*s["shape"]).to(device)
+        elif name == "mlp":
+            from .mlp_codec import decode_mlp
+            mlp.update(decode_mlp(data, s, device))            # raises for a model it does not know and for device="cpu"
         elif name.startswith("mlp/"):
             n = int(np.prod(s["shape"]))
             q = _unpack_bits(data, n, s["bits"]).astype(np.float32)

@@ -82,6 +82,10 @@ def build_parser():
     ap.add_argument("--occupancy-coder", dest="occupancy_coder", choices=["iid", "pyramid"], default="iid",
                     help="the container's occupancy section: one Bernoulli frequency for every cell (iid), or the grid "
                          "coded from a pyramid of itself with the tables' coder (pyramid, DESIGN.md §4.9)")
+    ap.add_argument("--mlp-coder", dest="mlp_coder", choices=["packed", "tree"], default="packed",
+                    help="the container's MLP: every tensor's 13-bit indices bit-packed (packed), or the same indices coded "
+                         "with a per-tensor bit-tree model and the tables' coder where that is smaller (tree, DESIGN.md "
+                         "§4.12); lossless either way")
     ap.add_argument("--distortion-weight", dest="distortion_weight", type=float, default=0.0,
                     help="weight of mip-NeRF 360's interval-distortion loss on the rendered samples, added to the ray loss "
                          "(mean over the batch's rays; DESIGN.md §4.10); 0 = off")
@@ -121,6 +125,7 @@ def make_config_and_data(args, device, rank=0, world=1):
               guarded_step=bool(getattr(args, "guarded_step", False)),
               device_coder=bool(getattr(args, "device_coder", False)),
               occupancy_coder=getattr(args, "occupancy_coder", "iid"),
+              mlp_coder=getattr(args, "mlp_coder", "packed"),
               distortion_weight=float(getattr(args, "distortion_weight", 0.0)),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions

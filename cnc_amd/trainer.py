@@ -89,6 +89,10 @@ class TrainConfig:
     # the occupancy section of `save_container`: "iid" (one Bernoulli frequency for every cell) or "pyramid" (the grid coded
     # from a pyramid of itself with the tables' coder, cnc_amd.occupancy_codec).  Also CNC_OCC_CODER=pyramid.
     occupancy_coder: str = "iid"
+    # the MLP of `save_container`: "packed" (every tensor's 13-bit indices bit-packed) or "tree" (the same indices coded with
+    # a per-tensor bit-tree model and the tables' coder where that is smaller, cnc_amd.mlp_codec, DESIGN.md §4.12: lossless
+    # against "packed").  Also CNC_MLP_CODER=tree.
+    mlp_coder: str = "packed"
     # the distortion regulariser (cnc_amd.nerfacc.losses.distortion): the ray loss becomes mse + this weight
     # times the mean over the batch's rays of mip-NeRF 360's interval-distortion loss on the rendered samples.  0 = off: the
     # step makes exactly the calls it makes without it
@@ -942,6 +946,14 @@ class Trainer:
             raise ValueError(f"occupancy coder must be 'iid' or 'pyramid', got {name!r}")
         return name
 
+    def mlp_coder_name(self) -> str:
+        """"tree" when this Trainer's containers code the MLP's indices with the bit-tree model (TrainConfig.mlp_coder or
+        CNC_MLP_CODER=tree), else "packed"."""
+        name = os.environ.get("CNC_MLP_CODER") or getattr(self.cfg, "mlp_coder", "packed")
+        if name not in ("packed", "tree"):
+            raise ValueError(f"mlp coder must be 'packed' or 'tree', got {name!r}")
+        return name
+
     @torch.no_grad()
     def encode(self, prefix: Optional[str] = None, coder: Optional[str] = None):
         os.makedirs(self.cfg.out_dir, exist_ok=True)
@@ -996,13 +1008,16 @@ class Trainer:
                 "log2_hashmap_size_2D": self.cfg.log2_hashmap_size_2D}
         if self.coder_name() == "device":
             meta["coder"] = "rans1"       # the table streams' format; no key = the range coder's
-        occ = self.occupancy_coder_name()
+        occ, mlp = self.occupancy_coder_name(), self.mlp_coder_name()
         size = write_container(path, meta=meta, table_streams=streams, binaries=self.estimator.binaries,
                                field_mlp=self._mlp_state(), context_state=self.context.state_dict(), occupancy_coder=occ,
-                               coder=self.coder_name(), symbols_per_lane=getattr(self.cfg, "symbols_per_lane", None))
+                               coder=self.coder_name(), symbols_per_lane=getattr(self.cfg, "symbols_per_lane", None),
+                               mlp_coder=mlp)
         res = {"file_KB": size / 1024.0, "embeddings_KB": coded_MB * 1024.0, "estimate_KB": est_MB * 1024.0}
         if occ == "pyramid":       # the section as written (the Bernoulli one still, for a grid with an odd side)
             res["occupancy_KB"] = section_sizes(path)["occupancy"] / 1024.0
+        if mlp == "tree":          # the section as written (the packed ones still, where the tree saved nothing)
+            res["mlp_KB"] = sum(v for k, v in section_sizes(path).items() if k == "mlp" or k.startswith("mlp/")) / 1024.0
         return res
 
     @torch.no_grad()

@@ -1391,6 +1391,53 @@ int cnc_occ_probs(const uint8_t* ctx, int64_t n, const float* table, float* p, v
 int cnc_occ_scatter(const float* sym, const int32_t* idx, int64_t n_cap, const void* rank_scratch, int64_t n_parents,
                     uint8_t* child, int64_t n_child, uint32_t* status, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * The entropy-coded MLP section ("tree1", DESIGN.md §4.12, csrc/mlp_tree.hip; additions: the version number stays).
+ *
+ * q / prefix: the `bits`-wide (8..16) quantisation indices of every MLP tensor, back to back in one uint16 vector of n
+ * elements (1 <= n < 2^31).  desc: n_tensors (1..65536) rows of CNC_MLP_TREE_DESC int32, in the order of the vector:
+ *   [0] first element   [1] elements   [2] depth d (0..8: the top d bits are modelled, r = bits - d stay raw)
+ *   [3] first entry of the tensor's 2^d - 1 probabilities in `tables` (heap order: plane j, prefix pi at 2^j - 1 + pi)
+ *   [4] first byte of the tensor's raw low bits   [5..7] zero   [8 + j] the tensor's first symbol in plane j's stream
+ * Stream-ordered, caller-owned buffers, no allocation, no host wait.  No call uses a descriptor member as an address
+ * without comparing it with the length given for that buffer, and every prefix is masked to the bits it can have: rows
+ * that do not fit (or a damaged stream) give wrong values, never an access outside the buffers.
+ * CNC_ERR_INVALID_VALUE for a null pointer, n, n_tensors, bits or plane outside the ranges above.
+ * ---------------------------------------------------------------------------------------- */
+#define CNC_MLP_TREE_DESC 16
+
+/* hist[t][(q >> (bits - 8)) & 255] += 1 for every element of tensor t; hist: n_tensors x 256 words the caller zeroed.
+ * Per-workgroup LDS bins flushed with integer atomics: exact, and the same whatever the order.                        */
+int cnc_mlp_tree_hist(const uint16_t* q, int64_t n, const int32_t* desc, int32_t n_tensors, int32_t bits, uint32_t* hist,
+                      void* stream);
+
+/* An encode, every plane in one launch: element e of a tensor with depth d writes, for each plane j < d, at
+ * plane_base[j] + desc[8 + j] + e the symbol sym = +1.0f / -1.0f for bit bits - 1 - j set / clear and the probability
+ * p = tables[desc[3] + 2^j - 1 + (q >> (bits - j))].  plane_base: 8 int64 on the HOST, read before the call returns.
+ * sym, p: n_out floats; tables: n_tab floats.  n_out == 0 (nothing modelled) succeeds and touches nothing.           */
+int cnc_mlp_tree_emit(const uint16_t* q, int64_t n, const int32_t* desc, int32_t n_tensors, int32_t bits, const float* tables,
+                      int64_t n_tab, const int64_t* plane_base, float* sym, float* p, int64_t n_out, void* stream);
+
+/* A decode, plane `plane` (0..7): p[desc[8 + plane] + e] = tables[desc[3] + 2^plane - 1 + (prefix & (2^plane - 1))] for
+ * the elements of every tensor with depth > plane; prefix holds the `plane` bits decoded so far.                    */
+int cnc_mlp_tree_probs(const uint16_t* prefix, int64_t n, const int32_t* desc, int32_t n_tensors, int32_t bits, int32_t plane,
+                       const float* tables, int64_t n_tab, float* p, int64_t n_out, void* stream);
+
+/* After the coder returned plane `plane`'s n_sym symbols: prefix = prefix << 1 | (sym > 0) for the same elements.     */
+int cnc_mlp_tree_fold(const float* sym, int64_t n_sym, uint16_t* prefix, int64_t n, const int32_t* desc, int32_t n_tensors,
+                      int32_t bits, int32_t plane, void* stream);
+
+/* The raw low bits: tensor by tensor (from byte desc[4]) its elements' r low bits, value i's bit b at bit i r + b, byte
+ * k >> 3, bit k & 7 — the order of the container's packed sections; the last byte of a tensor is padded with zeros.
+ * One lane per byte of `low` (n_low bytes, all written), no atomics.  n_low == 0 succeeds and touches nothing.       */
+int cnc_mlp_tree_pack_low(const uint16_t* q, int64_t n, const int32_t* desc, int32_t n_tensors, int32_t bits, uint8_t* low,
+                          int64_t n_low, void* stream);
+
+/* The inverse, one lane per element: q = (prefix & (2^d - 1)) << r | the element's r bits of `low`.  Every element of q
+ * is written (0 where no row covers it).  low may be NULL when n_low == 0.                                           */
+int cnc_mlp_tree_unpack(const uint16_t* prefix, int64_t n, const int32_t* desc, int32_t n_tensors, int32_t bits,
+                        const uint8_t* low, int64_t n_low, uint16_t* q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
