@@ -240,6 +240,11 @@ SIGNATURES = {
     "cnc_mlp_tree_fold": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp],
     "cnc_mlp_tree_pack_low": [_vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp],
     "cnc_mlp_tree_unpack": [_vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp],
+    "cnc_iso_active_points": [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "cnc_iso_lattice_positions": [_vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(_f32), C.POINTER(_f32), _vp, _vp],
+    "cnc_iso_classify": [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp],
+    "cnc_iso_emit_vertices": [_vp, _i32, _i32, _i32, _f32, C.POINTER(_f32), C.POINTER(_f32), _vp, _vp, _i64, _vp, _vp, _vp],
+    "cnc_iso_emit_faces": [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
 }
 
 # entry points that return something other than a status code
@@ -272,6 +277,7 @@ CNC_VERDICT_MAX_TENSORS = 48
 CNC_OCC_STATUS_COUNT = 1
 CNC_OCC_STATUS_INDEX = 2
 CNC_MLP_TREE_DESC = 16
+CNC_ISO_TABLE = 672
 CNC_CAMERA_ROW = 24
 CNC_CAMERA_PINHOLE = 0
 CNC_CAMERA_OPENCV = 1

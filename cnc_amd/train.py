@@ -9,8 +9,9 @@ default of `TrainConfig`.  What runs: train -> evaluate -> encode (.b files) -> 
 
 No dataset ships with this repository (no network): `--dataset procedural` (default when --data_root does not
 exist) trains on the built-in analytic scene so the whole protocol can be exercised anywhere.
-Extensions: --max_steps, --test_views (subset of the test images), --results, --dataset, and `--dataset transforms`
-(+ --aabb): a capture of one's own in the instant-ngp / nerfstudio transforms.json layout, lens distortion included.
+Extensions: --max_steps, --test_views (subset of the test images), --results, --dataset, `--dataset transforms`
+(+ --aabb): a capture of one's own in the instant-ngp / nerfstudio transforms.json layout, lens distortion included, and
+--save-mesh (+ --mesh-resolution, --mesh-threshold): the trained scene's surface as a PLY.
 """
 from __future__ import annotations
 
@@ -89,6 +90,14 @@ def build_parser():
     ap.add_argument("--distortion-weight", dest="distortion_weight", type=float, default=0.0,
                     help="weight of mip-NeRF 360's interval-distortion loss on the rendered samples, added to the ray loss "
                          "(mean over the batch's rays; DESIGN.md §4.10); 0 = off")
+    ap.add_argument("--save-mesh", dest="save_mesh", type=str, default=None, metavar="PATH",
+                    help="at the very end, write the scene's surface as a binary PLY: marching tetrahedra on the density of "
+                         "the model a receiver would hold (decoded tables, 13-bit MLP; DESIGN.md §4.13); default: off")
+    ap.add_argument("--mesh-resolution", dest="mesh_resolution", type=int, default=256,
+                    help="--save-mesh: lattice cells along the box's longest side")
+    ap.add_argument("--mesh-threshold", dest="mesh_threshold", type=float, default=None,
+                    help="--save-mesh: the density of the surface; default ln 2 / render_step_size (one render step half "
+                         "opaque), which scales with the scene and has not been tuned")
     return ap
 
 
@@ -127,6 +136,8 @@ def make_config_and_data(args, device, rank=0, world=1):
               occupancy_coder=getattr(args, "occupancy_coder", "iid"),
               mlp_coder=getattr(args, "mlp_coder", "packed"),
               distortion_weight=float(getattr(args, "distortion_weight", 0.0)),
+              save_mesh=getattr(args, "save_mesh", None), mesh_resolution=int(getattr(args, "mesh_resolution", 256)),
+              mesh_threshold=getattr(args, "mesh_threshold", None),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0
@@ -260,6 +271,10 @@ def main(argv=None):
     with open(out, "a") as fw:
         fw.write("\t".join(cols) + "\n")
     print(f"results line appended to {out}")
+    if cfg.save_mesh:
+        # last of all, on the decoded tables and the 13-bit MLP: the mesh of the model a receiver would hold
+        mesh = tr.extract_mesh(cfg.save_mesh, resolution=cfg.mesh_resolution, threshold=cfg.mesh_threshold)
+        print(f"mesh: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces written to {cfg.save_mesh}")
     return cols
 
 

@@ -97,6 +97,12 @@ class TrainConfig:
     # times the mean over the batch's rays of mip-NeRF 360's interval-distortion loss on the rendered samples.  0 = off: the
     # step makes exactly the calls it makes without it
     distortion_weight: float = 0.0
+    # mesh export (cnc_amd.mesh): `python -m cnc_amd.train --save-mesh PATH` writes the trained scene's
+    # iso-surface as a PLY at the very end of the run.  None = off: the run and its results line are what they were.
+    # mesh_threshold None = ln 2 / render_step_size (`Trainer.extract_mesh`)
+    save_mesh: Optional[str] = None
+    mesh_resolution: int = 256
+    mesh_threshold: Optional[float] = None
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -933,6 +939,21 @@ class Trainer:
         return tot / max(n_views, 1)
 
     # ------------------------------------------------------------------------------ codec
+    def extract_mesh(self, path: Optional[str] = None, resolution: int = 256, threshold: Optional[float] = None,
+                     colors: bool = True, return_lattice: bool = False):
+        """The scene's surface as a `cnc_amd.mesh.Mesh`: marching tetrahedra on a lattice of `resolution`
+        cells along the box's longest side, the field's `query_density` evaluated where the estimator's level-0 grid does
+        not rule a point out — the scene as the renderer sees it.  threshold None: the density at which one render step
+        is half opaque, ln 2 / cfg.render_step_size; it scales with the scene and has not been tuned.  colors: the field
+        once on the vertices, seen along -normal.  path: also written there as a binary PLY.  return_lattice (debugging):
+        -> (mesh, the capped float32 lattice it was cut from)."""
+        from .mesh import field_mesh
+        out = field_mesh(self.field, self.estimator.aabbs[0], self.estimator.binaries[0], self.cfg.render_step_size,
+                         resolution=resolution, threshold=threshold, colors=colors, return_lattice=return_lattice)
+        if path is not None:
+            (out[0] if return_lattice else out).save(path)
+        return out
+
     def coder_name(self) -> str:
         """"device" when this Trainer codes with the device coder (TrainConfig.device_coder or CNC_DEVICE_CODER=1)."""
         on = bool(getattr(self.cfg, "device_coder", False)) or os.environ.get("CNC_DEVICE_CODER", "0") == "1"

@@ -1438,6 +1438,58 @@ int cnc_mlp_tree_pack_low(const uint16_t* q, int64_t n, const int32_t* desc, int
 int cnc_mlp_tree_unpack(const uint16_t* prefix, int64_t n, const int32_t* desc, int32_t n_tensors, int32_t bits,
                         const uint8_t* low, int64_t n_low, uint16_t* q, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Mesh export: marching tetrahedra on a density lattice (csrc/iso_surface.hip; additions: the version
+ * number stays).  An extension: the reference has no exporter.
+ *
+ * The lattice has nx x ny x nz cells (each >= 1) and (nx + 1)(ny + 1)(nz + 1) < 2^31 points, x fastest:
+ * lin = (z (ny + 1) + y)(nx + 1) + x; cells likewise over (nx, ny, nz).  A point is INSIDE iff density >= threshold (NaN
+ * is outside).  An edge belongs to its lower end, its owner, and has one of seven directions: 0 (1,0,0)  1 (0,1,0)
+ * 2 (0,0,1)  3 (1,1,0)  4 (0,1,1)  5 (1,0,1)  6 (1,1,1); it carries a vertex iff its ends differ in "inside".  A cell is
+ * split into the six tetrahedra v0 = corner, v1 = v0 + e_p1, v2 = v1 + e_p2, v3 = corner + (1,1,1), p running through the
+ * axis permutations in lexicographic order; bit k of a tetrahedron's mask is "vk inside".
+ * table: CNC_ISO_TABLE int8, [6][16][7] = per (tetrahedron, mask) the triangle count (0..2) and three codes per triangle,
+ * code = corner * 8 + direction, corner = dx | dy << 1 | dz << 2 the owner of the edge that carries the triangle's vertex
+ * (cnc_amd/mesh.py tet_table() generates it; the library holds no copy).
+ * lo, h: 3 floats each on the HOST, read before the call returns: a point's position is lo + (float)i * h per component.
+ * Stream-ordered, caller-owned buffers, no allocation, no host wait, no atomics: outputs are written at the offsets the
+ * caller's exclusive prefix sums give, each compared with the output's length first.
+ * ---------------------------------------------------------------------------------------- */
+#define CNC_ISO_TABLE 672
+
+/* active[lin] = 1 iff some set cell of the occupancy grid (bytes [gx, gy, gz] over the same box, C order, non-zero = set)
+ * overlaps [p - h, p + h], else 0.  Decided per axis in integers: cell j overlaps point i iff j n <= (i + 1) g and
+ * (j + 1) n >= (i - 1) g (touching counts).                                                                           */
+int cnc_iso_active_points(const uint8_t* occupancy, int32_t gx, int32_t gy, int32_t gz, int32_t nx, int32_t ny, int32_t nz,
+                          uint8_t* active, void* stream);
+
+/* positions[i] (float32 [m, 3]) = the world position of lattice point lin[i], or of point first + i when lin is NULL.   */
+int cnc_iso_lattice_positions(const int64_t* lin, int64_t first, int64_t m, int32_t nx, int32_t ny, int32_t nz,
+                              const float* lo, const float* h, float* positions, void* stream);
+
+/* cap != 0: every point on the box's boundary gets density 0, in place, before anything else.  edge_mask[lin]: bit k =
+ * the point's edge of direction k carries a vertex.  cell_tris[cell] = the cell's triangle count, 0..12.  threshold > 0
+ * and finite.                                                                                                         */
+int cnc_iso_classify(float* density, int32_t nx, int32_t ny, int32_t nz, float threshold, int32_t cap, const int8_t* table,
+                     uint8_t* edge_mask, uint8_t* cell_tris, void* stream);
+
+/* vertex_scan: the exclusive prefix sum of popcount(edge_mask), int32 per point.  The vertex of the edge from a (owner)
+ * to b is pa + t (pb - pa) per component, t = (threshold - Da) / (Db - Da), at vertex_scan[a] + the direction's rank in
+ * a's mask: order by owner, then direction.  normals (nullable, [n_vertices, 3]): the gradients at a and b (central
+ * differences over 2 h, one-sided over h on the boundary) interpolated with the same t, negated, divided by their
+ * length (a zero vector stays zero).  n_vertices == 0 succeeds and touches nothing.                                   */
+int cnc_iso_emit_vertices(const float* density, int32_t nx, int32_t ny, int32_t nz, float threshold, const float* lo,
+                          const float* h, const uint8_t* edge_mask, const int32_t* vertex_scan, int64_t n_vertices,
+                          float* vertices, float* normals, void* stream);
+
+/* cell_scan: the exclusive prefix sum of cell_tris, int32 per cell.  faces (int32 [n_faces, 3], 3 n_faces < 2^31): a
+ * cell's triangles from cell_scan[cell] on, by tetrahedron, then triangle; a vertex's index is vertex_scan[owner] + the
+ * direction's rank in the owner's mask.  Counter-clockwise seen from the low-density side.  n_faces == 0 succeeds and
+ * touches nothing.                                                                                                    */
+int cnc_iso_emit_faces(const float* density, int32_t nx, int32_t ny, int32_t nz, float threshold, const int8_t* table,
+                       const uint8_t* edge_mask, const int32_t* vertex_scan, const uint8_t* cell_tris, const int32_t* cell_scan,
+                       int64_t n_vertices, int64_t n_faces, int32_t* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
