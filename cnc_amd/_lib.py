@@ -186,6 +186,9 @@ SIGNATURES = {
     "cnc_lens_undistort": [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _i64, _vp],
     "cnc_lens_undistort_fisheye": [_vp, _vp, _i64, _f32, _i32, _vp, _i64, _vp],
     "cnc_camera_rays": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cnc_camera_pose_apply": [_vp, _vp, _i32, _vp, _vp],
+    "cnc_ray_pose_grad_workspace": [_u32, _i32],
+    "cnc_ray_pose_grad": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _u32, _i32, _vp, C.c_uint64, _vp, _vp],
     "cnc_level_stats_forward": [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
     "cnc_level_stats_backward": [_vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _vp, _vp],
     "cnc_field_prepare": [_vp, _vp, _u32, _vp, _vp, _vp],
@@ -197,6 +200,7 @@ SIGNATURES = {
     "cnc_field_weight_grads_workspace": [C.POINTER(FieldWGrad), C.POINTER(C.c_uint64)],
     "cnc_field_weight_grads": [C.POINTER(FieldWGrad), _vp],
     "cnc_field_fused_forward": [C.POINTER(FusedField), _vp, _vp, _u32, _vp, _vp, _vp],
+    "cnc_field_position_grad": [C.POINTER(FusedField), _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp],
     "cnc_ste_binary_forward": [_vp, _vp, C.c_uint64, _vp],
     "cnc_ste_binary_backward": [_vp, _vp, _vp, C.c_uint64, _vp],
     "cnc_relu_backward_bias_partials": [_u32],
@@ -253,7 +257,8 @@ RESTYPES = {"cnc_grid_encode_backward_binned_workspace": C.c_uint64,
             "cnc_grid_encode_backward_ordered_workspace": C.c_uint64, "cnc_bernoulli_bits_partials": C.c_uint32,
             "cnc_ctx_mlp_backward_ordered_workspace": C.c_uint64, "cnc_field_backward_chain_ordered_workspace": C.c_uint64,
             "cnc_relu_backward_bias_partials": C.c_uint32, "cnc_occupancy_coarse_words": C.c_uint32,
-            "cnc_rans_scratch_bytes": C.c_uint64, "cnc_occ_rank_scratch_bytes": C.c_uint64}
+            "cnc_rans_scratch_bytes": C.c_uint64, "cnc_occ_rank_scratch_bytes": C.c_uint64,
+            "cnc_ray_pose_grad_workspace": C.c_uint64}
 
 CNC_FLAG_STE_BINARY = 1
 CNC_FLAG_LEVELS_FINEST_FIRST = 2

@@ -197,6 +197,9 @@ class TransformsLoader(_PosedImages):
     OPENGL_CAMERA = True
     TRAIN_SPLITS = ("train",)
     HOLD_OUT = 8
+    # set (on the instance) by pose refinement: a training batch also holds "camera_ids" i64 [num_rays], the row of
+    # `cameras` every ray was drawn from (cnc_amd.poses).  Off: the batch dict is what it always was
+    with_camera_ids = False
 
     def __init__(self, subject_id: str, root_fp: str, split: str, color_bkgd_aug: str = "white",
                  num_rays: int = None, near: float = None, far: float = None,
@@ -214,8 +217,12 @@ class TransformsLoader(_PosedImages):
         with open(path) as fp:
             meta = json.load(fp)
         frames = list(meta["frames"])
+        # where this split's cameras come from: the file, and each camera's index in its `frames` (cnc_amd.poses writes
+        # refined poses back there)
+        self.transforms_path, self.frame_ids = path, list(range(len(frames)))
         if path != per_split:
-            frames = [fr for i, fr in enumerate(frames) if (i % self.HOLD_OUT == 0) == (split == "test")]
+            self.frame_ids = [i for i in self.frame_ids if (i % self.HOLD_OUT == 0) == (split == "test")]
+            frames = [frames[i] for i in self.frame_ids]
         if not frames:
             raise ValueError(f"{path}: no frames for split '{split}'")
         images, rows, lens, models = [], [], [], set()
@@ -300,9 +307,12 @@ class TransformsLoader(_PosedImages):
             o, d, pix = camera_backend.camera_rays(self.cameras, self.model, self.OPENGL_CAMERA, cam0=int(index),
                                                    width=self.WIDTH, height=self.HEIGHT, images=self.images, bkgd=bkgd,
                                                    eps=self.eps, iters=self.iters)
-        return {"pixels": pix.reshape(*shape, 3),
-                "rays": Rays(origins=o.reshape(*shape, 3), viewdirs=d.reshape(*shape, 3)),
-                "color_bkgd": bkgd}
+        out = {"pixels": pix.reshape(*shape, 3),
+               "rays": Rays(origins=o.reshape(*shape, 3), viewdirs=d.reshape(*shape, 3)),
+               "color_bkgd": bkgd}
+        if self.with_camera_ids and self.training:
+            out["camera_ids"] = ids
+        return out
 
 
 class SyntheticBallDataset:

@@ -563,6 +563,42 @@ class FusedFieldForward:
         out["clips"] = clips
         return rgb, density, out
 
+    @torch.no_grad()
+    def position_grad(self, positions: torch.Tensor, selector, dX, dS, params=None):
+        """dL/dx [N, 3] of the world positions of a saving forward (cnc_field_position_grad): `selector` [>= N] and the
+        tables `params` are that forward's, `dX` [>= N, ld] the gradient of the feature matrix's encoder columns as the
+        chain kernel leaves it, `dS` [>= N, 3 + 6 n_freqs] the gradient of the columns behind them.  Bounded fields only."""
+        from . import _lib
+        f = self.field
+        if f.unbounded:
+            raise ValueError("position gradients: bounded fields only (the contraction's derivative is not built)")
+        mb = f.mlp_base
+        x = positions.reshape(-1, 3).contiguous()
+        N, dev = x.shape[0], x.device
+        if x.dtype != torch.float32 or not x.is_cuda or dX.dtype != torch.float32 or dS.dtype != torch.float32:
+            raise RuntimeError("position_grad: float32 CUDA tensors")
+        if dX.stride(1) != 1 or dS.stride(1) != 1 or selector.shape[0] < N or dX.shape[0] < N or dS.shape[0] < N:
+            raise RuntimeError("position_grad: row-major dX / dS and a selector of at least N rows")
+        if self._units is None or self._units.device != dev:
+            raise RuntimeError("position_grad: no forward has run on this device")
+        st = _lib.FusedField()
+        aabb = f.aabb if f.aabb.is_contiguous() else f.aabb.contiguous()
+        st.aabb = aabb.data_ptr()
+        keep = [aabb]
+        for k, e in enumerate(mb._encoders()):
+            bits, _ = e._bit_plane(e.params if params is None else params[k])
+            keep.append(bits)
+            st.bits[k], st.offsets[k], st.resolutions[k] = bits.data_ptr(), e.offsets_list.data_ptr(), e.resolutions_list.data_ptr()
+            st.n_levels[k] = e.n_levels
+        st.freqs, st.n_freqs = mb._freqs.data_ptr(), mb._freqs.numel()
+        st.units, st.n_features = self._units.data_ptr(), mb.encoding_xyz.n_features
+        g_x = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        import ctypes
+        _lib.check(_lib.lib().cnc_field_position_grad(ctypes.byref(st), x.data_ptr(), selector.data_ptr(), dX.data_ptr(),
+                                                      dX.stride(0), dS.data_ptr(), dS.stride(0), N, g_x.data_ptr(),
+                                                      _lib.stream(dev)), "field_position_grad")
+        return g_x.view(positions.shape)
+
     def guard_words(self):
         """The range guard's words on the host (a synchronisation): [last call that saturated / overflowed, layer flags]."""
         return None if self._buffers is None else self._buffers["guard"][:6].tolist()
@@ -618,10 +654,12 @@ class _FieldChain(Function):
         return (dX if need[0] else None, None, None, None, *layer_grads)
 
     @staticmethod
-    def chain(field, g_rgb, g_density, feat, selector, h1, base_out, head_in, h3, h4, rgb, Ws, need, ld_x, gap):
+    def chain(field, g_rgb, g_density, feat, selector, h1, base_out, head_in, h3, h4, rgb, Ws, need, ld_x, gap, keep=None):
         """(dX [Np, ld_x]: the gradient of the feature matrix's encoder columns; [dW1, db1, ..., dW5, db5], None where
         `need` says so) from the gradients of rgb / density and what the forward kept.  `base_out`: [Np, >= 1], column 0
-        = the raw density.  `gap`: `head_in` is in the fused kernel's layout [SH4 | 0 | geo] (cnc_field_save_t)."""
+        = the raw density.  `gap`: `head_in` is in the fused kernel's layout [SH4 | 0 | geo] (cnc_field_save_t).
+        `keep` (a dict): receives "G1" [Np, H], the gradient of the first layer's output the kernel left in HBM — what
+        the position gradient's sinusoid columns are made of (`_FieldTrain.backward`)."""
         from . import _lib
         from .mlp import splitk_weight_grad
         W1, W2, W3, W4, W5 = Ws
@@ -662,6 +700,8 @@ class _FieldChain(Function):
         else:
             _repro.ROUTE_CALLS["field_default"] += 1
             _lib.check(_lib.lib().cnc_field_backward_chain(ctypes.byref(st), _lib.stream(dev)), "field_backward_chain")
+        if keep is not None:
+            keep["G1"] = G1
         pairs = ((G1, feat, K0, H), (G2, h1, H, 1 + geo), (G3, head_in, 16 + geo, H), (G4, h3, H, H), (G5, h4, H, 3))
         gws = [None] * 5
         if any(need[0::2]):
@@ -707,14 +747,22 @@ class _FieldTrain(Function):
     post kernel, the sigmoid, 3 slice copies and their fills.
 
     Values: the layers in the three-product fp16 form (~5e-7 per term) where the op chain runs fp32
-    library GEMMs; the encoders' features are bit-identical.  Rows [N, Np) are rows of padding (`_bucket_rows`)."""
+    library GEMMs; the encoders' features are bit-identical.  Rows [N, Np) are rows of padding (`_bucket_rows`).
+
+    Positions that require grad receive dL/dx (cnc_field_position_grad): the derivative of the four
+    encoders' interpolation, the normaliser of border cells included, and of the raw-coordinate and sinusoid columns,
+    through the gradient the chain kernel left — one library GEMM (G1 times the sinusoid columns of W1) and one kernel
+    more, and only then.  The gradient with respect to the VIEW DIRECTION is deliberately not provided (as in
+    instant-ngp: the direction's path through the head is left out of the pose gradient); `directions.requires_grad`
+    raises in `NGPRadianceField_mygrid_2D3D.forward`.  A row outside the box (selector 0) gets a zero gradient."""
 
     @staticmethod
     def forward(ctx, positions, dirs, field, Np, *params_and_layers):
         params, layers = params_and_layers[:4], params_and_layers[4:]
         rgb, density, kept = field._field_fused.save_forward(positions, dirs, Np, params)
         ctx.save_for_backward(kept["feat"], kept["selector"], kept["h1"], kept["raw"], kept["head_in"], kept["h3"], kept["h4"],
-                              rgb, kept["xyz"], kept["xy"], kept["xz"], kept["yz"], *params, *kept["clips"], *layers[0::2])
+                              rgb, kept["xyz"], kept["xy"], kept["xz"], kept["yz"], *params, *kept["clips"], *layers[0::2],
+                              positions)
         ctx.field, ctx.N = field, positions.shape[0]
         from . import _gradsink
         ctx.sink = _gradsink.current()     # the caller thread's sink; the backward runs on autograd's own thread
@@ -728,12 +776,19 @@ class _FieldTrain(Function):
         xs, params, clips, Ws = t[8:12], t[12:16], t[16:20], t[20:25]
         field, need = ctx.field, ctx.needs_input_grad
         owner = field.mlp_base
+        keep = {} if need[0] else None
         dX, layer_grads = _FieldChain.chain(field, g_rgb, g_density, feat, selector, h1, raw, head_in, h3, h4, rgb, Ws,
-                                            need[8:18], owner._layout()[0], gap=True)
+                                            need[8:18], owner._layout()[0], gap=True, keep=keep)
+        g_x = None
+        if need[0]:
+            # the gradient of the 3 + 6 n_freqs columns behind the encoders': G1 times those columns of W1
+            n_enc = sum(e.n_output_dims for e in owner._encoders())
+            dS = keep["G1"] @ Ws[0][:, n_enc:n_enc + 3 + 6 * owner._freqs.numel()]
+            g_x = field._field_fused.position_grad(t[25], selector, dX, dS, params)
         grads = [None] * 4
         if any(need[4:8]):
             grads = _FusedFeatures.scatter(owner, dX, xs, params, clips, ctx.N, ctx.sink)
-        return (None, None, None, None, *grads, *layer_grads)
+        return (g_x, None, None, None, *grads, *layer_grads)
 
 
 class NGPRadianceField_mygrid_2D3D(nn.Module):
@@ -874,6 +929,23 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         if self._field_fused is None:
             self._field_fused = FusedFieldForward(self) if FusedFieldForward.shapes_ok(self) else False
         return bool(self._field_fused)
+
+    def _check_position_grad(self, positions, directions):
+        """`positions.requires_grad` on a CUDA call: only the fused training path provides dL/dx (`_FieldTrain`), so
+        every other way through `forward` raises instead of handing autograd a position without a gradient.  (`_train_ok`
+        itself keeps answering for positions without a gradient: it is asked about the detached positions here, and
+        `forward` takes the path on this check's word.)"""
+        if self.unbounded:
+            raise ValueError("positions.requires_grad: position gradients are built for bounded fields only "
+                             "(unbounded=True contracts the position inside the kernels)")
+        if directions is None or directions.requires_grad:
+            raise ValueError("positions.requires_grad: the gradient with respect to the view direction is not provided; "
+                             "pass directions that do not require grad")
+        if not (directions.is_cuda and directions.dtype == torch.float32 and self.use_viewdirs and self.geo_feat_dim > 0
+                and self._train_ok(positions.detach(), directions)):
+            raise RuntimeError("positions.requires_grad: the fused training path is not available for this call (switched "
+                               "off by the range guard or the environment, or a shape the gradient chain is not built for) "
+                               "and no other path provides position gradients")
 
     def check_range_guard(self) -> bool:
         """For the training loop, at a point where it synchronises anyway: True when a saving forward since the last check
@@ -1067,6 +1139,9 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
     def forward(self, positions: torch.Tensor, directions: torch.Tensor = None):
         if self.use_viewdirs and (directions is not None):
             assert positions.shape == directions.shape, f"{positions.shape} v.s. {directions.shape}"
+        want_gx = positions.is_cuda and positions.requires_grad and torch.is_grad_enabled()
+        if want_gx:
+            self._check_position_grad(positions, directions)
         if directions is not None and self.use_viewdirs and directions.is_cuda:
             fused = self._fused_forward(positions)
             if fused is not None:
@@ -1076,7 +1151,7 @@ class NGPRadianceField_mygrid_2D3D(nn.Module):
         if directions is not None and self.use_viewdirs and self.geo_feat_dim > 0 and self._glue_ok(positions) \
                 and directions.is_cuda and directions.dtype == torch.float32:
             lead = list(positions.shape[:-1])
-            if self._train_ok(positions, directions):
+            if want_gx or self._train_ok(positions, directions):
                 # the gradient pass: ONE kernel forward (the fused evaluator, saving what the backward reads), the
                 # gradient chain kernel + weight gradients + the encoders' scatter backward (`_FieldTrain`)
                 p = positions.reshape(-1, 3)

@@ -60,8 +60,11 @@ def _mid_points(origins, dirs, ray_indices, t_starts, t_ends):
 class _FieldOnRays:
     """The two callbacks the sampler / compositor want, bound to one set of rays."""
 
-    def __init__(self, field, origins, dirs, with_positions):
+    def __init__(self, field, origins, dirs, with_positions, position_grad=False):
         self.field, self.o, self.d, self.with_positions = field, origins, dirs, with_positions
+        # the sample positions as a leaf that requires grad (pose refinement, DESIGN.md §4.14): the field's backward then
+        # leaves dL/dx in its `.grad`
+        self.position_grad = position_grad
 
     def density(self, t_starts, t_ends, ray_indices):
         x, _ = _mid_points(self.o, self.d, ray_indices, t_starts, t_ends)
@@ -86,6 +89,8 @@ class _FieldOnRays:
 
     def colour_and_density_at(self, x, v):
         """The same for sample positions / directions the caller already has (cnc_march_samples' extras)."""
+        if self.position_grad:
+            x = x.detach().requires_grad_(True)
         rgb, sigma = self.field(x, v)
         sigma = sigma.squeeze(-1)
         return (rgb, sigma, x) if self.with_positions else (rgb, sigma)
@@ -96,15 +101,19 @@ def render_image_with_occgrid(radiance_field: torch.nn.Module, estimator: OccGri
                               render_bkgd: Optional[torch.Tensor] = None, cone_angle: float = 0.0,
                               alpha_thre: float = 0.0, test_chunk_size: int = 8192,
                               timestamps: Optional[torch.Tensor] = None, return_extra=False, tmp=None, *,
-                              with_samples=False):
+                              with_samples=False, position_grad=False):
     """(rgb, opacity, depth, n_samples[, extras]) for a batch or an image of rays.  Training renders every
     ray in one go with jittered sample offsets; evaluation goes `test_chunk_size` rays at a time.  For each
     chunk the estimator picks the samples (a gradient-free density pass decides visibility), then the field is
     queried with gradients and composited.  `with_samples` (extension; implies `return_extra`): the extras are a
     copy that also holds the samples they belong to, `t_starts`, `t_ends`, `ray_indices` and `packed_info` (of the
-    last chunk, like the other extras) — what a loss on the samples needs (`cnc_amd.nerfacc.losses.distortion`)."""
+    last chunk, like the other extras) — what a loss on the samples needs (`cnc_amd.nerfacc.losses.distortion`).
+    `position_grad` (extension; implies `with_samples`): the sample positions the field is queried at are a leaf that
+    requires grad, handed out as the extras' `positions` — after the backward its `.grad` is dL/dx per sample, what the
+    camera-pose gradient is folded from (`cnc_amd.poses`)."""
     if timestamps is not None:
         raise NotImplementedError("time-dependent fields (dnerf) are outside the CNC path")
+    with_samples = with_samples or position_grad
     rays, lead = _as_ray_list(rays)
     total = rays.origins.shape[0]
     training = radiance_field.training
@@ -112,7 +121,7 @@ def render_image_with_occgrid(radiance_field: torch.nn.Module, estimator: OccGri
     parts, n_samples, extras = [], 0, None
     for first in range(0, total, max(per_chunk, 1)):
         o, d = rays.origins[first:first + per_chunk], rays.viewdirs[first:first + per_chunk]
-        fn = _FieldOnRays(radiance_field, o, d, with_positions=True)
+        fn = _FieldOnRays(radiance_field, o, d, with_positions=True, position_grad=position_grad)
         ray_indices, t_starts, t_ends = estimator.sampling(
             o, d, sigma_fn=fn.density, near_plane=near_plane, far_plane=far_plane,
             render_step_size=render_step_size, stratified=training, cone_angle=cone_angle, alpha_thre=alpha_thre)

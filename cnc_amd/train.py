@@ -11,7 +11,9 @@ No dataset ships with this repository (no network): `--dataset procedural` (defa
 exist) trains on the built-in analytic scene so the whole protocol can be exercised anywhere.
 Extensions: --max_steps, --test_views (subset of the test images), --results, --dataset, `--dataset transforms`
 (+ --aabb): a capture of one's own in the instant-ngp / nerfstudio transforms.json layout, lens distortion included, and
---save-mesh (+ --mesh-resolution, --mesh-threshold): the trained scene's surface as a PLY.
+--save-mesh (+ --mesh-resolution, --mesh-threshold): the trained scene's surface as a PLY, and --refine-poses LR
+(+ --refine-poses-from STEP): a capture's training poses refined next to the field, written to
+<out_dir>/transforms_refined.json.
 """
 from __future__ import annotations
 
@@ -98,6 +100,12 @@ def build_parser():
     ap.add_argument("--mesh-threshold", dest="mesh_threshold", type=float, default=None,
                     help="--save-mesh: the density of the surface; default ln 2 / render_step_size (one render step half "
                          "opaque), which scales with the scene and has not been tuned")
+    ap.add_argument("--refine-poses", dest="refine_poses", type=float, default=0.0, metavar="LR",
+                    help="--dataset transforms: learn a correction (rotation vector, translation) of every training "
+                         "camera's pose at this Adam learning rate (DESIGN.md §4.14) and write the capture with the refined "
+                         "poses to <out_dir>/transforms_refined.json; 0 = off.  The rate has no tuned default")
+    ap.add_argument("--refine-poses-from", dest="refine_poses_from", type=int, default=0, metavar="STEP",
+                    help="--refine-poses: the first step that moves the poses")
     return ap
 
 
@@ -138,6 +146,7 @@ def make_config_and_data(args, device, rank=0, world=1):
               distortion_weight=float(getattr(args, "distortion_weight", 0.0)),
               save_mesh=getattr(args, "save_mesh", None), mesh_resolution=int(getattr(args, "mesh_resolution", 256)),
               mesh_threshold=getattr(args, "mesh_threshold", None),
+              pose_lr=float(getattr(args, "refine_poses", 0.0)), pose_refine_from=int(getattr(args, "refine_poses_from", 0)),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0

@@ -103,6 +103,11 @@ class TrainConfig:
     save_mesh: Optional[str] = None
     mesh_resolution: int = 256
     mesh_threshold: Optional[float] = None
+    # camera pose refinement (cnc_amd.poses): the learning rate of one (omega, tau) per training camera, from
+    # step `pose_refine_from` on.  0 = off: no object, launch or batch key more than without it.  Also CNC_POSE_LR.  A capture
+    # through `TransformsLoader` on the GPU, one process, a bounded field; the rate has no tuned default
+    pose_lr: float = 0.0
+    pose_refine_from: int = 0
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -227,6 +232,9 @@ class Trainer:
         self.dataset = dataset if dataset is not None else \
             SyntheticBallDataset(c.image_size, device=self.device, seed=c.seed + 1000 * self.rank)
         self.dataset.update_num_rays(c.init_batch_size)
+        # ---- camera pose refinement: nothing unless asked for (`enable_pose_refinement`, called behind the optimizers)
+        self.pose_refiner = self.opt_pose = self._pose_base = None
+        self._pose_from, self._pose_on = 0, False
         # ---- the guarded step's decision, taken here and nowhere else: `_make_optimizers` builds the verdict's buffer from
         # it, the gradient bucket sizes its tail from it
         self._guarded = bool(getattr(c, "guarded_step", False)) or os.environ.get("CNC_GUARDED_STEP", "0") == "1"
@@ -297,6 +305,85 @@ class Trainer:
             self._ctx_rand = None
             self.context.rand_like = synced_rand_like
         self._check_table_adam()
+        pose_lr = float(getattr(c, "pose_lr", 0.0)) or float(os.environ.get("CNC_POSE_LR", "0") or 0.0)
+        if pose_lr > 0:
+            self.enable_pose_refinement(pose_lr, int(getattr(c, "pose_refine_from", 0)))
+
+    # -------------------------------------------------------------------------------- camera pose refinement
+    def enable_pose_refinement(self, lr: float, start: int = 0) -> None:
+        """From step `start` on, every step also learns one (omega, tau) per training camera at rate `lr` (DESIGN.md
+        §4.14): the render pass hands back dL/dx per sample, `CameraPoseRefiner.accumulate` folds it per camera, an Adam of
+        its own (fused, no weight decay; the guarded step's verdict covers it) updates `delta`, and
+        cnc_camera_pose_apply rewrites the loader's camera table from a copy of the file's.  ValueError where that cannot
+        work: anything but a `LoaderDataset` over a `TransformsLoader` on the GPU, data parallel, an unbounded field, or a
+        model outside the fused training path's shapes (the only path with position gradients)."""
+        from .datasets import TransformsLoader
+        from .field import FusedFieldForward
+        from .poses import CameraPoseRefiner
+        loader = getattr(self.dataset, "train", None)
+        if not isinstance(self.dataset, LoaderDataset) or not isinstance(loader, TransformsLoader) \
+                or self.device.type != "cuda" or not loader.cameras.is_cuda:
+            raise ValueError("pose refinement needs a capture with per-camera poses on the GPU: a LoaderDataset over a "
+                             "TransformsLoader built with device=cuda (--dataset transforms)")
+        if self.dp:
+            raise ValueError("pose refinement is not built for data-parallel training (world > 1): the pose gradient would "
+                             "need a collective of its own")
+        if self.field.unbounded:
+            raise ValueError("pose refinement needs a bounded field: position gradients are not built for the contraction")
+        if not (lr > 0):
+            raise ValueError("pose refinement: the learning rate must be positive")
+        probe = torch.zeros((1, 3), dtype=torch.float32, device=self.device)
+        with torch.enable_grad():
+            on_path = FusedFieldForward.shapes_ok(self.field) and self.field._train_ok(probe, probe)
+        if not on_path:
+            raise ValueError("pose refinement needs the fused training forward (position gradients exist on that path "
+                             "only): a model of its shapes (64 or 160 neurons), CNC_FUSED_TRAIN / CNC_FUSED_FIELD on")
+        loader.with_camera_ids = True
+        self.pose_refiner = CameraPoseRefiner(len(loader), self.device)
+        self._pose_base = loader.cameras.clone()
+        self.opt_pose = torch.optim.Adam([self.pose_refiner.delta], lr=float(lr), eps=1e-15, weight_decay=0.0, fused=True)
+        self._pose_from, self._pose_on = int(start), True
+
+    def _pose_step(self, step: int, data) -> bool:
+        """Does this step refine poses?  Stops for good, with a warning, once the range guard has switched the fused
+        training forward off: no other path provides position gradients."""
+        if not self._pose_on:
+            return False
+        if not self.field.fused_train:
+            import warnings
+            warnings.warn("cnc_amd: pose refinement stops here: the fused training forward was switched off (fp16 range "
+                          "guard) and no other path provides position gradients; the poses keep their current values")
+            self._pose_on = False
+            return False
+        return step >= self._pose_from and "camera_ids" in data      # (a batch drawn before refinement was enabled has none)
+
+    def _pose_gradient(self, data, extra) -> bool:
+        """Behind the render backward: dL/dx of the samples -> `delta.grad`.  False: the ray loss reached no sample."""
+        g_x = extra["positions"].grad if extra is not None and extra.get("positions") is not None else None
+        if g_x is None:
+            self.pose_refiner.delta.grad = None
+            return False
+        from .render import _as_ray_list
+        rays, _ = _as_ray_list(data["rays"])
+        self.pose_refiner.accumulate(g_x, extra, rays, data["camera_ids"])
+        return True
+
+    def _pose_update(self) -> None:
+        """The poses' Adam step and the loader's table rewritten from the file's poses.  The look-ahead batch of the NEXT
+        step has been drawn already, from the table as the step before left it: a one-step lag, the same every run — the
+        rewrite waits for that draw, and the draw after it is ordered behind this step's kernels."""
+        self.opt_pose.step()
+        if self._next_ready is not None:
+            torch.cuda.current_stream(self.device).wait_event(self._next_ready)
+        self.pose_refiner.apply(self._pose_base, out=self.dataset.train.cameras)
+
+    def write_refined_transforms(self, path: Optional[str] = None) -> str:
+        """The capture's training file with the refined poses, to `<out_dir>/transforms_refined.json` (or `path`)."""
+        loader = self.dataset.train
+        path = path or os.path.join(self.cfg.out_dir, "transforms_refined.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self.pose_refiner.write_transforms(loader.transforms_path, path, loader.frame_ids)
+        return path
 
     def build_context(self):
         """The context models of this configuration (train:221-241).  Their vertex tables draw from the CPU
@@ -697,11 +784,18 @@ class Trainer:
         """Render forward and loss, backward and gradient assembly, verdict, update, stats."""
         c = self.cfg
         rays, pixels, bkgd = data["rays"], data["pixels"], data["color_bkgd"]
+        refine = self._pose_step(step, data)
         with _gradsink.activate(self.sink_render):
-            rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
-                self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
-                render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
-                with_samples=c.distortion_weight > 0)
+            if refine:
+                rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
+                    self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
+                    render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
+                    position_grad=True)
+            else:
+                rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
+                    self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
+                    render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
+                    with_samples=c.distortion_weight > 0)
         self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event()
         # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
         # fused one is asked before the poll below can switch it off)
@@ -733,9 +827,13 @@ class Trainer:
             bpp, mb, table_pieces = self._backward_single(step, ray_loss, ctx_future, tables_fused)
         else:
             bpp, mb, table_pieces = self._backward_dp(step, ray_loss, ctx_future, tables_fused, len(pixels), n_samples, range_guard)
+        if refine:
+            refine = self._pose_gradient(data, extra)
         if sg is not None:
-            self._verdict(mse, bpp, range_guard, tables_fused, distortion)
+            self._verdict(mse, bpp, range_guard, tables_fused, distortion, pose=refine)
         self._update(step, table_pieces, tables_fused)
+        if refine:
+            self._pose_update()
         if not want_stats:
             return {"n_rendering_samples": n_samples, "num_rays": len(pixels)}
         # the step's scalars in one device->host copy
@@ -856,7 +954,7 @@ class Trainer:
         A.bind(force=True)
         return bpp, mb, table_pieces
 
-    def _verdict(self, mse, bpp, range_guard, tables_fused, distortion=None) -> None:
+    def _verdict(self, mse, bpp, range_guard, tables_fused, distortion=None, pose=False) -> None:
         """The guarded step's verdict, on the device and before any update."""
         # Scanned: every gradient the two library optimizers will read (the tables' pieces are not: DESIGN.md §13) and the
         # loss scalars; data parallel: what every rank holds alike — the bucket's summed non-table runs with the entropy
@@ -867,12 +965,16 @@ class Trainer:
                     if p.grad is not None and id(p) not in self._table_ids]
             scan += [t.detach().reshape(-1) for t in (mse, bpp, distortion)
                      if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
+            if pose:                            # the pose gradient joins the scan, the poses' Adam takes the same word
+                scan.append(self.pose_refiner.delta.grad.reshape(-1))
             sg.scan(scan, range_guard=range_guard)
         else:
             sg.scan([A.flat[lo:hi] for lo, hi in A.runs_excluding(self._tables)] + [A.tail[1:2]])
         grp = self.opt.param_groups[1]
         sg.seal(grp["lr"], grp["eps"], grp["weight_decay"], self.table_adam.clip_counters() if tables_fused else ())
         self.opt.found_inf = self.opt2.found_inf = sg.found_inf
+        if pose:
+            self.opt_pose.found_inf = sg.found_inf
         sg.poll()
 
     def _update(self, step, table_pieces, tables_fused) -> None:
@@ -916,6 +1018,11 @@ class Trainer:
                     f"n_rendering_samples={s['n_rendering_samples']} | num_rays={s['num_rays']} | "
                     f"bits_per_param={s['bpp']:.3f} | embed_bits_MB={s['embed_bits_MB']:.3f}"
                     + (f" | skipped={self.step_guard.stats()['skipped']}" if self.step_guard is not None else ""))
+        if self.pose_refiner is not None and self.rank == 0:
+            path = self.write_refined_transforms()
+            if log:
+                tau, omega = self.pose_refiner.mean_magnitudes()
+                log(f"pose refinement: mean |tau|={tau:.3e} | mean |omega|={omega:.3e} rad | refined poses written to {path}")
         return last
 
     # ------------------------------------------------------------------------------ evaluation

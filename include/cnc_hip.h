@@ -752,6 +752,47 @@ int cnc_camera_rays(const float* cams, int32_t n_cams, int32_t model, int32_t op
                     float eps, int32_t iters, const uint8_t* images, const float* bkgd, float* origins, float* viewdirs,
                     float* pixels, void* stream);
 
+/* (ABI v33, added entries: no signature changed) Camera pose refinement (csrc/pose.hip).
+ *
+ * cnc_camera_pose_apply: cams_out [n_cams, CNC_CAMERA_ROW] = cams_base with R' = exp(omega) R0 and t' = t0 + tau, every
+ * other field copied; delta f32 [n_cams, 6] = (omega, tau) per camera.  cams_base and cams_out 16-byte aligned (rows
+ * travel as six 16-byte accesses) and must not overlap.
+ * Every element of cams_out is written exactly once, by plain vector stores.  Per camera, in float32, nothing fused, in
+ * this order (w = omega):
+ *     t2 = (w0 w0 + w1 w1) + w2 w2
+ *     t2 == 0:      R' = R0, copied bit for bit
+ *     t2 < 2^-24:   A = 1 - t2 / 6 ;  B = 0.5 - t2 / 24
+ *     otherwise, in DOUBLE from th = sqrt((double)t2), each rounded to float once:
+ *                   A = sin(th) / th ;  B = 0.5 (sh sh) with sh = sin(0.5 th) / (0.5 th)       [= (1 - cos th) / th^2]
+ *     E_ij = ((i == j ? 1 : 0) + A k_ij) + B s_ij,   k = [w]x (k_01 = -w2, k_02 = w1, k_12 = -w0, antisymmetric, 0 on the
+ *            diagonal),   s_ij = w_i w_j off the diagonal, w_i w_i - t2 on it                   [exp = I + A [w]x + B [w]x^2]
+ *     R'_ij = (E_i0 R0_0j + E_i1 R0_1j) + E_i2 R0_2j
+ *     t'_i = tau_i == 0 ? t0_i : t0_i + tau_i
+ * so that delta = 0 gives cams_out bit-equal to cams_base, negative zeros included.                                  */
+int cnc_camera_pose_apply(const float* cams_base, const float* delta, int32_t n_cams, float* cams_out, void* stream);
+
+/* cnc_ray_pose_grad: the gradient of the loss with respect to every camera's pose, G f32 [n_cams, 6], from the position
+ * gradients g_x [n_samples, 3] of a render pass's samples.  t_starts, t_ends [n_samples]; chunk_starts, chunk_cnts i64
+ * [n_rays]: the per-ray sample table of cnc_volrend_forward (a pair is cut to [0, n_samples): no load leaves the sample
+ * arrays); dirs [n_rays, 3] the rays' unit directions; cam_ids i64 [n_rays], clamped into [0, n_cams) as
+ * cnc_camera_rays clamps them.  A sample lies at x_s = o + m_s d with m_s = (t0 + t1) 0.5.
+ * Stage 1, per ray, over its samples in sample order from +0:   g_o += g_x[s] ;  g_d += m_s g_x[s]   (product, then add)
+ *     q_r = (d x g_d, g_o),   (d x g)_0 = d1 g2 - d2 g1,  _1 = d2 g0 - d0 g2,  _2 = d0 g1 - d1 g0
+ * Stage 2: rays are cut into chunks of 256 consecutive rays.  Per (chunk, camera c) the q_r of the chunk's rays with
+ * cam_ids[r] == c are added in ray order from +0; G[c] = the chunks' sums added in chunk order from +0.  The order is a
+ * function of the ray indices alone — no atomics, nothing that depends on launch geometry or scheduling: equal inputs
+ * give equal bits, and a camera without rays gets exact +0.  This is the only form (the reproducible mode needs no
+ * second route).
+ * G[c][0..2] is the gradient with respect to a LEFT perturbation exp(phi) R_c at phi = 0 (R_c the rotation the rays
+ * were drawn with), G[c][3..5] the gradient with respect to t_c: the gradient of (omega, tau) exactly at omega = 0 and up
+ * to the left Jacobian I + O(|omega|) elsewhere.
+ * workspace: cnc_ray_pose_grad_workspace(n_rays, n_cams) bytes, 4-byte aligned, owned by the call until it has run.
+ * Every element of G is written exactly once by a plain store.                                                        */
+uint64_t cnc_ray_pose_grad_workspace(uint32_t n_rays, int32_t n_cams);
+int cnc_ray_pose_grad(const float* g_x, const float* t_starts, const float* t_ends, int64_t n_samples,
+                      const int64_t* chunk_starts, const int64_t* chunk_cnts, const float* dirs, const int64_t* cam_ids,
+                      uint32_t n_rays, int32_t n_cams, void* workspace, uint64_t workspace_bytes, float* G, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Context-model heads and the Bernoulli rate  —  replace the ATen chains of examples/utils_bpp_acc.py
  * (context MLPs :378-393 applied at :561-566 / :689-692, hash fusion :567-572 / :693-701,
@@ -1182,6 +1223,28 @@ int cnc_field_pack_all(const cnc_field_pack_t* desc, void* stream);
  * CNC_ERR_UNSUPPORTED for shapes outside the table above (the caller then runs the unfused chain).            */
 int cnc_field_fused_forward(const cnc_fused_field_t* field, const float* positions, const float* dirs, uint32_t N,
                             float* density, float* rgb, void* stream);
+
+/* (ABI v33, added entry: no signature changed) The gradient of the loss with respect to the sample positions of a
+ * gradient pass (csrc/field_position_grad.hip): g_x f32 [N, 3], world units, from
+ *   field      the descriptor of the saving forward: aabb, bits, units, n_levels, n_features (2, 4 or 8), freqs, n_freqs
+ *              are read; CNC_FIELD_CONTRACT in flags returns CNC_ERR_UNSUPPORTED (bounded fields only)
+ *   positions  [N, 3] world positions, selector u8 [>= N] (cnc_field_save_t.selector)
+ *   dX         [>= N, ld_x]: the gradient of the first layer's encoder columns as cnc_field_backward_chain leaves it
+ *              (unit u's F columns at u F); 16-byte aligned, ld_x a multiple of 4
+ *   dS         nullable, [>= N, ld_s]: the gradient of the 3 + 6 n_freqs columns behind them, [x | sin, cos per frequency]
+ * Nothing is kept by the forward for this call: the unit-cube position and each unit's corner set-up are recomputed by
+ * the forward's own device functions (same cell, same fraction, bit for bit), the signs gathered from the bit planes.
+ * Per unit of resolution R, with t the fraction, V the corners off the border ring, wn their weights' sum (1e-9 if 0):
+ *     d y_c / d x_a = (R - 2) sum_V d_a w_i (e_ic - y_c) / wn            (the normaliser differentiated too; 0 for empty V)
+ *     g_unit[a] = sum_units sum_c dX[u F + c] d y_c / d x_a + dS[a] + sum_k f_k (cos(x_a f_k) dS_sin - sin(x_a f_k) dS_cos)
+ *     g_x[a] = g_unit[a] / (aabb[3 + a] - aabb[a])
+ * the arguments x_a f_k formed in float32 as the forward forms them.  A row whose selector is 0, or whose position is
+ * not strictly inside the box, gets +0.  The view direction's path is not part of it.  Four lanes share a sample and add
+ * their partial sums in a fixed tree; no atomics; every element of g_x is written exactly once by a plain store: equal
+ * inputs give equal bits.                                                                                          */
+int cnc_field_position_grad(const cnc_fused_field_t* field, const float* positions, const uint8_t* selector,
+                            const float* dX, uint32_t ld_x, const float* dS, uint32_t ld_s, uint32_t N, float* g_x,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (extension, ABI v26) The gradient chain of the field's two MLPs as one kernel: autograd through mlp_head and mlp_base of
