@@ -6,8 +6,10 @@ Host-side mirror of examples/utils_bpp_acc.py of the reference:
     decode :867-999), `Bernoulli_entropy` :1002-1013.
 Same class / method names, argument meaning, return values and file naming, so the reference's
 drivers can call it unchanged.  The three passes share their per-level arithmetic here (the
-reference repeats it three times); every kernel call goes through the HIP mirrors
-(`_gridencoder`, `pack_and_align`), the entropy coder through libcnc_codec.so.
+reference repeats it three times), and encode and decode share their stream records (`_Stream`: which
+file carries which rows of which table under which probabilities — the bitstream format, said once);
+every kernel call goes through the HIP mirrors (`_gridencoder`, `pack_and_align`), the entropy coders
+(cnc_amd/coders.py, re-exported here) through libcnc_codec.so and the device coder's kernels.
 
 Differences that do not change results:
   * device is taken from the constructor (`device=`) instead of hard-coded 'cuda' module
@@ -21,6 +23,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from typing import Optional
 
 import contextlib
@@ -44,7 +47,7 @@ from .backends import pack_and_align
 from .gridencoder import STE_binary, STE_multistep
 from .mlp import Linear
 
-from ._codec import lib as _codec_lib  # noqa: E402  (libcnc_codec.so, include/cnc_codec.h)
+from .coders import DEVICE_CODER_SYMBOLS_PER_LANE, CoderPool, DeviceCoder, decoder, encoder, make_coder  # noqa: F401  (re-exported)
 
 
 def get_grid_index(hashmap_size, resolution, pos_grid):
@@ -238,228 +241,6 @@ class _vote_tables3(Function):
         return None, grad_embeddings
 
 
-def _encode_host(x, p, file_name):
-    """x, p: contiguous float32 HOST tensors.  Writes the .b file, returns its size in bits."""
-    n = x.numel()
-    L = _codec_lib()
-    cap = int(L.cnc_rc_bound(n))
-    buf = np.empty(cap, dtype=np.uint8)
-    nbytes = L.cnc_rc_encode_pm1(p.data_ptr(), x.data_ptr(), n, buf.ctypes.data, cap)
-    if nbytes < 0:
-        raise RuntimeError("range coder: output buffer too small")
-    with open(file_name, "wb") as fout:
-        fout.write(buf[:nbytes].tobytes())
-    return int(nbytes) * 8
-
-
-def _decode_host(p, file_name):
-    with open(file_name, "rb") as fin:
-        stream = np.frombuffer(fin.read(), dtype=np.uint8)
-    out = torch.empty(p.numel(), dtype=torch.float32)
-    _codec_lib().cnc_rc_decode_pm1(p.data_ptr(), p.numel(), stream.ctypes.data, stream.shape[0], out.data_ptr())
-    return out
-
-
-def encoder(x, p, file_name):
-    """Code x in {-1,+1} with P(x=+1)=p into `file_name` (.b); returns the size in bits
-    (utils_bpp_acc.py:77-93)."""
-    assert file_name[-2:] == ".b"
-    x = x.detach().to(torch.float32).cpu().contiguous().view(-1)
-    p = p.detach().to(torch.float32).cpu().contiguous().view(-1)
-    return _encode_host(x, p, file_name)
-
-
-def decoder(p, file_name):
-    """Inverse of `encoder`: returns float32 ±1 on p's device (utils_bpp_acc.py:95-110)."""
-    assert file_name[-2:] == ".b"
-    dvc = p.device
-    return _decode_host(p.detach().to(torch.float32).cpu().contiguous().view(-1), file_name).to(dvc)
-
-
-class CoderPool:
-    """The reference codes its 33 streams one after the other, each behind two blocking `.cpu()` copies
-    (utils_bpp_acc.py:77-110, call sites :722-804).  The streams are independent files, so here they are
-    coded CONCURRENTLY: `encode` / `decode` start a device->pinned-host copy on a side stream and hand the
-    rest (wait for the copy, run the C coder — ctypes drops the GIL —, touch the file) to a worker thread;
-    the GPU goes on computing the next stream's probabilities meanwhile.  Same bytes as `encoder` /
-    `decoder` (tests/test_gpu_context.py).  At most `max_in_flight` streams hold pinned buffers at once."""
-
-    def __init__(self, workers=None, max_in_flight=8):
-        import concurrent.futures as cf
-        import threading
-        self.pool = cf.ThreadPoolExecutor(max_workers=workers or min(8, os.cpu_count() or 1))
-        self.slots = threading.Semaphore(max_in_flight)
-        self.copy_stream = {}
-
-    def _to_host(self, t):
-        """float32 flat copy of `t` in pinned memory + the event that says it has arrived."""
-        t = t.detach().to(torch.float32).contiguous().view(-1)
-        if not t.is_cuda:
-            return t, None
-        side = self.copy_stream.setdefault(t.device, torch.cuda.Stream(device=t.device))
-        side.wait_stream(torch.cuda.current_stream(t.device))
-        host = torch.empty(t.numel(), dtype=torch.float32, pin_memory=True)
-        with torch.cuda.stream(side):
-            host.copy_(t, non_blocking=True)
-            t.record_stream(side)
-            ev = torch.cuda.Event()
-            ev.record(side)
-        return host, ev
-
-    def encode(self, x, p, file_name):
-        """Future of the stream's size in bits."""
-        assert file_name[-2:] == ".b"
-        self.slots.acquire()
-        (xh, ex), (ph, ep) = self._to_host(x), self._to_host(p)
-
-        def job():
-            try:
-                for ev in (ex, ep):
-                    if ev is not None:
-                        ev.synchronize()
-                return _encode_host(xh, ph, file_name)
-            finally:
-                self.slots.release()
-        return self.pool.submit(job)
-
-    def decode(self, p, file_name):
-        """Future of the decoded float32 +-1 HOST tensor (pinned when p lives on a GPU)."""
-        assert file_name[-2:] == ".b"
-        self.slots.acquire()
-        ph, ep = self._to_host(p)
-
-        def job():
-            try:
-                if ep is not None:
-                    ep.synchronize()
-                return _decode_host(ph, file_name)
-            finally:
-                self.slots.release()
-        return self.pool.submit(job)
-
-    def shutdown(self):
-        self.pool.shutdown(wait=True)
-
-
-# Symbols per rANS lane of the device coder when the caller names none: the smallest of 2^12, 2^14, 2^16 whose
-# full-size container stays within 1 % of the host coder's (profiles/device_coder.md).
-DEVICE_CODER_SYMBOLS_PER_LANE = 16384
-
-
-def _flat_p(p):
-    """(float32 device tensor, p_stride, n) of a probability tensor: an expanded scalar (the levels coded with one
-    Pg) stays one element, read with stride 0."""
-    n = p.numel()
-    if p.dim() == 1 and n > 1 and p.stride(0) == 0:
-        return p.detach()[:1].to(torch.float32).contiguous(), 0, n
-    return p.detach().to(torch.float32).contiguous().view(-1), 1, n
-
-
-class DeviceCoder:
-    """The call shape of `CoderPool` on the device entropy coder (cnc_amd/csrc/rans_coder.hip, the "rans1" format of
-    include/cnc_codec.h): symbols and probabilities stay where they are, one batched call codes every stream handed
-    over, and only compressed bytes cross PCIe.  `encode` collects; `finish` launches, copies sizes and bytes to the
-    host, writes the .b files and returns the bits.  `decode_group` checks the files on the host (`cnc_rans_check`),
-    uploads their bytes in one copy and returns the decoded DEVICE tensors without waiting; the streams' status words
-    are read by `check()`, once, when the caller is done."""
-
-    def __init__(self, symbols_per_lane=None):
-        self.S = int(symbols_per_lane or DEVICE_CODER_SYMBOLS_PER_LANE)
-        if self.S < 1:
-            raise ValueError("symbols_per_lane must be >= 1")
-        self._queued = []            # (x, p, p_stride, n, file name)
-        self._status = []            # (status tensor, file names) of the decode groups so far
-
-    # ---- encode
-    def encode(self, x, p, file_name):
-        assert file_name[-2:] == ".b"
-        if not x.is_cuda:
-            raise RuntimeError("x must be a CUDA tensor")
-        x = x.detach().to(torch.float32).contiguous().view(-1)
-        p, stride, n = _flat_p(p)
-        assert n == x.numel() or (stride == 1 and n == 1 == x.numel())
-        self._queued.append((x, p, stride, x.numel(), file_name))
-
-    def finish(self):
-        """Codes everything queued; returns the total size in bits."""
-        from . import _lib
-        if not self._queued:
-            return 0
-        L, Lc = _lib.lib(), _codec_lib()
-        dev = self._queued[0][0].device
-        caps = [int(Lc.cnc_rans_bound(n, self.S)) for _, _, _, n, _ in self._queued]
-        at = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
-        out = torch.empty(int(at[-1]), dtype=torch.uint8, device=dev)
-        table = (_lib.RansStream * len(caps))()
-        for k, (x, p, stride, n, _) in enumerate(self._queued):
-            table[k] = _lib.RansStream(p.data_ptr(), stride, x.data_ptr(), n, self.S, out.data_ptr() + int(at[k]), caps[k])
-        need = int(L.cnc_rans_scratch_bytes(table, len(caps)))
-        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        sizes = torch.empty(len(caps), dtype=torch.int64, device=dev)
-        _lib.check(L.cnc_rans_encode_pm1(table, len(caps), scratch.data_ptr(), need, sizes.data_ptr(), _lib.stream(dev)),
-                   "rans_encode_pm1")
-        sizes_h = sizes.cpu().tolist()
-        if min(sizes_h) < 0:
-            raise RuntimeError("device coder: output buffer too small")
-        # the streams packed on the device, then one copy of what was written (a few hundred KB of the worst-case buffer)
-        packed = torch.cat([out[int(at[k]):int(at[k]) + s] for k, s in enumerate(sizes_h)]).cpu().numpy()
-        pos = 0
-        for (_, _, _, _, file_name), s in zip(self._queued, sizes_h):
-            with open(file_name, "wb") as fout:
-                fout.write(packed[pos:pos + s].tobytes())
-            pos += s
-        self._queued = []
-        return 8 * sum(sizes_h)
-
-    # ---- decode
-    def decode_group(self, items):
-        """items: [(p, file name)], streams that do not depend on each other.  Returns their symbols as float32 +-1
-        DEVICE tensors, in order.  A file that is not a well-formed rans1 stream for p's length raises here, on the host,
-        before anything is uploaded or launched."""
-        Lc = _codec_lib()
-        blobs, ps = [], []
-        for p, file_name in items:
-            assert file_name[-2:] == ".b"
-            if not p.is_cuda:
-                raise RuntimeError("p must be a CUDA tensor")
-            with open(file_name, "rb") as fin:
-                blob = np.frombuffer(fin.read(), dtype=np.uint8)
-            p, stride, n = _flat_p(p)
-            if Lc.cnc_rans_check(blob.ctypes.data, blob.shape[0], n) < 0:
-                raise RuntimeError(f"{file_name}: not a valid rans1 stream of {n} symbols")
-            blobs.append(blob)
-            ps.append((p, stride, n))
-        return self._launch_decode(ps, blobs, [f for _, f in items])
-
-    def _launch_decode(self, ps, blobs, names):
-        from . import _lib
-        L = _lib.lib()
-        dev = ps[0][0].device
-        at = np.concatenate([[0], np.cumsum([b.shape[0] for b in blobs])]).astype(np.int64)
-        host = torch.from_numpy(np.concatenate(blobs))
-        data = (host.pin_memory() if dev.type == "cuda" else host).to(dev, non_blocking=True)
-        outs = [torch.empty(n, dtype=torch.float32, device=dev) for _, _, n in ps]
-        status = torch.empty(len(ps), dtype=torch.int32, device=dev)
-        table = (_lib.RansStream * len(ps))()
-        for k, (p, stride, n) in enumerate(ps):
-            table[k] = _lib.RansStream(p.data_ptr(), stride, outs[k].data_ptr(), n, 0, data.data_ptr() + int(at[k]),
-                                       int(blobs[k].shape[0]))
-        _lib.check(L.cnc_rans_decode_pm1(table, len(ps), status.data_ptr(), _lib.stream(dev)), "rans_decode_pm1")
-        self._status.append((status, names))
-        return outs
-
-    def check(self):
-        """One host wait for every group decoded so far: raises if a lane of any stream did not end where it began,
-        naming every such stream of every group.  The groups are forgotten either way: a verdict is given once."""
-        groups, self._status = self._status, []
-        bad = [n for status, names in groups for n, s in zip(names, status.cpu().tolist()) if s != 0]
-        if bad:
-            raise RuntimeError(f"device coder: damaged stream(s) {bad}")
-
-    def shutdown(self):
-        self._queued = []
-
-
 class align_and_pack(Function):
     """Ragged [T, F] rows grouped by `unique_cnt` -> padded [N, max(cnt), F] (utils_bpp_acc.py:113-139)."""
 
@@ -561,6 +342,16 @@ def _save_level_table(cache_dir, R, rows, D, pos_sorted, unique_value, unique_cn
     torch.save({"key": (R, rows, D), "pos_sorted": pos_sorted.cpu(), "unique_value": unique_value.cpu(),
                 "unique_cnt": unique_cnt.cpu()}, tmp)
     os.replace(tmp, path)      # atomic: concurrent ranks never see a half-written table
+
+
+# One .b file of the tables' bitstream, as the encoder and the decoder both see it (`_streams_3D`, `_stream_2D`):
+#   suffix  the file is {prefix}_{suffix}.b: "3D5", "3D7_2" (chunk 2 of level 7), "xy0"
+#   dst     where its symbols live in their table: a slice of rows or an int64 row tensor — the symbols are
+#           table[dst].reshape(-1), and a decode writes them back to table[dst]
+#   p       flat P(+1) per symbol: the level's frequency as an expanded scalar, or the clamped `mean`
+#   mean    the context models' prediction [rows, F] (what the encoder's estimate is taken under); None for a level coded
+#           with its frequency
+_Stream = namedtuple("_Stream", "suffix dst p mean")
 
 
 def _zero_order_bits(pos_num, neg_num, Pg):
@@ -1415,6 +1206,32 @@ class CNC_context_models(nn.Module):
         est_MB = ttl_bit_sum.detach() * (1.0 / 8388608.0)        # / 8 / 1024 / 1024: a power of two, one op, same value
         return bits_per_param, (est_MB.item() if sync_MB else est_MB)
 
+    # ------------------------------------------------------------------------------- the bitstream's streams
+    def _stream_Pg(self, suffix, off_host, n, Pg_n):
+        """A level that is not context-coded: all its rows, every symbol under the level's frequency."""
+        a, b = off_host[n], off_host[n + 1]
+        return _Stream(suffix, slice(a, b), Pg_n.reshape(1).expand((b - a) * self.n_features), None)
+
+    def _streams_3D(self, Encoding_xyz, n, Pg_n, binary_vxl, outspace_params):
+        """The streams of 3-D level n, in file order: one for a level that is not coded, one per chunk of `_chunks_3D`
+        for a coded one.  A generator: the caller hands a chunk to the coder before the next chunk's context pass runs.
+        `outspace_params`: the table the context reads (None = the encoder's own; a decode passes what it has decoded)."""
+        if not self._coded_3D(n):
+            yield self._stream_Pg(f"3D{n}", self._off3_host, n, Pg_n)
+            return
+        for sn, v0, v1 in self._chunks_3D(n):
+            mean, mask_exist, rows = self._level_chunk_3D(Encoding_xyz, n, v0, v1, Pg_n, binary_vxl, outspace_params)
+            yield _Stream(f"3D{n}_{sn}", rows[mask_exist], torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1), mean)
+
+    def _stream_2D(self, Ec, axis, n, Pg_n, binary_2D, pn_frac, outspace_params):
+        """The stream of level n of the plane `axis` ("xy", "xz", "yz")."""
+        if not self._coded_2D(n):
+            return self._stream_Pg(f"{axis}{n}", self._off2_host, n, Pg_n)
+        points_n, order, rows, unique_cnt = self._sorted_slots_2D(binary_2D, n)
+        mean = self._mean_2D(Ec, n, points_n, Pg_n, binary_2D, pn_frac, order, unique_cnt,
+                             outspace_params=outspace_params, detach_pn=True)
+        return _Stream(f"{axis}{n}", rows, torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1), mean)
+
     # ------------------------------------------------------------------------------- encode
     def encode_binary_vxl_mixPg_3D2D(self, Encoding_xyz, Encoding_xy, Encoding_xz, Encoding_yz,
                                      binary_vxl=None, filename_prefix="b", coder="host", symbols_per_lane=None):
@@ -1422,17 +1239,20 @@ class CNC_context_models(nn.Module):
         Returns (Pgs_dict, estimated MB, coded MB) (utils_bpp_acc.py:709-865).  coder="host": the range coder on worker
         threads (`CoderPool`); coder="device" (an extension): the same streams through `DeviceCoder`, one batched call
         at the end, in the "rans1" format — the two kinds of file are not interchangeable."""
-        if coder not in ("host", "device"):
-            raise ValueError(f"coder must be 'host' or 'device', not {coder!r}")
+        coders = make_coder(coder, symbols_per_lane)
         Pgs_dict = {}
         params_q_xy = self.get_STE_params(Encoding_xy)
         params_q_xz = self.get_STE_params(Encoding_xz)
         params_q_yz = self.get_STE_params(Encoding_yz)
         params_q_xyz = self.get_STE_params(Encoding_xyz)
-        F = self.n_features
         ttl_bit_sum = 0
-        coders = DeviceCoder(symbols_per_lane) if coder == "device" else CoderPool()
-        streams = []            # futures: every stream is an independent file, coded while the next is prepared
+
+        def code(table, s, bits_n):
+            """Hands the stream's symbols to the coder (every stream is an independent file, coded while the next is
+            prepared); returns its estimated bits: `bits_n` for a level coded with its frequency."""
+            values_q = table[s.dst]
+            coders.encode(values_q.reshape(-1), s.p, f"{filename_prefix}_{s.suffix}.b")
+            return bits_n if s.mean is None else torch.sum(self.entropy_model(values_q, s.mean))
 
         idx_coords2 = self.get_idx_coords2(binary_vxl) if self.use_dimension_wise else None
         finest_3D = params_q_xyz[self.offsets_list[-2]:self.offsets_list[-1]]
@@ -1443,36 +1263,14 @@ class CNC_context_models(nn.Module):
             for n in range(self.n_levels_2D):
                 Pg_n, bits_n, _ = self.get_BiRF_wentropy_leveln(p_q, n, self.offsets_list_2D)
                 Pgs_dict[axis + str(n)] = Pg_n
-                fname = f"{filename_prefix}_{axis}{n}.b"
-                if not self._coded_2D(n):
-                    xs = p_q[self.offsets_list_2D[n]:self.offsets_list_2D[n + 1]].reshape(-1)
-                    ps = Pg_n.reshape(1).expand(xs.numel())
-                else:
-                    points_n, order, rows, unique_cnt = self._sorted_slots_2D(binary_2D, n)
-                    mean = self._mean_2D(Ec, n, points_n, Pg_n, binary_2D, pn_frac, order, unique_cnt, detach_pn=True)
-                    values_q = p_q[rows, :]
-                    bits_n = torch.sum(self.entropy_model(values_q, mean))
-                    xs = values_q.reshape(-1)
-                    ps = torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1)
-                streams.append(coders.encode(xs, ps, fname))
-                ttl_bit_sum = ttl_bit_sum + bits_n
+                ttl_bit_sum = ttl_bit_sum + code(p_q, self._stream_2D(Ec, axis, n, Pg_n, binary_2D, pn_frac, None), bits_n)
 
         for n in range(self.n_levels):
             Pg_n, bits_n, _ = self.get_BiRF_wentropy_leveln(params_q_xyz, n)
             Pgs_dict["3D" + str(n)] = Pg_n
-            if not self._coded_3D(n):
-                xs = params_q_xyz[self.offsets_list[n]:self.offsets_list[n + 1]].reshape(-1)
-                ps = Pg_n.reshape(1).expand(xs.numel())
-                streams.append(coders.encode(xs, ps, f"{filename_prefix}_3D{n}.b"))
-                ttl_bit_sum = ttl_bit_sum + bits_n
-                continue
-            for sn, v0, v1 in self._chunks_3D(n):
-                mean, mask_exist, rows = self._level_chunk_3D(Encoding_xyz, n, v0, v1, Pg_n, binary_vxl, None)
-                values_q = params_q_xyz[rows][mask_exist]
-                ttl_bit_sum = ttl_bit_sum + torch.sum(self.entropy_model(values_q, mean))
-                ps = torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1)
-                streams.append(coders.encode(values_q.reshape(-1), ps, f"{filename_prefix}_3D{n}_{sn}.b"))
-        encode_bits = coders.finish() if coder == "device" else sum(f.result() for f in streams)
+            for s in self._streams_3D(Encoding_xyz, n, Pg_n, binary_vxl, None):
+                ttl_bit_sum = ttl_bit_sum + code(params_q_xyz, s, bits_n)
+        encode_bits = coders.finish()
         coders.shutdown()
         return Pgs_dict, ttl_bit_sum.item() / 8.0 / 1024 / 1024, encode_bits / 8.0 / 1024 / 1024
 
@@ -1484,89 +1282,31 @@ class CNC_context_models(nn.Module):
         """Sequential inverse of encode: 3-D levels coarse to fine (each level's context reads the
         already decoded lower levels), then the three planes (which need the decoded finest 3-D
         level).  Rows never coded keep the caller's initial value (utils_bpp_acc.py:867-999).  `coder` names what
-        wrote the files: "host" (range coder) or "device" (rans1, decoded on the device)."""
-        if coder not in ("host", "device"):
-            raise ValueError(f"coder must be 'host' or 'device', not {coder!r}")
-        if coder == "device":
-            return self._decode_on_device(Encoding_xyz, Encoding_xy, Encoding_xz, Encoding_yz, params_q_xyz_rec,
-                                          params_q_xy_rec, params_q_xz_rec, params_q_yz_rec, binary_vxl, Pgs_dict,
-                                          filename_prefix)
-        F = self.n_features
-        coders = CoderPool()
-        dev = params_q_xyz_rec.device
-        with torch.no_grad():
-            # 3-D: level n needs levels < n decoded, but the chunks of ONE level only read lower levels:
-            # their probabilities are computed first, then the chunk streams are decoded concurrently
-            for n in range(self.n_levels):
-                Pg_n = Pgs_dict["3D" + str(n)]
-                if not self._coded_3D(n):
-                    rows = int(self.offsets_list[n + 1] - self.offsets_list[n])
-                    sout = coders.decode(Pg_n.reshape(1).expand(rows * F), f"{filename_prefix}_3D{n}.b").result()
-                    params_q_xyz_rec[self.offsets_list[n]:self.offsets_list[n + 1]] = sout.to(dev).view(rows, F)
-                    continue
-                pending = []
-                for sn, v0, v1 in self._chunks_3D(n):
-                    mean, mask_exist, rows = self._level_chunk_3D(Encoding_xyz, n, v0, v1, Pg_n,
-                                                                  binary_vxl, params_q_xyz_rec)
-                    ps = torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1)
-                    pending.append((coders.decode(ps, f"{filename_prefix}_3D{n}_{sn}.b"), rows[mask_exist], mean.shape))
-                for fut, dst, shape in pending:
-                    params_q_xyz_rec[dst] = fut.result().to(dev).view(*shape)
+        wrote the files: "host" (range coder) or "device" (rans1, decoded on the device).
 
-            # planes: level n of a plane needs its own levels < n (and the finest 3-D level); the three planes
-            # are independent of each other, so each level is decoded for xy / xz / yz concurrently
-            idx_coords2 = self.get_idx_coords2(binary_vxl) if self.use_dimension_wise else None
-            finest_3D = params_q_xyz_rec[self.offsets_list[-2]:self.offsets_list[-1]]
-            planes = []
-            for Ec, rec, axis in zip((Encoding_xy, Encoding_xz, Encoding_yz),
-                                     (params_q_xy_rec, params_q_xz_rec, params_q_yz_rec), ("xy", "xz", "yz")):
-                binary_2D = self._project(binary_vxl, axis)
-                pn_frac = self.get_pn_embed_frac(finest_3D, idx_coords2, axis=axis) if self.use_dimension_wise else None
-                planes.append((Ec, rec, axis, binary_2D, pn_frac))
-            for n in range(self.n_levels_2D):
-                pending = []
-                for Ec, rec, axis, binary_2D, pn_frac in planes:
-                    Pg_n = Pgs_dict[axis + str(n)]
-                    fname = f"{filename_prefix}_{axis}{n}.b"
-                    if not self._coded_2D(n):
-                        rows = int(self.offsets_list_2D[n + 1] - self.offsets_list_2D[n])
-                        dst = slice(int(self.offsets_list_2D[n]), int(self.offsets_list_2D[n + 1]))
-                        pending.append((coders.decode(Pg_n.reshape(1).expand(rows * F), fname), rec, dst))
-                        continue
-                    points_n, order, rows, unique_cnt = self._sorted_slots_2D(binary_2D, n)
-                    mean = self._mean_2D(Ec, n, points_n, Pg_n, binary_2D, pn_frac, order, unique_cnt,
-                                         outspace_params=rec, detach_pn=True)
-                    ps = torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1)
-                    pending.append((coders.decode(ps, fname), rec, rows))
-                for fut, rec, dst in pending:
-                    rec[dst] = fut.result().to(dev).view(-1, F)
-        coders.shutdown()
-        return params_q_xyz_rec, params_q_xy_rec, params_q_xz_rec, params_q_yz_rec
-
-    def _decode_on_device(self, Encoding_xyz, Encoding_xy, Encoding_xz, Encoding_yz, params_q_xyz_rec, params_q_xy_rec,
-                          params_q_xz_rec, params_q_yz_rec, binary_vxl, Pgs_dict, filename_prefix):
-        """`decode_binary_vxl_mixPg_3D2D` for files of the device coder: the same order of levels, every group of
-        streams that do not depend on each other (the chunks of a 3-D level; level n of the three planes) as one
-        `DeviceCoder.decode_group` call.  The decoded symbols never leave the device and nothing waits on the host
-        between the levels; the streams' status words are read once, at the end."""
+        Every group of streams that do not depend on each other (the chunks of a 3-D level; level n of the three planes)
+        is one `decode_group` call: the host coder decodes them concurrently, a stream on its way while the next one's
+        probabilities are computed; the device coder decodes them in one launch, the symbols never leave the device and
+        nothing waits on the host between the levels.  `check()` reads the device coder's status words once, at the end."""
+        coders = make_coder(coder)
         F = self.n_features
-        coders = DeviceCoder()
+
+        def decode(pairs):
+            """pairs: (table, stream) of one group, taken one by one."""
+            seen = []
+
+            def items():
+                for table, s in pairs:
+                    seen.append((table, s))
+                    yield s.p, f"{filename_prefix}_{s.suffix}.b"
+            outs = coders.decode_group(items())
+            for (table, s), sout in zip(seen, outs):
+                table[s.dst] = sout.view(-1, F)
+
         with torch.no_grad():
             for n in range(self.n_levels):
-                Pg_n = Pgs_dict["3D" + str(n)]
-                if not self._coded_3D(n):
-                    rows = int(self.offsets_list[n + 1] - self.offsets_list[n])
-                    sout, = coders.decode_group([(Pg_n.reshape(1).expand(rows * F), f"{filename_prefix}_3D{n}.b")])
-                    params_q_xyz_rec[self.offsets_list[n]:self.offsets_list[n + 1]] = sout.view(rows, F)
-                    continue
-                group, where = [], []
-                for sn, v0, v1 in self._chunks_3D(n):
-                    mean, mask_exist, rows = self._level_chunk_3D(Encoding_xyz, n, v0, v1, Pg_n,
-                                                                  binary_vxl, params_q_xyz_rec)
-                    group.append((torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1), f"{filename_prefix}_3D{n}_{sn}.b"))
-                    where.append((rows[mask_exist], mean.shape))
-                for sout, (dst, shape) in zip(coders.decode_group(group), where):
-                    params_q_xyz_rec[dst] = sout.view(*shape)
+                decode((params_q_xyz_rec, s) for s in self._streams_3D(Encoding_xyz, n, Pgs_dict["3D" + str(n)], binary_vxl,
+                                                                       params_q_xyz_rec))
 
             idx_coords2 = self.get_idx_coords2(binary_vxl) if self.use_dimension_wise else None
             finest_3D = params_q_xyz_rec[self.offsets_list[-2]:self.offsets_list[-1]]
@@ -1577,22 +1317,9 @@ class CNC_context_models(nn.Module):
                 pn_frac = self.get_pn_embed_frac(finest_3D, idx_coords2, axis=axis) if self.use_dimension_wise else None
                 planes.append((Ec, rec, axis, binary_2D, pn_frac))
             for n in range(self.n_levels_2D):
-                group, where = [], []
-                for Ec, rec, axis, binary_2D, pn_frac in planes:
-                    Pg_n = Pgs_dict[axis + str(n)]
-                    fname = f"{filename_prefix}_{axis}{n}.b"
-                    if not self._coded_2D(n):
-                        rows = int(self.offsets_list_2D[n + 1] - self.offsets_list_2D[n])
-                        group.append((Pg_n.reshape(1).expand(rows * F), fname))
-                        where.append((rec, slice(int(self.offsets_list_2D[n]), int(self.offsets_list_2D[n + 1]))))
-                        continue
-                    points_n, order, rows, unique_cnt = self._sorted_slots_2D(binary_2D, n)
-                    mean = self._mean_2D(Ec, n, points_n, Pg_n, binary_2D, pn_frac, order, unique_cnt,
-                                         outspace_params=rec, detach_pn=True)
-                    group.append((torch.clamp(mean, min=1e-6, max=1 - 1e-6).reshape(-1), fname))
-                    where.append((rec, rows))
-                for sout, (rec, dst) in zip(coders.decode_group(group), where):
-                    rec[dst] = sout.view(-1, F)
+                decode((rec, self._stream_2D(Ec, axis, n, Pgs_dict[axis + str(n)], binary_2D, pn_frac, rec))
+                       for Ec, rec, axis, binary_2D, pn_frac in planes)
             coders.check()
         coders.shutdown()
         return params_q_xyz_rec, params_q_xy_rec, params_q_xz_rec, params_q_yz_rec
+

@@ -26,7 +26,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .occupancy_codec import _coder, c1_of_counts, p_of_c1
+from .occupancy_codec import c1_of_counts, p_of_c1
 
 MODEL = "tree1"
 MAX_DEPTH = 8
@@ -176,9 +176,9 @@ def encode_mlp(state: Dict[str, torch.Tensor], bits: int = 13, coder: str = "hos
     measurement can visit every (depth, low-bit width) pair on tiny tensors, and nothing in the product passes it."""
     from .backends import mlp_tree as B
     from .container import quantize_tensor
-    from .context import encoder
+    from .coders import make_coder
     bits = check_bits(bits)
-    dc = _coder(coder, symbols_per_lane)
+    coders = make_coder(coder, symbols_per_lane)
     if not state:
         raise ValueError("encode_mlp: no tensors")
     for name, p in state.items():
@@ -224,16 +224,13 @@ def encode_mlp(state: Dict[str, torch.Tensor], bits: int = 13, coder: str = "hos
         files = [os.path.join(td, f"mlp{j}.b") for j in range(lay["D"])]
         for j, f in enumerate(files):
             a, b = base[j], base[j] + lay["plane_n"][j]
-            if dc is not None:
-                dc.encode(sym[a:b], p[a:b], f)
-            else:
-                encoder(sym[a:b], p[a:b], f)
+            coders.encode(sym[a:b], p[a:b], f)
         low_host = low.cpu().numpy().tobytes()
-        if dc is not None:
-            dc.finish()
+        coders.finish()
         for f in files:
             with open(f, "rb") as fin:
                 streams.append(fin.read())
+    coders.shutdown()
     info = dict(model=MODEL, coder="rans1" if coder == "device" else "range", bits=bits,
                 tensors=[dict(name=n, shape=[int(s) for s in state[n].shape], lo=los[t], interval=intervals[t], depth=depths[t])
                          for t, n in enumerate(names)],
@@ -247,13 +244,13 @@ def decode_indices(payload: bytes, info: Dict, device) -> Dict[str, np.ndarray]:
     RuntimeError, before anything is launched, for a payload or a header that do not fit each other; a damaged stream
     gives wrong indices or the device coder's own RuntimeError."""
     from .backends import mlp_tree as B
-    from .context import decoder
+    from .coders import make_coder
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("decode_mlp: a tree1 MLP section decodes on the GPU only (no CPU path)")
     bits, tensors, _, lay = _check_header(info)
     c1, low, streams = split_payload(payload, info)
-    dc = _coder("device" if info.get("coder", "range") == "rans1" else "host", None)
+    coders = make_coder("device" if info.get("coder", "range") == "rans1" else "host")
     desc = _device_vector(lay["desc"], device)
     tables = _device_vector(p_of_c1(np.concatenate(c1)), device) if lay["n_tab"] else None
     prefix = torch.zeros(lay["n"], dtype=torch.int16, device=device)
@@ -264,12 +261,12 @@ def decode_indices(payload: bytes, info: Dict, device) -> Dict[str, np.ndarray]:
             f = os.path.join(td, f"mlp{j}.b")
             with open(f, "wb") as fout:
                 fout.write(streams[j])
-            sym = dc.decode_group([(p, f)])[0] if dc is not None else decoder(p, f)
+            sym, = coders.decode_group([(p, f)])
             B.fold(sym, prefix, desc, bits, j)
     q = torch.empty(lay["n"], dtype=torch.int16, device=device)
     B.unpack(prefix, desc, bits, _device_vector(np.frombuffer(low, dtype=np.uint8).copy(), device), q)
-    if dc is not None:
-        dc.check()
+    coders.check()
+    coders.shutdown()
     q = q.cpu().numpy().view(np.uint16).astype(np.uint32)
     out, at = {}, 0
     for name, shape, n, _, _, _ in tensors:

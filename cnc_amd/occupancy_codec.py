@@ -98,25 +98,18 @@ def join_payload(top_level: np.ndarray, c1: np.ndarray, streams: List[bytes]) ->
     return raw + np.asarray(c1).astype("<u2").tobytes() + b"".join(streams[k] for k in range(len(streams) - 1, -1, -1))
 
 
-def _coder(coder, symbols_per_lane):
-    from .context import DeviceCoder
-    if coder not in ("host", "device"):
-        raise ValueError(f"coder must be 'host' or 'device', got {coder!r}")
-    return DeviceCoder(symbols_per_lane) if coder == "device" else None
-
-
 @torch.no_grad()
 def encode_occupancy(binaries: torch.Tensor, coder: str = "host", symbols_per_lane=None) -> Tuple[bytes, Dict]:
     """binaries: bool / uint8 [n_grids, rx, ry, rz] on the GPU.  Returns (payload, info); info is the section's header
     entry (plus `c1`, which the payload carries and a header need not repeat)."""
     from .backends import occ_pyramid as B
-    from .context import encoder
+    from .coders import make_coder
     if not binaries.is_cuda:
         raise RuntimeError("binaries must be a CUDA tensor")
     shape = [int(s) for s in binaries.shape]
     K = levels_of(shape)
     dev = binaries.device
-    dc = _coder(coder, symbols_per_lane)
+    coders = make_coder(coder, symbols_per_lane)
     g0 = binaries.contiguous()
     g0 = g0.view(torch.uint8) if g0.dtype == torch.bool else g0.to(torch.uint8)
     shapes = [level_shape(shape, k) for k in range(K + 1)]
@@ -158,15 +151,12 @@ def encode_occupancy(binaries: torch.Tensor, coder: str = "host", symbols_per_la
             p = torch.empty(n[k], dtype=torch.float32, device=dev)
             B.probs(ctx[k], tables[k], p)
             files[k] = os.path.join(td, f"occ{k}.b")
-            if dc is not None:
-                dc.encode(sym[k][:n[k]], p, files[k])
-            else:
-                encoder(sym[k][:n[k]], p, files[k])
-        if dc is not None:
-            dc.finish()
+            coders.encode(sym[k][:n[k]], p, files[k])
+        coders.finish()
         for k, f in files.items():
             with open(f, "rb") as fin:
                 streams[k] = fin.read()
+    coders.shutdown()
     info = dict(model=MODEL, shape=shape, levels=K, n=n, c1=c1.astype(int).tolist(), stream_sizes=[len(s) for s in streams],
                 coder="rans1" if coder == "device" else "range")
     return join_payload(top, c1, streams), info
@@ -177,7 +167,7 @@ def decode_occupancy(payload: bytes, info: Dict, device, coder=None) -> torch.Te
     """Inverse of encode_occupancy: the bool grid on `device` (a GPU).  `coder`: what wrote the streams, default what the
     header names.  RuntimeError for a payload or header that does not fit the grid it describes."""
     from .backends import occ_pyramid as B
-    from .context import decoder
+    from .coders import make_coder
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("decode_occupancy: a pyramid1 occupancy section decodes on the GPU only (no CPU path)")
@@ -186,7 +176,7 @@ def decode_occupancy(payload: bytes, info: Dict, device, coder=None) -> torch.Te
         raise RuntimeError(f"occupancy section: streams in an unknown format {fmt!r}")
     if coder is None:
         coder = "device" if fmt == "rans1" else "host"
-    dc = _coder(coder, None)
+    coders = make_coder(coder)
     shape, K, n, _ = _check_header(info)
     top, c1, streams = split_payload(payload, info)
     tables = torch.from_numpy(p_of_c1(c1)).to(device)
@@ -208,11 +198,11 @@ def decode_occupancy(payload: bytes, info: Dict, device, coder=None) -> torch.Te
                 f = os.path.join(td, f"occ{k}.b")
                 with open(f, "wb") as fout:
                     fout.write(streams[k])
-                sym = dc.decode_group([(p, f)])[0] if dc is not None else decoder(p, f)
+                sym, = coders.decode_group([(p, f)])
                 B.scatter(sym, idx, scratch, cells[k + 1], child, status)
             parent = child
-    if dc is not None:
-        dc.check()
+    coders.check()
+    coders.shutdown()
     flags = int(status.item())                                                         # the decode's one wait
     if flags:
         raise RuntimeError(f"occupancy section: the header's candidate counts do not fit the decoded grid (status {flags})")

@@ -82,10 +82,10 @@ class TrainConfig:
     # value, or whose forward tripped the fp16 range guard, updates nothing — decided on the device, no host wait.
     # Also CNC_GUARDED_STEP=1
     guarded_step: bool = False
-    # the device entropy coder (cnc_amd.context.DeviceCoder): `encode` / `save_container` code the tables on
+    # the device entropy coder (cnc_amd.coders.DeviceCoder): `encode` / `save_container` code the tables on
     # the GPU in the "rans1" format instead of with the host range coder.  Also CNC_DEVICE_CODER=1.  Off by default.
     device_coder: bool = False
-    symbols_per_lane: Optional[int] = None     # of the device coder; None = cnc_amd.context.DEVICE_CODER_SYMBOLS_PER_LANE
+    symbols_per_lane: Optional[int] = None     # of the device coder; None = cnc_amd.coders.DEVICE_CODER_SYMBOLS_PER_LANE
     # the occupancy section of `save_container`: "iid" (one Bernoulli frequency for every cell) or "pyramid" (the grid coded
     # from a pyramid of itself with the tables' coder, cnc_amd.occupancy_codec).  Also CNC_OCC_CODER=pyramid.
     occupancy_coder: str = "iid"

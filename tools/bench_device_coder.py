@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from cnc_amd import _lib, context
+from cnc_amd import _lib, coders
 from cnc_amd._codec import lib as codec_lib
 from cnc_amd.trainer import TrainConfig, Trainer
 
@@ -132,6 +132,9 @@ class _Collect:
                 return 0
         return Done()
 
+    def finish(self):
+        return 0
+
     def shutdown(self):
         pass
 
@@ -139,8 +142,8 @@ class _Collect:
 def host_split(tr, reps):
     """The host path's parts, each alone: the probability kernels; the device -> host copies; the range coder."""
     tr.cfg.device_coder = False
-    real = context.CoderPool
-    context.CoderPool = _Collect
+    real = coders.CoderPool          # the name `coders.make_coder` looks up
+    coders.CoderPool = _Collect
     prob = []
     try:
         for _ in range(reps + 1):
@@ -151,7 +154,7 @@ def host_split(tr, reps):
             torch.cuda.synchronize()
             prob.append(time.perf_counter() - t0)
     finally:
-        context.CoderPool = real
+        coders.CoderPool = real
     streams = _Collect.streams
     n_sym = sum(x.numel() for x, _ in streams)
     torch.cuda.synchronize()
