@@ -502,6 +502,34 @@ def test_backward_ste_clip_count_hint(cuda, oracle, outliers):
         assert np.all(ge.cpu().numpy()[np.abs(emb) > 1] == 0)
 
 
+@pytest.mark.parametrize("F,extra", [(8, 2400), (1, 2403)])
+def test_pack_sign_bits_behind_its_grid_cap(cuda, F, extra):
+    """k_pack_sign_bits launches at most 256 * 32 = 8192 blocks of 256 lanes, one output byte (8 values) a lane, and walks
+    on by the grid's width: 2,097,152 bytes = 16,777,216 values a trip.  One trip plus 300 bytes (F = 8), and plus three
+    values more (F = 1: the scalar tail on the second trip).  Every byte against the same bits packed by tensor
+    expressions, the clip count against the count of |v| > 1 — integers, equal or not (on the MI355X: no byte differs,
+    the counts are equal)."""
+    from cnc_amd.backends import gridencoder_backend as be
+    g = torch.Generator(device=cuda).manual_seed(F)
+    n_vals = 8 * 8192 * 256 + extra
+    emb = (torch.rand(n_vals, device=cuda, generator=g) * 2.2 - 1.1).view(n_vals // F, F)
+    flat = emb.view(-1)
+    flat[::1001] = 0.0
+    flat[1::1001] = -0.0                                       # -0 >= 0: a set bit
+    flat[-1] = 1.5
+    cc = torch.full((1,), 123, dtype=torch.int32, device=cuda)
+    bits = be.pack_sign_bits(emb, None, cc)
+    pad = (-n_vals) % 8
+    sign = torch.cat([flat >= 0, torch.zeros(pad, dtype=torch.bool, device=cuda)]).view(-1, 8).to(torch.int32)
+    want = (sign << torch.arange(8, device=cuda, dtype=torch.int32)).sum(1).to(torch.uint8)
+    wrong = int((bits != want).sum())
+    n_clip = int((flat.abs() > 1).sum())
+    print(f"pack_sign_bits {n_vals} values: {wrong} of {want.numel()} bytes differ; clip count {int(cc.item())}, want {n_clip}")
+    assert bits.numel() == want.numel() == (n_vals + 7) // 8 and wrong == 0
+    assert int(cc.item()) == n_clip and n_clip > 10 ** 6
+    assert want.numel() > 8192 * 256 and int(want[8192 * 256:].to(torch.int64).sum()) > 0
+
+
 @pytest.mark.parametrize("D,Rb", [(3, 16), (3, 128), (2, 32), (2, 128)])
 def test_occupancy_sat_gives_the_scans_answer(cuda, oracle, D, Rb):
     """Masked encode with the summed-volume table == masked encode with the box scan == oracle

@@ -24,8 +24,17 @@ def _grads(f, x, d, wr, wd, chain, train=False):
     return rgb.detach(), den.detach(), {n: p.grad.clone() for n, p in f.named_parameters() if p.grad is not None}
 
 
-@pytest.mark.parametrize("n", [1, 33, 5000, 70001])
-@pytest.mark.parametrize("cfg", ["f8_full", "f4_default", "f2_toy", "f8_toy", "f4_h64"])
+# k_field_bwd_chain and the two-wave forward kernels launch what is resident at once — the occupancy of a 128-thread
+# workgroup times the CUs — and walk `tile += gridDim.x` over the 32-row tiles.  At H = 160 the chain's 22.7 KB of LDS
+# allow 7 workgroups a CU: 70001 rows (2188 tiles) are past it.  At H = 64 the workgroups are small enough for the wave
+# limit, 16 a CU: up to 4096 on 256 CUs, 131,072 rows.  32 * 4096 + 33 rows are past that, the last tile with one row.
+PAST_ANY_RESIDENT_GRID = 32 * 4096 + 33
+CHAIN_CFGS = ["f8_full", "f4_default", "f2_toy", "f8_toy", "f4_h64"]
+CHAIN_SIZES = [(cfg, n) for cfg in CHAIN_CFGS for n in (1, 33, 5000, 70001)] + \
+              [(cfg, PAST_ANY_RESIDENT_GRID) for cfg in ("f2_toy", "f4_h64")]
+
+
+@pytest.mark.parametrize("cfg,n", CHAIN_SIZES)
 def test_chain_gradients_equal_the_layer_by_layer_path(cuda, cfg, n):
     f = _field(cuda, CONFIGS[cfg], seed=8)
     x, d = _inputs(cuda, n, seed=n + 1)
@@ -64,8 +73,7 @@ def test_chain_handles_missing_output_gradients(cuda):
             assert float((a - b).abs().max()) <= 2e-5 * max(float(b.abs().max()), 1e-30), (which, name)
 
 
-@pytest.mark.parametrize("n", [1, 33, 5000, 70001])
-@pytest.mark.parametrize("cfg", ["f8_full", "f4_default", "f2_toy", "f8_toy", "f4_h64"])
+@pytest.mark.parametrize("cfg,n", CHAIN_SIZES)
 def test_fused_training_forward_and_its_gradients(cuda, cfg, n):
     """`_FieldTrain`: the gradient pass's forward as the saving form of the fused evaluator (cnc_field_save_t) — the
     outputs within the fused kernel's 2e-5 of the op chain's, every parameter gradient within 1e-4 of its largest entry

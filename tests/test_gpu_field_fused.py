@@ -69,9 +69,17 @@ def _select(f, precision):
     f.fused_field_precision = precision.split("-")[0]
 
 
+# The fused kernels launch what is resident at once (field_fused_common.hpp `resident_grid`: occupancy x CUs, at most 8
+# one-wave or 16 two-wave workgroups a CU) and walk `tile += gridDim.x` over 32-row tiles: at most 65,536 rows on 256 CUs
+# for the one-wave kernel and 131,072 for the two-wave one.  70001 rows are past the first; 32 * 4096 + 33 rows are past
+# the second, the last tile with one row (H = 64 only: the 2^20-sample test below covers H = 160).
+PAST_ANY_RESIDENT_GRID = 32 * 4096 + 33
+FUSED_SIZES = [(cfg, n) for cfg in CONFIGS for n in (1, 31, 32, 33, 1000, 70001)] + \
+              [(cfg, PAST_ANY_RESIDENT_GRID) for cfg in CONFIGS if CONFIGS[cfg]["n_neurons"] == 64]
+
+
 @PRECISIONS
-@pytest.mark.parametrize("n", [1, 31, 32, 33, 1000, 70001])
-@pytest.mark.parametrize("cfg", list(CONFIGS))
+@pytest.mark.parametrize("cfg,n", FUSED_SIZES)
 def test_fused_field_equals_the_chain(cuda, cfg, n, precision):
     from cnc_amd.field import FusedFieldForward
     f = _field(cuda, CONFIGS[cfg], seed=3)

@@ -518,3 +518,25 @@ def test_window_positions_and_counted_scatter(cuda):
             assert float(out[0]) in set(values[total:k].tolist()) | {float(ref[0])}
             out[0] = ref[0]
         assert torch.equal(out, ref)
+
+
+def test_counted_scatter_behind_its_grid_cap(cuda):
+    """k_scatter_counted launches at most 4096 blocks of 256 lanes (1,048,576 rows) and walks `i += gridDim.x * 256`: a
+    capacity 300 rows past that, the count at the capacity, one row short of the second trip's end, and inside the first
+    trip.  Distinct targets, so the result is a copy: equal to the indexed assignment or not (on the MI355X: no element
+    differs at any of the five counts)."""
+    from cnc_amd.backends import volrend_backend as K
+    g = torch.Generator(device=cuda).manual_seed(9)
+    first_trip = 4096 * 256
+    cap, n = first_trip + 300, first_trip + 1000
+    src = torch.randperm(n, device=cuda, generator=g)[:cap].contiguous()
+    values = torch.rand(cap, device=cuda, generator=g)
+    for count in (cap, cap - 1, first_trip + 1, first_trip, cap + 5):
+        out = torch.full((n,), -1.0, device=cuda)
+        K.scatter_counted(out, src, values, torch.tensor([count], dtype=torch.int64, device=cuda))
+        k = min(count, cap)
+        ref = torch.full((n,), -1.0, device=cuda)
+        ref[src[:k]] = values[:k]
+        wrong = int((out != ref).sum())
+        print(f"scatter_counted capacity {cap}, count {count}: {wrong} of {n} elements differ")
+        assert wrong == 0

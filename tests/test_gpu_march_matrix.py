@@ -564,6 +564,36 @@ def test_ray_aabb_at_frame_size(cuda, oracle, near, far, miss):
     assert _untouched(g0[n * m:]) and _untouched(g1[n * m:]) and _untouched(gh[n * m:])
 
 
+def test_ray_aabb_behind_its_grid_cap(cuda, oracle):
+    """k_ray_aabb launches at most 65535 blocks of 256 lanes (16,776,960 ray-box pairs) and walks on by the grid's width:
+    70 000 rays x 240 boxes = 16,800,000 pairs, the last 23,040 of them on a lane's second trip.  Bit-equal to the oracle
+    (on the MI355X: no element of hits, t_min or t_max differs); nothing written behind the pairs."""
+    lib, stream = _api()
+    n, m = 70_000, 240
+    o, d, _, _ = ML.batch(n, seed=47)
+    rng = np.random.default_rng(48)
+    centre = rng.uniform(-1.2, 1.2, size=(m, 3))
+    half = rng.uniform(0.05, 1.5, size=(m, 3))
+    aabbs = np.concatenate([centre - half, centre + half], axis=1).astype(np.float32)
+    assert n * m > 65535 * 256
+    near, far, miss = 0.5, 4.2, -1.0
+    w0, w1, wh = oracle.ray_aabb_intersect(o, d, aabbs, near, far, miss)
+    behind = wh.reshape(-1)[65535 * 256:]
+    assert 0 < behind.sum() < behind.size
+    od, dd, bd_ = _dev(cuda, o), _dev(cuda, d), _dev(cuda, aabbs)
+    g0, g1 = (_poison(cuda, (n * m + PAD,), torch.float32) for _ in range(2))
+    gh = _poison(cuda, (n * m + PAD,), torch.uint8)
+    rc = lib.cnc_ray_aabb_intersect(_p(od), _p(dd), _p(bd_), n, m, float(near), float(far), float(miss), _p(g0), _p(g1),
+                                    _p(gh), stream(cuda))
+    torch.cuda.synchronize()
+    assert rc == 0
+    wrong = [int((got[: n * m].cpu().numpy() != want.reshape(-1)).sum())
+             for got, want in ((gh, wh.astype(np.uint8)), (g0, w0), (g1, w1))]
+    print(f"ray_aabb {n} x {m}: elements that differ from the oracle (hits, t_min, t_max): {wrong}")
+    assert wrong == [0, 0, 0]
+    assert _untouched(g0[n * m:]) and _untouched(g1[n * m:]) and _untouched(gh[n * m:])
+
+
 @pytest.mark.parametrize("gname", ["ball128", "flipped128", "full128", "nested2x128", "nested4x64", "box64x32x48", "nested2x132"])
 def test_coarse_bits(cuda, gname):
     """cnc_occupancy_coarse_bits against NumPy's `any` over the 4 x 4 x 4 blocks; CNC_ERR_UNSUPPORTED, and nothing written,

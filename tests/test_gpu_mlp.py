@@ -92,6 +92,66 @@ def test_fused_mlp_32_row_kernel(cuda, dims, N, aligned):
     assert (got - want).abs().max() <= 2e-5 * (1 + want.abs().max())
 
 
+def _chain64_in_chunks(seq, x, rows=1 << 15):
+    """`chain64` over row chunks (the float64 activations of half a million rows at once would be ~0.7 GB a layer)."""
+    return torch.cat([chain64(seq, x[r:r + rows]) for r in range(0, x.shape[0], rows)])
+
+
+# Both kernels cap their grid at 256 * 32 = 8192 one-wave blocks (csrc/mlp.hip, `blocks` / `bw`); a block then walks
+# `tile += gridDim.x`.  (rows per wave, rows per tile, dims, N):
+GRID_CAP = 256 * 32
+BEHIND_THE_CAP = [
+    # k_mlp_forward, 16-row tiles: 16 * 8192 + 17 rows = 8194 tiles, blocks 0 and 1 take a second tile, the last tile
+    # holds one row.  Run-time widths, then the two compile-time instances <10, 10, 1> and <10, 5, 0>.
+    (16, 16, (25, 32, 32, 8), 16 * GRID_CAP + 17),
+    (16, 16, (95, 160, 160, 3), 16 * GRID_CAP + 17),
+    (16, 16, (255, 160, 80), 16 * GRID_CAP + 17),
+    # k_mlp_forward64, 64-row tiles.  2^17 rows: the size from which cnc_amd/field.py calls this kernel (2048 full
+    # tiles, one trip).  64 * 8192 + 65 rows = 8194 tiles: blocks 0 and 1 take a second tile, the last tile has one
+    # live row and an empty second 32-row half.
+    (32, 64, (95, 160, 160, 3), 1 << 17),
+    (32, 64, (64, 160, 96), 1 << 17),
+    (32, 64, (95, 160, 160, 3), 64 * GRID_CAP + 65),
+    (32, 64, (64, 160, 96), 64 * GRID_CAP + 65),
+]
+
+
+@pytest.mark.parametrize("rows_per_wave,tile_rows,dims,N", BEHIND_THE_CAP)
+def test_tile_loop_behind_the_grid_cap(cuda, rows_per_wave, tile_rows, dims, N):
+    """The blocks' second trip through `for (tile = blockIdx.x; tile < tiles; tile += gridDim.x)`.
+
+    (a) every output against the float64 chain within the file's REL of max(1, |want|_max);
+    (b) the rows of the second trip and the 64 rows on either side of the first trip's end equal, bit for bit, the same
+        rows evaluated alone in a call that stays inside the first trip: an output element is one k-ordered fmaf chain
+        whose order does not depend on the tile the row sits in.
+
+    Measured on the MI355X, the largest |got - float64| / (REL scale): 16-row kernel 0.0192 ((255, 160, 80)), of that
+    0.0092 on the rows behind the cap; 64-row kernel 0.0204 ((64, 160, 96) at N = 2^17), 0.0119 behind the cap
+    ((64, 160, 96) at N = 524353).  (b) held in all five cases that have a second trip."""
+    from cnc_amd.mlp import FusedMLPForward
+    torch.manual_seed(len(dims) * 1000 + N % 9973 + rows_per_wave)
+    seq = make_seq(dims, cuda)
+    fused = FusedMLPForward(seq, rows_per_wave=rows_per_wave)
+    x = torch.randn(N, dims[0], device=cuda)
+    got = fused(x)
+    assert got.shape == (N, dims[-1])
+    ref = _chain64_in_chunks(seq, x)
+    scale = ref.abs().max().clamp_min(1.0)
+    err = torch.cat([(got[r:r + (1 << 16)].double() - ref[r:r + (1 << 16)]).abs().amax(dim=1)
+                     for r in range(0, N, 1 << 16)])
+    first_trip = tile_rows * GRID_CAP
+    print(f"MLP {rows_per_wave}-row kernel dims={dims} N={N}: |got - float64| / (REL scale) {float(err.max() / (REL * scale)):.3g}"
+          + (f", behind the cap {float(err[first_trip:].max() / (REL * scale)):.3g}" if N > first_trip else ""))
+    assert err.max() <= REL * scale
+    if N > first_trip:
+        lo = first_trip - 64
+        alone = fused(x[lo:].clone())
+        assert alone.shape[0] == N - lo <= first_trip
+        assert torch.equal(alone.view(torch.int32), got[lo:].view(torch.int32)), \
+            f"rows {lo}..{N - 1} differ from the same rows in a call of their own"
+        assert float(got[first_trip:].abs().max()) > 0
+
+
 def test_field_glue_kernels_equal_the_op_chain(cuda):
     """normalise + selector, density activation, SH-4 encoding and the head-input concat as single kernels
     (cnc_amd/csrc/field_glue.hip) vs the reference's op chain (ngp.py:516-547): same rgb / density and the

@@ -54,6 +54,9 @@ GRIDS = {
     "ones": lambda: np.ones((1, 32, 32, 32), np.uint8),
     "corners": lambda: _corners(32),
     "half32": lambda: _rand((1, 32, 32, 32), 0.5, 4),
+    # occ_scan_kernel: one workgroup scans 1024 block counts (262144 parents) per trip and carries the total into the
+    # next.  128^3 has exactly 262144 level-1 parents — one trip; five 80^3 grids have 320000 — two trips
+    "five_80": lambda: _rand((5, 80, 80, 80), 0.05, 5),
 }
 BIG = ("ball128", "blobs_rods128")
 
@@ -245,6 +248,36 @@ def test_wrong_count_stays_inside_the_buffers(cuda, delta):
     assert status.get()[0] == CNC_OCC_STATUS_COUNT
     for buf in (parent, scratch, status, idx, ctx, sym, child):
         assert buf.intact()
+
+
+# occ_scan_kernel's trips: kScanThreads = 1024 counts of 256 parents each.  262144 parents: the last size of one trip;
+# + 1: a second trip of one count (one parent in it); 2 * 262144 + 77: three trips, the last count a partial block
+@pytest.mark.parametrize("n_parents", [262144, 262145, 2 * 262144 + 77])
+def test_rank_scan_carries_between_its_chunks(cuda, n_parents):
+    """cnc_occ_rank on random parent bytes: the scratch equals NumPy's exclusive cumulative sum of the per-256 counts with
+    the total behind it — integers, so equal or not; the status word stays 0 for the right n_expected and takes
+    CNC_OCC_STATUS_COUNT for one that is 8 off either way.  On the MI355X: 0 of 1025, 1026 and 2050 words differ."""
+    from cnc_amd._lib import CNC_OCC_STATUS_COUNT
+    from cnc_amd.backends import occ_pyramid as B
+    rng = np.random.default_rng(n_parents)
+    host = (rng.uniform(size=n_parents) < 0.3).astype(np.uint8) * rng.integers(1, 256, n_parents).astype(np.uint8)
+    host[-1] = 1                                                  # the last trip's last count is not zero
+    per_block = np.add.reduceat((host != 0).astype(np.int64), np.arange(0, n_parents, 256))
+    want = np.concatenate([np.cumsum(per_block) - per_block, [per_block.sum()]]).astype(np.int32)
+    assert want.size == (n_parents + 255) // 256 + 1 == B.rank_scratch_words(n_parents)
+    assert (want.size - 1 > 1024) == (n_parents > 262144) and per_block[:1024].sum() > 0
+    parent = Guarded(host.reshape(1, 1, 1, n_parents), cuda)
+    total = int(want[-1])
+    for n_expected, flag in ((-1, 0), (8 * total, 0), (8 * total + 8, CNC_OCC_STATUS_COUNT), (8 * total - 8, CNC_OCC_STATUS_COUNT)):
+        scratch = Guarded.empty((want.size,), np.int32, cuda)
+        status = Guarded(np.zeros(1, np.int32), cuda)
+        B.rank(parent.tensor(), scratch.tensor(), n_expected=n_expected, status=status.tensor())
+        got = scratch.get()
+        wrong = np.flatnonzero(got != want)
+        print(f"occ rank n_parents={n_parents} n_expected={n_expected}: {wrong.size} of {want.size} words differ")
+        assert wrong.size == 0, (int(wrong[0]), int(got[wrong[0]]), int(want[wrong[0]]))
+        assert status.get()[0] == flag
+        assert scratch.intact() and status.intact() and parent.intact()
 
 
 def test_container_and_trainer(cuda, tmp_path):

@@ -2,13 +2,19 @@
 twins (tests/pose_twin.py, which tests/test_pose_twin.py holds to finite differences and to their float64 modes), run
 under every sentinel fill (tests/guarded.py, in the style of tests/test_gpu_footprint_rays.py), twice.
 
-cnc_camera_pose_apply: C in {1, 3, 7}; per camera a delta of zero, a rotation under the series' switch, at it, of
+cnc_camera_pose_apply: C in {1, 3, 7} and {11, 64, 65, 200} (one thread per camera in blocks of 64: a full block, a second
+block of one camera, four blocks); per camera a delta of zero, a rotation under the series' switch, at it, of
 |omega| = 0.3 and up to pi, with and without a translation; zero delta gives the base table's bits (-0 entries included).
 
 cnc_ray_pose_grad: rays of 0, 1, 64 and 65 samples among others, n_rays in {1, 64, 65, 1000} (one chunk of the fold less
-than full, full, plus one; four chunks), C in {1, 3, 7}, one camera without rays, one camera holding all rays.  The
+than full, full, plus one; four chunks), C in {1, 3, 7}, one camera without rays, one camera holding all rays; C in
+{11, 64, 65, 200} at n_rays in {65, 1000}: k_pose_fold_chunks' 64 threads stride over the cameras from C = 65 on, and
+k_pose_fold_cameras' C * 6 elements need a second 64-lane block from C = 11 on; camera ids outside [0, C).  The
 samples of a ray do not follow those of the ray before: there are holes before, between and behind the rays, and they
-hold the fill — 0xFF reads as NaN, so a kernel that touched a hole would show it."""
+hold the fill — 0xFF reads as NaN, so a kernel that touched a hole would show it.
+
+Measured on the MI355X at C >= 11: both kernels equal their float32 twins bit for bit; the float32 fold's distance from
+its float64 mode is at most 0.020 of the (n_rays + 70) 2^-24 bound (n_rays = 65, C = 200), 0.0033 at n_rays = 1000."""
 import numpy as np
 import pytest
 import torch
@@ -33,16 +39,21 @@ def _deltas(rng, C):
     return d
 
 
-@pytest.mark.parametrize("C", [1, 3, 7])
+# k_camera_pose_apply: one thread per camera, 64 per block — 64 fills the first block, 65 opens a second, 200 needs four
+@pytest.mark.parametrize("C", [1, 3, 7, 11, 64, 65, 200])
 def test_pose_apply_is_the_twin_bit_for_bit(cuda, C):
     from cnc_amd import _lib
     rng = np.random.default_rng(C)
+    if C >= 7:                                               # every branch of the kernel is taken at this count
+        t2 = (_deltas(np.random.default_rng(0), C)[:, :3].astype(np.float64) ** 2).sum(axis=1)
+        assert (t2 == 0).any() and ((t2 > 0) & (t2 < P.SERIES_BELOW * 0.99)).any() and (t2 > 1.0).any()
+        assert (t2[64:] == 0).any() == (C > 70) and (t2[64:] > 4.0).any() == (C > 67)      # ... in the later blocks too
     clean = _table(rng, C).astype(f32)
     signed = clean.copy()                                    # -0 in a rotation and in a translation entry: zero delta keeps them
     signed[0, 5] = -0.0
     signed[C - 1, 15] = -0.0
     for base, delta in ((clean, _deltas(rng, C)), (signed, np.zeros((C, 6), f32)),
-                        (clean, np.roll(_deltas(rng, 7), 2, axis=0)[:C])):
+                        (clean, np.roll(_deltas(rng, max(C, 7)), 2, axis=0)[:C])):
         def build(fill):
             return dict(base=Guarded(base, cuda, fill=fill), delta=Guarded(delta, cuda, fill=fill),
                         out=Guarded.empty((C, P.CAMERA_ROW), f32, cuda, fill=fill))
@@ -109,6 +120,9 @@ def _rays(rng, n_rays, C, ids_kind):
         ids = np.full(n_rays, C - 1, i64)
     else:                                                    # camera 0 without rays (when there is another one)
         ids = rng.integers(min(1, C - 1), C, size=n_rays).astype(i64)
+    if ids_kind == "some_outside":                           # below 0 and at or above C: clamped to the first / last camera
+        for k, bad in zip(range(3, n_rays, max(1, n_rays // 9)), [-1, C, -(2 ** 40), C + 5, 2 ** 31, -7, 2 ** 62, C, -1]):
+            ids[k] = bad
     return dict(g_x=g_x, t0=t0, t1=t1, starts=starts.astype(i64), counts=counts.astype(i64), d=d, ids=ids, hole=hole, n=n)
 
 
@@ -131,10 +145,26 @@ def _poison(a, hole, fill):
     return a
 
 
+# k_pose_fold_chunks: 64 threads, `c += 64` over the cameras — a second round from C = 65.  k_pose_fold_cameras: one lane
+# per (camera, component), 64 per block — C = 11 is the first C with C * 6 > 64; 64, 65 and 200 give 6, 7 and 19 blocks.
+FOLD_SIZES = [(n_rays, C) for C in (1, 3, 7) for n_rays in (1, 64, 65, 1000)] + \
+             [(n_rays, C) for C in (11, 64, 65, 200) for n_rays in (65, 1000)]
+
+
 @pytest.mark.parametrize("ids_kind", ["one_without", "all_in_one"])
-@pytest.mark.parametrize("C", [1, 3, 7])
-@pytest.mark.parametrize("n_rays", [1, 64, 65, 1000])
+@pytest.mark.parametrize("n_rays,C", FOLD_SIZES)
 def test_ray_pose_grad_is_the_twin_bit_for_bit(cuda, n_rays, C, ids_kind):
+    _check_ray_pose_grad(cuda, n_rays, C, ids_kind)
+
+
+@pytest.mark.parametrize("n_rays,C", [(65, 3), (1000, 65)])
+def test_ray_pose_grad_clamps_camera_ids_outside_the_table(cuda, n_rays, C):
+    """A few cam_ids below 0 and at or above C (up to 2^62): the kernel clamps them to camera 0 / C - 1 as cnc_camera_rays
+    does, and so does the twin; same references and bounds as above."""
+    _check_ray_pose_grad(cuda, n_rays, C, "some_outside")
+
+
+def _check_ray_pose_grad(cuda, n_rays, C, ids_kind):
     from cnc_amd import _lib
     L = _lib.lib()
     v = _rays(np.random.default_rng(n_rays * 10 + C), n_rays, C, ids_kind)
@@ -163,13 +193,18 @@ def test_ray_pose_grad_is_the_twin_bit_for_bit(cuda, n_rays, C, ids_kind):
     assert same_bits(got, want), np.abs(got.astype(np.float64) - want).max()
     if ids_kind == "all_in_one":
         assert np.all(got[:C - 1] == 0) and not np.signbit(got[:C - 1]).any() and np.all(got[C - 1] != 0)
-    elif C > 1:
+    elif C > 1 and ids_kind == "one_without":
         assert np.all(got[0] == 0) and not np.signbit(got[0]).any(), "a camera without rays must get exact zeros"
+    if ids_kind == "some_outside":
+        assert (v["ids"] < 0).sum() >= 2 and (v["ids"] >= C).sum() >= 2
+    idle = np.setdiff1d(np.arange(C), np.clip(v["ids"], 0, C - 1))
+    assert np.all(got[idle] == 0) and not np.signbit(got[idle]).any(), "a camera without rays must get exact zeros"
     # the float32 fold's distance from its float64 mode, within the n - 1 roundings of its longest chain
     G64 = P.ray_pose_grad(v["g_x"], v["t0"], v["t1"], v["starts"], v["counts"], v["d"], v["ids"], C, np.float64)
     A64 = _sums_of_abs_terms(v, C)
     print(f"RAY POSE GRAD n_rays={n_rays} C={C} {ids_kind}: float32 against float64 "
-          f"{float((np.abs(got - G64) / np.maximum(A64, 1e-30)).max()):.3e} of the sums of |terms|")
+          f"{float((np.abs(got - G64) / np.maximum(A64, 1e-30)).max()):.3e} of the sums of |terms|, "
+          f"{float((np.abs(got - G64) / np.maximum((n_rays + 70) * 2.0 ** -24 * A64, 1e-300)).max()):.3g} of the bound")
     assert np.all(np.abs(got - G64) <= (n_rays + 70) * 2.0 ** -24 * A64)
 
 

@@ -1,8 +1,8 @@
 """GPU: cnc_field_position_grad (cnc_amd/csrc/field_position_grad.hip) against its float64 twin
 (tests/pose_twin.py, itself held to central differences by tests/test_pose_twin.py), through the C ABI.
 
-Models: the smallest of tests/field_lattice.py with both a dense and a hashed 3-D level and planes, at F = 2 and F = 8,
-and the all-hashed one (hashed planes too).  N in {1, 63, 64, 65, 257}: one lane quad, a block less one / exactly / plus
+Models: the smallest of tests/field_lattice.py with both a dense and a hashed 3-D level and planes, at F = 2, 4 and 8
+(the kernel's three instances), and the all-hashed one (hashed planes too). N in {1, 63, 64, 65, 257}: one lane quad, a block less one / exactly / plus
 one sample (64 samples per block), several blocks.  The points cycle through: uniform in the box, cell faces of the
 coarsest and finest levels (`field_lattice.boundary_points`: floor() at its edge — twin and kernel take the cell from
 the same float32 operations, so they stand on the same side), the border ring (a coordinate in the outermost cell,
@@ -13,7 +13,8 @@ Bound: |got - want| <= 1e-4 x the entry's sum of |terms| (the bound tests/test_g
 entries); an entry without terms must be exactly 0.  Every buffer lies inside a sentinel-filled allocation
 (tests/guarded.py); dX and the selector have more rows than N, dX and dS wider rows than the kernel reads, all poisoned.
 
-Measured on the MI355X: the largest |got - want| / sum |terms| over all cases is 1.23e-7 (f2_h64_5x3d_5x2d, N = 257)."""
+Measured on the MI355X: the largest |got - want| / sum |terms| over all cases is 1.23e-7 (f2_h64_5x3d_5x2d, N = 257);
+at F = 4, 1.01e-7 (f4_h64_6x3d_1x2d, N = 65), 1.0e-3 of the bound."""
 import ctypes
 
 import numpy as np
@@ -26,7 +27,8 @@ from guarded import Guarded, same_bits, under_fills, moved_with_fill
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-MODELS = ["f2_h64_5x3d_5x2d", "f8_h160_5x3d_3x2d", "f2_h64_4x3d_2x2d_hashed"]
+# (the kernel is instantiated for F in {2, 4, 8}: the last entry is the F = 4 instance, dense and hashed 3-D levels again)
+MODELS = ["f2_h64_5x3d_5x2d", "f8_h160_5x3d_3x2d", "f2_h64_4x3d_2x2d_hashed", "f4_h64_6x3d_1x2d"]
 SIZES = [1, 63, 64, 65, 257]
 AABB = [-1.5, -1.0, -2.0, 1.5, 2.0, 1.0]
 _MODELS = {}

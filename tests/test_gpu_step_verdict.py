@@ -83,13 +83,23 @@ def _clean(rng, n):
     return x
 
 
+# k_verdict_scan's grid is capped at kScanMaxBlocks = 64 blocks of 256 lanes, one uint4 a lane: 65536 elements a pass, the
+# lanes going on `i += stride`.  4097 elements take two blocks; 300003 take the 64 and five passes (on the MI355X every bad
+# word is found at each of the five places behind the first pass, and the clean array gives go)
+ABOVE_THE_GRID_CAP = 300003
+PASS = 64 * 256 * 4
+
+
 def _places(n):
-    """First, last, either side of every 16-byte boundary the length reaches at its start, and of the last one."""
+    """First, last, either side of every 16-byte boundary the length reaches at its start, and of the last one.  Above the
+    grid's cap only the places behind the first grid-wide pass: the second element of each later pass, and the last."""
+    if n == ABOVE_THE_GRID_CAP:
+        return [PASS * k + 1 for k in range(1, 5)] + [n - 1]
     last4 = 4 * ((n - 1) // 4)
     return sorted({i for i in (0, n - 1, 3, 4, last4 - 1, last4, n // 2) if 0 <= i < n})
 
 
-@pytest.mark.parametrize("n", LENGTHS)
+@pytest.mark.parametrize("n", LENGTHS + [ABOVE_THE_GRID_CAP])
 def test_one_non_finite_element_anywhere_is_found(cuda, n):
     rng = np.random.default_rng(n)
     v = _Verdict(cuda)
