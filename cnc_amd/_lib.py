@@ -189,6 +189,9 @@ SIGNATURES = {
     "cnc_camera_pose_apply": [_vp, _vp, _i32, _vp, _vp],
     "cnc_ray_pose_grad_workspace": [_u32, _i32],
     "cnc_ray_pose_grad": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _u32, _i32, _vp, C.c_uint64, _vp, _vp],
+    "cnc_envmap_forward": [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
+    "cnc_envmap_backward_rays": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
+    "cnc_envmap_backward_texture": [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp],
     "cnc_level_stats_forward": [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
     "cnc_level_stats_backward": [_vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _vp, _vp],
     "cnc_field_prepare": [_vp, _vp, _u32, _vp, _vp, _vp],

@@ -13,7 +13,8 @@ frequency, or — `occupancy_coder="pyramid"`, the section then says `model: "py
 from a pyramid of itself, occupancy_codec.py), the radiance-field MLP tensors uniformly quantised to
 `mlp_bits` (13) bits and bit-packed (`mlp/<name>` sections) or — `mlp_coder="tree"`, one `mlp` section that says
 `model: "tree1"` — the same indices entropy-coded with a per-tensor bit-tree model (mlp_codec.py) whenever that is smaller,
-the context-model weights in fp32.
+the context-model weights in fp32, and — only when a run learned one — the environment-map background's texture as raw
+uint8 (`envmap`).
 """
 from __future__ import annotations
 
@@ -62,8 +63,9 @@ def quantize_tensor(p: torch.Tensor, bits: int):
 def write_container(path: str, *, meta: Dict, table_streams: Dict[str, bytes], binaries: torch.Tensor,
                     field_mlp: Dict[str, torch.Tensor], context_state: Dict[str, torch.Tensor],
                     mlp_bits: int = 13, occupancy_coder: str = "iid", coder: str = "host", symbols_per_lane=None,
-                    mlp_coder: str = "packed") -> int:
-    """Returns the file size in bytes.  occupancy_coder: "iid" (one Bernoulli frequency, the host range coder) or
+                    mlp_coder: str = "packed", envmap=None) -> int:
+    """Returns the file size in bytes.  envmap: None, or the learned background's uint8 [H, 2H, 3] texture
+    (`EnvMapBackground.quantized()`), written raw as the last section, `envmap`; without it the file is what it was.  occupancy_coder: "iid" (one Bernoulli frequency, the host range coder) or
     "pyramid" (occupancy_codec.encode_occupancy with `coder`, "host" or "device": the coder of the table streams).
     mlp_coder: "packed" (the `mlp/<name>` sections) or "tree" (mlp_codec.encode_mlp with `coder`; the packed sections
     still, byte for byte, when the tree1 section would not be smaller than their sum)."""
@@ -116,6 +118,11 @@ def write_container(path: str, *, meta: Dict, table_streams: Dict[str, bytes], b
             add("mlp/" + name, _pack_bits(q, mlp_bits), shape=list(p.shape), lo=lo, interval=interval, bits=mlp_bits)
     for name, p in context_state.items():
         add("ctx/" + name, p.detach().float().cpu().numpy().tobytes(), shape=list(p.shape))
+    if envmap is not None:
+        u8 = torch.as_tensor(envmap).detach().cpu()
+        if u8.dtype != torch.uint8 or u8.dim() != 3 or u8.shape[2] != 3 or u8.shape[1] != 2 * u8.shape[0]:
+            raise ValueError(f"envmap must be uint8 [H, 2H, 3], got {u8.dtype} {list(u8.shape)}")
+        add("envmap", u8.contiguous().numpy().tobytes(), shape=list(u8.shape))
     header = json.dumps(dict(meta=meta, sections=sections)).encode()
     with open(path, "wb") as fo:
         fo.write(MAGIC)
@@ -133,8 +140,25 @@ def section_sizes(path: str) -> Dict[str, int]:
         return {name: int(s["size"]) for name, s in json.loads(fi.read(hlen))["sections"].items()}
 
 
+def read_envmap(path: str):
+    """The `envmap` section of a container as uint8 [H, 2H, 3] (on the host), or None when it has none."""
+    with open(path, "rb") as fi:
+        assert fi.read(4) == MAGIC, "not a CNC1 container"
+        (hlen,) = struct.unpack("<I", fi.read(4))
+        s = json.loads(fi.read(hlen))["sections"].get("envmap")
+        if s is None:
+            return None
+        fi.seek(int(s["offset"]), os.SEEK_CUR)
+        data = fi.read(int(s["size"]))
+    shape = [int(v) for v in s["shape"]]
+    if len(shape) != 3 or shape[2] != 3 or shape[1] != 2 * shape[0] or len(data) != int(np.prod(shape)):
+        raise RuntimeError(f"{path}: malformed envmap section (shape {shape}, {len(data)} bytes)")
+    return torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).view(*shape)
+
+
 def read_container(path: str, device="cpu"):
-    """Returns (meta, table_streams, binaries, field_mlp (dequantised), context_state)."""
+    """Returns (meta, table_streams, binaries, field_mlp (dequantised), context_state).  A learned background, when the file
+    has one, is read by `read_envmap`: section names this function does not know are ignored."""
     with open(path, "rb") as fi:
         assert fi.read(4) == MAGIC, "not a CNC1 container"
         (hlen,) = struct.unpack("<I", fi.read(4))

@@ -322,6 +322,7 @@ class SyntheticBallDataset:
     (nerf_synthetic.py:164-239); `view(i)` returns a whole test image."""
 
     RADIUS = 0.8
+    has_alpha = True         # pixels a ray misses the ball with are transparent, blended with the batch's colour (`fetch`)
 
     def __init__(self, image_size=200, n_train_views=100, device="cuda", seed=0):
         self.H = self.W = image_size

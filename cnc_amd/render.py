@@ -101,7 +101,7 @@ def render_image_with_occgrid(radiance_field: torch.nn.Module, estimator: OccGri
                               render_bkgd: Optional[torch.Tensor] = None, cone_angle: float = 0.0,
                               alpha_thre: float = 0.0, test_chunk_size: int = 8192,
                               timestamps: Optional[torch.Tensor] = None, return_extra=False, tmp=None, *,
-                              with_samples=False, position_grad=False):
+                              with_samples=False, position_grad=False, background=None):
     """(rgb, opacity, depth, n_samples[, extras]) for a batch or an image of rays.  Training renders every
     ray in one go with jittered sample offsets; evaluation goes `test_chunk_size` rays at a time.  For each
     chunk the estimator picks the samples (a gradient-free density pass decides visibility), then the field is
@@ -110,9 +110,12 @@ def render_image_with_occgrid(radiance_field: torch.nn.Module, estimator: OccGri
     last chunk, like the other extras) — what a loss on the samples needs (`cnc_amd.nerfacc.losses.distortion`).
     `position_grad` (extension; implies `with_samples`): the sample positions the field is queried at are a leaf that
     requires grad, handed out as the extras' `positions` — after the backward its `.grad` is dL/dx per sample, what the
-    camera-pose gradient is folded from (`cnc_amd.poses`)."""
+    camera-pose gradient is folded from (`cnc_amd.poses`).  `background` (extension): a `cnc_amd.envmap.EnvMapBackground`;
+    the chunks are rendered with `render_bkgd=None` and composited through it, rgb + (1 - opacity) env(viewdirs)."""
     if timestamps is not None:
         raise NotImplementedError("time-dependent fields (dnerf) are outside the CNC path")
+    if background is not None:
+        render_bkgd = None
     with_samples = with_samples or position_grad
     rays, lead = _as_ray_list(rays)
     total = rays.origins.shape[0]
@@ -131,6 +134,8 @@ def render_image_with_occgrid(radiance_field: torch.nn.Module, estimator: OccGri
         if with_samples:
             extras = dict(extras, t_starts=t_starts, t_ends=t_ends, ray_indices=ray_indices,
                           packed_info=getattr(estimator, "last_packed_info", None))
+        if background is not None:
+            rgb = background(rgb, opacity, d)
         parts.append((rgb, opacity, depth))
         n_samples += t_starts.shape[0]
     rgb, opacity, depth = (torch.cat(p, dim=0).view(*lead, -1) for p in zip(*parts))
@@ -208,11 +213,12 @@ def render_image_with_occgrid_test(max_samples: int, radiance_field: torch.nn.Mo
                                    far_plane: float = 1e10, render_step_size: float = 1e-3,
                                    render_bkgd: Optional[torch.Tensor] = None, cone_angle: float = 0.0,
                                    alpha_thre: float = 0.0, early_stop_eps: float = 1e-4,
-                                   timestamps: Optional[torch.Tensor] = None):
+                                   timestamps: Optional[torch.Tensor] = None, *, background=None):
     """Evaluation render of all rays together, a bounded number of march steps per round: rays that became
     opaque (opacity > 1 - early_stop_eps) or left the grid drop out, the survivors continue from where they
     stopped, and the fewer are alive the more steps each gets (num_rays // alive, at most 64).  Returns
-    (rgb, opacity, depth, n_samples)."""
+    (rgb, opacity, depth, n_samples).  `background` (extension): a `cnc_amd.envmap.EnvMapBackground` composited behind the
+    finished render in place of `render_bkgd`, once (all rays are one chunk here)."""
     if timestamps is not None:
         raise NotImplementedError("time-dependent fields (dnerf) are outside the CNC path")
     from .backends import nerfacc_cuda as _C
@@ -274,7 +280,9 @@ def render_image_with_occgrid_test(max_samples: int, radiance_field: torch.nn.Mo
                 shaded += t_starts.shape[0]
         # a ray goes on if it is not opaque yet and used its whole step budget (else it left the grid)
         alive = (opacity.view(-1) <= opaque) & (counts == steps)
-    if render_bkgd is not None:
+    if background is not None:
+        rgb = background(rgb, opacity, d)
+    elif render_bkgd is not None:
         rgb = rgb + render_bkgd * (1.0 - opacity)
     depth = depth / opacity.clamp_min(torch.finfo(rgb.dtype).eps)
     return rgb.view(*lead, -1), opacity.view(*lead, -1), depth.view(*lead, -1), shaded

@@ -13,7 +13,9 @@ Extensions: --max_steps, --test_views (subset of the test images), --results, --
 (+ --aabb): a capture of one's own in the instant-ngp / nerfstudio transforms.json layout, lens distortion included, and
 --save-mesh (+ --mesh-resolution, --mesh-threshold): the trained scene's surface as a PLY, and --refine-poses LR
 (+ --refine-poses-from STEP): a capture's training poses refined next to the field, written to
-<out_dir>/transforms_refined.json.
+<out_dir>/transforms_refined.json, and --background envmap (+ --envmap-resolution H, --envmap-lr LR): a learned
+environment-map background behind the field, for opaque captures; the run then also writes <out_dir>/scene.cnc, the
+container that holds the map.
 """
 from __future__ import annotations
 
@@ -26,7 +28,7 @@ import time
 import numpy as np
 import torch
 
-from .render import NERF_SYNTHETIC_SCENES, TANKS_SCENES, render_image_with_occgrid_test
+from .render import NERF_SYNTHETIC_SCENES, TANKS_SCENES
 from .trainer import LoaderDataset, TrainConfig, Trainer, quantize_params
 
 NAMED_SCENES = NERF_SYNTHETIC_SCENES + TANKS_SCENES + ["ball"]
@@ -106,6 +108,14 @@ def build_parser():
                          "poses to <out_dir>/transforms_refined.json; 0 = off.  The rate has no tuned default")
     ap.add_argument("--refine-poses-from", dest="refine_poses_from", type=int, default=0, metavar="STEP",
                     help="--refine-poses: the first step that moves the poses")
+    ap.add_argument("--background", choices=["solid", "envmap"], default="solid",
+                    help="what lies behind the field: the batch's colour (solid), or a learned equirectangular texture "
+                         "indexed by ray direction (envmap, DESIGN.md §4.15) for opaque captures without an alpha channel; "
+                         "one process only.  With envmap the run also writes <out_dir>/scene.cnc, the container with the map")
+    ap.add_argument("--envmap-resolution", dest="envmap_resolution", type=int, default=16, metavar="H",
+                    help="--background envmap: the texture is [H, 2H, 3]; H even, 2..64.  The default is untuned")
+    ap.add_argument("--envmap-lr", dest="envmap_lr", type=float, default=1e-2, metavar="LR",
+                    help="--background envmap: the constant Adam rate of the texture.  The default is untuned")
     return ap
 
 
@@ -147,6 +157,8 @@ def make_config_and_data(args, device, rank=0, world=1):
               save_mesh=getattr(args, "save_mesh", None), mesh_resolution=int(getattr(args, "mesh_resolution", 256)),
               mesh_threshold=getattr(args, "mesh_threshold", None),
               pose_lr=float(getattr(args, "refine_poses", 0.0)), pose_refine_from=int(getattr(args, "refine_poses_from", 0)),
+              background=getattr(args, "background", "solid"), envmap_resolution=int(getattr(args, "envmap_resolution", 16)),
+              envmap_lr=float(getattr(args, "envmap_lr", 1e-2)),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0
@@ -193,15 +205,12 @@ def evaluate(tr: Trainer, n_views: int):
     all-reduced — every rank calls this at the same point of the protocol and gets the same three numbers."""
     from . import dist as cdist
     from .metrics import psnr, ssim
-    c = tr.cfg
     tr.field.eval(); tr.estimator.eval()
     lo, hi = cdist.shard_range(n_views, tr.rank, tr.world)
     ps = ss = 0.0
     for i in range(lo, hi):
         d = tr.dataset.view(i)
-        rgb, _, _, _ = render_image_with_occgrid_test(1024, tr.field, tr.estimator, d["rays"], near_plane=c.near_plane,
-                                                      render_step_size=c.render_step_size, render_bkgd=d["color_bkgd"],
-                                                      cone_angle=c.cone_angle, alpha_thre=c.alpha_thre)
+        rgb = tr.render_test_view(d)
         ps += psnr(rgb, d["pixels"])
         ss += -ssim(rgb.permute(2, 0, 1).unsqueeze(0), d["pixels"].permute(2, 0, 1).unsqueeze(0))
     ps, ss = cdist.sum_over_ranks([ps, ss], tr.device)
@@ -244,6 +253,13 @@ def main(argv=None):
     say(f"evaluation_decoded: psnr_avg_codec={psnr_c}, lpips_avg_codec={lpips_c}, ssim_avg_codec={ssim_c}, "
           f"size_codec={embed_bits_MB_codec}")
 
+    if tr.envmap is not None and rank == 0:
+        # the learned background travels in the container only (the .b files hold the tables): write one, from the model as
+        # it stands here — decoded tables, the MLP not yet quantised (the container quantises it itself)
+        box = os.path.join(cfg.out_dir, "scene.cnc")
+        kb = tr.save_container(box)
+        say(f"container with the learned background ({tr.envmap.texture.numel()} bytes of envmap): {box}, "
+            f"{kb['file_KB']:.1f} KB")
     sizes = tr.sizes_MB(embed_bits_MB_codec)
     occ_note = ""
     if tr.occupancy_coder_name() == "pyramid" and all(int(s) % 2 == 0 for s in tr.estimator.binaries.shape[1:]):

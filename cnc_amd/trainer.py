@@ -108,6 +108,14 @@ class TrainConfig:
     # through `TransformsLoader` on the GPU, one process, a bounded field; the rate has no tuned default
     pose_lr: float = 0.0
     pose_refine_from: int = 0
+    # the background behind the field: "solid" = the batch's colour, as ever — no object, launch, optimizer
+    # or batch key more than before; "envmap" = a learned equirectangular texture [H, 2H, 3] indexed by ray direction
+    # (cnc_amd.envmap), for opaque captures without an alpha channel.  envmap_resolution is H (even, 2..64; 16: a section of
+    # 1,536 bytes).  envmap_lr: the constant rate of the texture's own Adam — UNTUNED, like the default resolution: nobody has
+    # run this on a real capture here.  One process only
+    background: str = "solid"
+    envmap_resolution: int = 16
+    envmap_lr: float = 1e-2
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -200,6 +208,19 @@ class _StreamMismatchWarningOff:
         return False
 
 
+def _dataset_has_alpha(dataset) -> bool:
+    """Do the training images carry alpha below 1?  What the dataset says of itself (`has_alpha`), else a loader's RGBA
+    images, looked at once (a host read: construction only); a dataset that offers neither is taken to be opaque."""
+    own = getattr(dataset, "has_alpha", None)
+    if own is not None:
+        return bool(own)
+    images = getattr(getattr(dataset, "train", None), "images", None)
+    if isinstance(images, torch.Tensor) and images.dim() == 4 and images.shape[-1] == 4 and images.numel():
+        top = 255 if images.dtype == torch.uint8 else 1.0
+        return bool((images[..., 3] < top).any())
+    return False
+
+
 class Trainer:
     def __init__(self, cfg: TrainConfig, device="cuda", dataset=None):
         """Built in dependency order: device, models and dataset, the guard's decision, optimizers, gradient sinks, the
@@ -218,6 +239,17 @@ class Trainer:
         elif on_gpu and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())     # the worker threads select it by index
         set_random_seed(c.seed)
+        background = getattr(c, "background", "solid")
+        if background not in ("solid", "envmap"):
+            raise ValueError(f"background must be 'solid' or 'envmap', got {background!r}")
+        if background == "envmap":
+            from .backends.envmap_backend import check_resolution
+            check_resolution(c.envmap_resolution)
+            if self.dp:
+                raise ValueError("the environment-map background is not built for data-parallel training (world > 1): the "
+                                 "map's gradient would need a collective of its own")
+            if not (c.envmap_lr > 0):
+                raise ValueError("the environment-map background: envmap_lr must be positive")
         # ---- models and dataset
         aabb = torch.tensor(c.aabb, device=self.device)
         self.estimator = OccGridEstimator(roi_aabb=aabb, resolution=c.grid_resolution, levels=c.grid_nlvl).to(self.device)
@@ -246,6 +278,10 @@ class Trainer:
         # gradients add into ONE buffer per parameter and pass instead of a fresh zero-filled tensor per call
         # (CNC_GRAD_SINK=0: off)
         self._make_optimizers()
+        # ---- the learned background: nothing unless asked for
+        self.envmap = self.opt_env = None
+        if background == "envmap":
+            self._enable_envmap()
         self.loss_scale = 2.0 ** 10          # GradScaler(2**10), never unscaled (train:211,361-362)
         self._make_sinks()
         # ---- the planes' half of the entropy pass as one captured graph per refresh interval (CNC_PLANES_GRAPH=0: op by op)
@@ -384,6 +420,31 @@ class Trainer:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         self.pose_refiner.write_transforms(loader.transforms_path, path, loader.frame_ids)
         return path
+
+    # -------------------------------------------------------------------------------- the learned background
+    def _enable_envmap(self) -> None:
+        """`TrainConfig.background == "envmap"`: the texture, an Adam of its own (fused, no weight decay, a
+        constant rate: no schedule) and one warning when the training images carry alpha below 1 — the option is meant for
+        opaque captures; with RGBA images the loader still blends its pixels with its own background colour."""
+        from .envmap import EnvMapBackground
+        c = self.cfg
+        self.envmap = EnvMapBackground(c.envmap_resolution, device=self.device)
+        self.opt_env = torch.optim.Adam([self.envmap.texture], lr=float(c.envmap_lr), eps=1e-15, weight_decay=0.0,
+                                        fused=self.device.type == "cuda")
+        if _dataset_has_alpha(self.dataset):
+            import warnings
+            warnings.warn("cnc_amd: background='envmap' with training images that carry alpha below 1: the loader still "
+                          "blends those pixels with its own background colour, which the map will then learn; the option "
+                          "is meant for opaque captures")
+
+    def render_test_view(self, d):
+        """The evaluation render of one test view `d` (`dataset.view(i)`) -> rgb [H, W, 3]: behind the batch's colour, or
+        behind the learned background when there is one.  `evaluate()` and the results line's loop both use it."""
+        c = self.cfg
+        rgb, _, _, _ = render_image_with_occgrid_test(
+            1024, self.field, self.estimator, d["rays"], near_plane=c.near_plane, render_step_size=c.render_step_size,
+            render_bkgd=d["color_bkgd"], cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, background=self.envmap)
+        return rgb
 
     def build_context(self):
         """The context models of this configuration (train:221-241).  Their vertex tables draw from the CPU
@@ -706,6 +767,8 @@ class Trainer:
         if bucket is None:
             self.opt.zero_grad(set_to_none=True)
             self.opt2.zero_grad(set_to_none=True)
+            if self.opt_env is not None:
+                self.opt_env.zero_grad(set_to_none=True)
         else:
             bucket.zero()
             bucket.bind(force=True)
@@ -785,17 +848,18 @@ class Trainer:
         c = self.cfg
         rays, pixels, bkgd = data["rays"], data["pixels"], data["color_bkgd"]
         refine = self._pose_step(step, data)
+        # (`background=`: the learned background, when there is one, takes the place of the batch's colour; None = as ever)
         with _gradsink.activate(self.sink_render):
             if refine:
                 rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
                     self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
                     render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
-                    position_grad=True)
+                    position_grad=True, background=self.envmap)
             else:
                 rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
                     self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
                     render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
-                    with_samples=c.distortion_weight > 0)
+                    with_samples=c.distortion_weight > 0, background=self.envmap)
         self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event()
         # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
         # fused one is asked before the poll below can switch it off)
@@ -834,6 +898,9 @@ class Trainer:
         self._update(step, table_pieces, tables_fused)
         if refine:
             self._pose_update()
+        if self.envmap is not None and self.envmap.texture.grad is not None:
+            self.opt_env.step()
+            self.envmap.clamp_()            # what the container's uint8 section can hold
         if not want_stats:
             return {"n_rendering_samples": n_samples, "num_rays": len(pixels)}
         # the step's scalars in one device->host copy
@@ -967,6 +1034,8 @@ class Trainer:
                      if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
             if pose:                            # the pose gradient joins the scan, the poses' Adam takes the same word
                 scan.append(self.pose_refiner.delta.grad.reshape(-1))
+            if self.envmap is not None and self.envmap.texture.grad is not None:       # ... and so does the background's
+                scan.append(self.envmap.texture.grad.reshape(-1))
             sg.scan(scan, range_guard=range_guard)
         else:
             sg.scan([A.flat[lo:hi] for lo, hi in A.runs_excluding(self._tables)] + [A.tail[1:2]])
@@ -975,6 +1044,8 @@ class Trainer:
         self.opt.found_inf = self.opt2.found_inf = sg.found_inf
         if pose:
             self.opt_pose.found_inf = sg.found_inf
+        if self.opt_env is not None:
+            self.opt_env.found_inf = sg.found_inf
         sg.poll()
 
     def _update(self, step, table_pieces, tables_fused) -> None:
@@ -1036,10 +1107,7 @@ class Trainer:
         tot = 0.0
         for i in range(lo, hi):
             d = self.dataset.view(i)
-            rgb, acc, depth, _ = render_image_with_occgrid_test(
-                1024, self.field, self.estimator, d["rays"], near_plane=c.near_plane,
-                render_step_size=c.render_step_size, render_bkgd=d["color_bkgd"], cone_angle=c.cone_angle,
-                alpha_thre=c.alpha_thre)
+            rgb = self.render_test_view(d)
             mse = F.mse_loss(rgb, d["pixels"])
             tot += -10.0 * math.log10(max(mse.item(), 1e-12))
         tot = cdist.sum_over_ranks(tot, self.device)
@@ -1113,8 +1181,12 @@ class Trainer:
         _, occ_MB, _ = get_binary_vxl_size(self.estimator.binaries)
         mlp = {k: v for k, v in self.field.state_dict().items() if "encoding" not in k and k != "aabb"}
         mlp_MB, _, _ = quantize_params(mlp, digits=13)
-        return {"embeddings": coded_MB, "context_models": ctx_MB, "occupancy_grid": occ_MB, "mlp_13bit": mlp_MB,
-                "total": coded_MB + ctx_MB + occ_MB + mlp_MB}
+        sizes = {"embeddings": coded_MB, "context_models": ctx_MB, "occupancy_grid": occ_MB, "mlp_13bit": mlp_MB,
+                 "total": coded_MB + ctx_MB + occ_MB + mlp_MB}
+        if self.envmap is not None:          # the container's raw uint8 section
+            sizes["envmap"] = self.envmap.texture.numel() / 1024.0 / 1024.0
+            sizes["total"] += sizes["envmap"]
+        return sizes
 
     # ------------------------------------------------------------------------------ container
     def _mlp_state(self):
@@ -1140,7 +1212,7 @@ class Trainer:
         size = write_container(path, meta=meta, table_streams=streams, binaries=self.estimator.binaries,
                                field_mlp=self._mlp_state(), context_state=self.context.state_dict(), occupancy_coder=occ,
                                coder=self.coder_name(), symbols_per_lane=getattr(self.cfg, "symbols_per_lane", None),
-                               mlp_coder=mlp)
+                               mlp_coder=mlp, envmap=None if self.envmap is None else self.envmap.quantized())
         res = {"file_KB": size / 1024.0, "embeddings_KB": coded_MB * 1024.0, "estimate_KB": est_MB * 1024.0}
         if occ == "pyramid":       # the section as written (the Bernoulli one still, for a grid with an odd side)
             res["occupancy_KB"] = section_sizes(path)["occupancy"] / 1024.0
@@ -1152,8 +1224,17 @@ class Trainer:
     def load_container(self, path: str) -> None:
         """Inverse of save_container on a freshly constructed Trainer with the same config: restores
         occupancy, context models and the (13-bit) MLP, then decodes the four tables."""
-        from .container import read_container
+        from .container import read_container, read_envmap
         import tempfile
+        env = read_envmap(path)
+        if (env is None) != (self.envmap is None):
+            raise RuntimeError(f"{path} " + ("holds a learned background (an `envmap` section) and this Trainer has none: "
+                                             "build it with background='envmap'" if self.envmap is None else
+                                             "holds no learned background and this Trainer has one: build it with "
+                                             "background='solid'"))
+        if env is not None and tuple(env.shape) != tuple(self.envmap.texture.shape):
+            raise RuntimeError(f"{path}: the background is {list(env.shape)}, this Trainer's {list(self.envmap.texture.shape)}"
+                               " (envmap_resolution)")
         meta, streams, binaries, mlp, ctx = read_container(path, device=self.device)
         self.estimator.binaries = binaries.to(self.device)
         self.context.load_state_dict(ctx, strict=True)
@@ -1166,3 +1247,5 @@ class Trainer:
             if fmt not in (None, "rans1"):
                 raise RuntimeError(f"{path}: table streams in an unknown format {fmt!r}")
             self.decode_into_field(Pgs, os.path.join(td, "b"), coder="device" if fmt == "rans1" else "host")
+        if env is not None:          # validated above, assigned last: a load that failed on the way leaves the map as it was
+            self.envmap.load_quantized(env)

@@ -793,6 +793,46 @@ int cnc_ray_pose_grad(const float* g_x, const float* t_starts, const float* t_en
                       const int64_t* chunk_starts, const int64_t* chunk_cnts, const float* dirs, const int64_t* cam_ids,
                       uint32_t n_rays, int32_t n_cams, void* workspace, uint64_t workspace_bytes, float* G, void* stream);
 
+/* (ABI v33, added entries: no signature changed) The learned environment-map background (csrc/envmap.hip):
+ * an equirectangular RGB texture T f32 [H, W, 3], W = 2 H, H even and 2 <= H <= 64, looked up by ray direction and
+ * composited behind the field.  n <= 2^29 - 1 rays; n == 0 succeeds, launches nothing and touches nothing.
+ * CNC_ERR_INVALID_VALUE for any other H or n and for a null pointer that is not marked nullable.  No launch caps its grid.
+ *
+ * Per ray, in float32, nothing fused, in this order (d = dirs[r], not necessarily of unit length):
+ *     dead  <=>  a component of d is not finite, or len = sqrt((dx dx + dy dy) + dz dz) is zero or not finite
+ *                (decided before anything else: no index is formed from a NaN)
+ *     cz = clamp(dz / len, -1, 1) ;  phi = atan2f(dy, dx) ;  theta = acosf(cz)
+ *     u = (phi / 2pi + 0.5) W - 0.5 ;  v = (theta / pi) H - 0.5        (2pi, pi: the float32 nearest to each)
+ *     x0 = floor(u), fx = u - x0 ;  y0 = floor(v), fy = v - y0 ;  as integers x0 clamped into [-1, W - 1], y0 into
+ *     [-1, H - 1] ;  x0 == W - 1 is then renamed -1: the same pair of columns (W - 1, 0) with the same fx
+ *     cell = (y0 + 1) W + (x0 + 1)        (x0 + 1 in [0, W - 1], so the cell names (x0, y0) uniquely) ;  dead: cell = -1
+ *     columns wrap: xa = x0 mod W, xb = (x0 + 1) mod W ;  rows clamp: ya = max(y0, 0), yb = min(y0 + 1, H - 1)
+ *     gx = 1 - fx, gy = 1 - fy ;  w0 = gx gy, w1 = fx gy, w2 = gx fy, w3 = fx fy     (corner k = 2 [row yb] + [column xb])
+ *     env_c = ((w0 T[ya, xa, c] + w1 T[ya, xb, c]) + w2 T[yb, xa, c]) + w3 T[yb, xb, c] ;  dead: env = 0, frac = 0
+ * cnc_envmap_forward: out[r, c] = rgb[r, c] + (1 - opacity[r]) env_c ;  rgb == opacity == NULL (both or neither): the pure
+ * lookup, out = env.  cell i32 [n] and frac f32 [n, 2] = (fx, fy) are what the backward reads; both nullable.
+ * cnc_envmap_backward_rays, from the forward's cell and frac (env recomputed by the expressions above):
+ *     g_opacity[r] = -((g0 env_0 + g1 env_1) + g2 env_2), +0 for a dead ray (nullable: the pure lookup has none)
+ *     s[r, c] = (1 - opacity[r]) g_out[r, c]   (opacity NULL: 1 g_out)
+ *     keys i32 [n, 4]: the texel ya W + xa etc. of corner k, H W for every corner of a dead ray
+ * There is no gradient with respect to the direction.
+ * cnc_envmap_backward_texture: g_texture[t, c] = the sum of w_k s[r, c] over the contributions i = 4 r + k listed in
+ * order[offsets[t] .. offsets[t + 1]) (i64 both; offsets [H W + 1]) — the caller groups the 4 n contributions by key with
+ * a STABLE sort, so that a segment lists its contributions in ascending i.  One wave per texel: lane l adds elements
+ * l, l + 64, l + 128, ... of the segment in that order from +0 (one rounded multiply, one rounded add each), then
+ * p[l] = p[l] + p[l + o] for o = 32, 16, 8, 4, 2, 1.  No atomics of any kind: a function of the segment alone, equal
+ * inputs give equal bits, and there is no second route.  Every element of g_texture is written exactly once by a plain
+ * store; a texel without contributions gets +0.  Segments are cut to [0, 4 n) and list entries outside it are skipped: no
+ * load leaves the arrays whatever the tables hold.                                                                     */
+int cnc_envmap_forward(const float* dirs, const float* rgb /* nullable */, const float* opacity /* nullable */,
+                       const float* texture, int32_t H, int64_t n, float* out, int32_t* cell /* nullable */,
+                       float* frac /* nullable */, void* stream);
+int cnc_envmap_backward_rays(const float* g_out, const float* opacity /* nullable */, const int32_t* cell, const float* frac,
+                             const float* texture, int32_t H, int64_t n, float* g_opacity /* nullable */, float* s,
+                             int32_t* keys, void* stream);
+int cnc_envmap_backward_texture(const int64_t* order, const int64_t* offsets, const float* frac, const float* s, int32_t H,
+                                int64_t n, float* g_texture, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Context-model heads and the Bernoulli rate  —  replace the ATen chains of examples/utils_bpp_acc.py
  * (context MLPs :378-393 applied at :561-566 / :689-692, hash fusion :567-572 / :693-701,
