@@ -252,6 +252,9 @@ SIGNATURES = {
     "cnc_iso_classify": [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp],
     "cnc_iso_emit_vertices": [_vp, _i32, _i32, _i32, _f32, C.POINTER(_f32), C.POINTER(_f32), _vp, _vp, _i64, _vp, _vp, _vp],
     "cnc_iso_emit_faces": [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "cnc_components_label_grid": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "cnc_components_sizes": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "cnc_components_label_graph": [_vp, _i64, _i32, _vp, _vp],
 }
 
 # entry points that return something other than a status code

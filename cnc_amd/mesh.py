@@ -164,9 +164,19 @@ class Mesh:
             fh.write(rec.tobytes())
             fh.write(frec.tobytes())
 
-    def components(self) -> np.ndarray:
+    def components(self, on_device: bool = False) -> np.ndarray:
         """Face count of every connected component, largest first (a floater is a small closed component).  A union-find
-        on the host, over the vertices: roots hooked under the smaller root, paths halved until nothing moves."""
+        on the host, over the vertices: roots hooked under the smaller root, paths halved until nothing moves.
+        on_device=True: the same array from the device's union-find (`cnc_amd.components.label_graph`) and a bincount of
+        the label of every face's first vertex; the faces stay where they are."""
+        if on_device:
+            from .components import label_graph
+            if self.faces.shape[0] == 0:
+                return np.zeros(0, np.int64)
+            labels = label_graph(self.faces.contiguous(), int(self.vertices.shape[0]))
+            counts = torch.bincount(labels[self.faces[:, 0].to(torch.int64)].to(torch.int64))
+            counts = counts[counts > 0].cpu().numpy()
+            return np.sort(counts)[::-1].astype(np.int64)
         f = self.faces.detach().cpu().numpy().astype(np.int64)
         if f.shape[0] == 0:
             return np.zeros(0, np.int64)
@@ -198,7 +208,8 @@ _POPCOUNT = np.asarray([bin(m).count("1") for m in range(256)], np.uint8)
 @torch.no_grad()
 def extract_mesh(density: Union[Callable, torch.Tensor], aabb, resolution: int = 256, threshold: Optional[float] = None, *,
                  occupancy: Optional[torch.Tensor] = None, cap: bool = True, normals: bool = True,
-                 render_step_size: Optional[float] = None, chunk: int = 1 << 20, device=None, return_lattice: bool = False):
+                 render_step_size: Optional[float] = None, chunk: int = 1 << 20, device=None, return_lattice: bool = False,
+                 min_component_points: int = 0):
     """The surface `density == threshold` inside the box `aabb` as a Mesh (tensors on the device).
 
     density      a callable [M, 3] -> [M] or [M, 1] (evaluated in chunks of `chunk` points, without gradients), or a ready
@@ -212,8 +223,16 @@ def extract_mesh(density: Union[Callable, torch.Tensor], aabb, resolution: int =
     normals      also the unit normals, from the lattice's differences
     device       of a callable's lattice; default: the occupancy grid's, else the current GPU
     return_lattice   debugging: return (mesh, the float32 lattice the mesh was cut from, capping applied)
+    min_component_points   > 0: prune floaters before the surface is cut.  The inside set — the lattice points with
+                 density >= threshold (NaN is outside), the box's boundary excluded under `cap` — is labelled with the Kuhn
+                 neighbourhood (connectivity 14: the lattice edges marching tetrahedra cuts), and the points
+                 of every component with fewer points get density 0; the largest component always stays.  The mesh is
+                 watertight as before, and a returned lattice is the pruned one.  A cavity inside the object is a
+                 component of the OUTSIDE set and is left alone.  0 (default): off, nothing more is called.  Untuned
     """
     from .backends import iso_surface as iso
+    if int(min_component_points) < 0:
+        raise ValueError(f"min_component_points must not be negative, got {min_component_points}")
     threshold = resolve_threshold(threshold, render_step_size)
     ready = isinstance(density, torch.Tensor)
     if ready:
@@ -269,6 +288,17 @@ def extract_mesh(density: Union[Callable, torch.Tensor], aabb, resolution: int =
                 flat[piece] = val
         del pos, lin
 
+    if int(min_component_points) > 0:
+        from .components import prune_small
+        inside = D >= threshold
+        if cap:
+            for axis in range(3):
+                inside.select(axis, 0).fill_(False)
+                inside.select(axis, -1).fill_(False)
+        kept, _ = prune_small(inside, int(min_component_points), connectivity=14)
+        D.masked_fill_(inside & ~kept, 0.0)
+        del inside, kept
+
     table = torch.from_numpy(tet_table().reshape(-1)).to(device)
     edge_mask = torch.empty(points, dtype=torch.uint8, device=device)
     cell_tris = torch.empty(n[0] * n[1] * n[2], dtype=torch.uint8, device=device)
@@ -295,10 +325,10 @@ def extract_mesh(density: Union[Callable, torch.Tensor], aabb, resolution: int =
 
 @torch.no_grad()
 def field_mesh(field, aabb, occupancy, render_step_size, resolution: int = 256, threshold: Optional[float] = None,
-               colors: bool = True, chunk: int = 1 << 20, return_lattice: bool = False):
+               colors: bool = True, chunk: int = 1 << 20, return_lattice: bool = False, min_component_points: int = 0):
     """The mesh of a radiance field as its renderer sees it: `field.query_density` on the lattice points the occupancy
     grid does not rule out, the default threshold from `render_step_size`, and (colors=True) one call of the field on the
-    vertices with view direction -normal, as uint8.  Bounded fields only."""
+    vertices with view direction -normal, as uint8.  min_component_points: `extract_mesh`'s.  Bounded fields only."""
     if getattr(field, "unbounded", False):
         raise ValueError("mesh export needs a bounded field: an unbounded field (unbounded=True) has no box to march")
     threshold = resolve_threshold(threshold, render_step_size)
@@ -307,7 +337,8 @@ def field_mesh(field, aabb, occupancy, render_step_size, resolution: int = 256, 
     field.eval()
     try:
         out = extract_mesh(lambda x: field.query_density(x), aabb, resolution, threshold, occupancy=occupancy, chunk=chunk,
-                           device=aabb.device if isinstance(aabb, torch.Tensor) else None, return_lattice=return_lattice)
+                           device=aabb.device if isinstance(aabb, torch.Tensor) else None, return_lattice=return_lattice,
+                           min_component_points=min_component_points)
         mesh = out[0] if return_lattice else out
         if colors:
             V = int(mesh.vertices.shape[0])

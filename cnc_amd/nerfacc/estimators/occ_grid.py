@@ -339,6 +339,23 @@ class OccGridEstimator(AbstractEstimator):
         self.binaries = (self.occs > level).view(self.binaries.shape)
 
     @torch.no_grad()
+    def prune_small_components(self, min_cells: int, connectivity: int = 26) -> dict:
+        """(extension) Clear the floaters: every connected component of set cells with fewer than
+        `min_cells` cells, each level on its own; a level's largest component always stays.  The pruned grid is installed
+        as a NEW tensor, the way `_update` installs one (the march's caches key on the buffer's address and version), and
+        `occs` of the cleared cells becomes 0, so that `binaries` and `occs` still agree; a cleared cell was set, so its
+        `occs` was positive and no cell turns invisible.  -> the stats of `cnc_amd.components.prune_small`."""
+        from ...components import prune_small
+        pruned, stats = prune_small(self.binaries, min_cells, connectivity)
+        if stats["removed_cells"]:
+            current = getattr(self, "_vis_key", None) == (id(self.occs), self.occs._version)
+            self.occs.masked_fill_((self.binaries & ~pruned).view(-1), 0.0)
+            if current:                      # the cached answer was about these very contents: it still holds
+                self._stamp_visible()
+        self.binaries = pruned
+        return stats
+
+    @torch.no_grad()
     def mark_invisible_cells(self, K: Tensor, c2w: Tensor, width: int, height: int, near_plane: float = 0.0,
                              chunk: int = 32 ** 3) -> None:
         """occs <- -1 for cells that no camera sees, or that lie between some camera and its near plane while

@@ -15,7 +15,9 @@ Extensions: --max_steps, --test_views (subset of the test images), --results, --
 (+ --refine-poses-from STEP): a capture's training poses refined next to the field, written to
 <out_dir>/transforms_refined.json, and --background envmap (+ --envmap-resolution H, --envmap-lr LR): a learned
 environment-map background behind the field, for opaque captures; the run then also writes <out_dir>/scene.cnc, the
-container that holds the map.
+container that holds the map, and --prune-floaters N (+ --prune-connectivity): the occupancy grid's small connected
+components cleared once, after training and before the first evaluation, and --mesh-min-component N:
+the same for the lattice a --save-mesh mesh is cut from.
 """
 from __future__ import annotations
 
@@ -116,6 +118,15 @@ def build_parser():
                     help="--background envmap: the texture is [H, 2H, 3]; H even, 2..64.  The default is untuned")
     ap.add_argument("--envmap-lr", dest="envmap_lr", type=float, default=1e-2, metavar="LR",
                     help="--background envmap: the constant Adam rate of the texture.  The default is untuned")
+    ap.add_argument("--prune-floaters", dest="prune_floaters", type=int, default=0, metavar="N",
+                    help="after training and before the first evaluation, clear every connected component of the occupancy "
+                         "grid with fewer than N cells (the largest always stays; DESIGN.md §4.16); the test views are "
+                         "evaluated before and after, so that the cut's cost shows.  0 = off.  N has no tuned value")
+    ap.add_argument("--prune-connectivity", dest="prune_connectivity", type=int, choices=[6, 14, 26], default=26,
+                    help="--prune-floaters: which cells count as neighbours; 26 merges most and removes least")
+    ap.add_argument("--mesh-min-component", dest="mesh_min_component", type=int, default=0, metavar="N",
+                    help="--save-mesh: drop the components of the lattice's inside set with fewer than N points before the "
+                         "surface is cut (the largest always stays); 0 = off.  N has no tuned value")
     return ap
 
 
@@ -159,6 +170,8 @@ def make_config_and_data(args, device, rank=0, world=1):
               pose_lr=float(getattr(args, "refine_poses", 0.0)), pose_refine_from=int(getattr(args, "refine_poses_from", 0)),
               background=getattr(args, "background", "solid"), envmap_resolution=int(getattr(args, "envmap_resolution", 16)),
               envmap_lr=float(getattr(args, "envmap_lr", 1e-2)),
+              prune_floaters=int(getattr(args, "prune_floaters", 0)),
+              prune_connectivity=int(getattr(args, "prune_connectivity", 26)),
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0
@@ -238,6 +251,15 @@ def main(argv=None):
     # rank waits in a barrier under the communicator's watchdog while another one works.  Rank 0's files are the
     # ones under the canonical prefix, and rank 0 prints and writes the results line.
     say = print if rank == 0 else (lambda *a, **k: None)
+    if cfg.prune_floaters > 0:
+        # once, before anything reads the grid: the evaluations, the codec, the container and the mesh then see the one
+        # pruned grid (every rank prunes its replica's: same grid, same result).  A thin detached part of the scene can be
+        # a small component, so the views are evaluated on the unpruned grid first
+        psnr_before, _, _ = evaluate(tr, cfg.test_views)
+        say(f"evaluation_before_pruning: psnr_avg={psnr_before}")
+        stats = tr.prune_floaters()
+        say(f"pruned: {stats['removed_components']} components / {stats['removed_cells']} cells removed, "
+            f"{stats['components'] - stats['removed_components']} components kept")
     psnr_avg, lpips_avg, ssim_avg = evaluate(tr, cfg.test_views)
     say(f"evaluation: psnr_avg={psnr_avg}, lpips_avg={lpips_avg}, ssim_avg={ssim_avg}")
 
@@ -298,7 +320,8 @@ def main(argv=None):
     print(f"results line appended to {out}")
     if cfg.save_mesh:
         # last of all, on the decoded tables and the 13-bit MLP: the mesh of the model a receiver would hold
-        mesh = tr.extract_mesh(cfg.save_mesh, resolution=cfg.mesh_resolution, threshold=cfg.mesh_threshold)
+        mesh = tr.extract_mesh(cfg.save_mesh, resolution=cfg.mesh_resolution, threshold=cfg.mesh_threshold,
+                               min_component_points=int(getattr(args, "mesh_min_component", 0)))
         print(f"mesh: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces written to {cfg.save_mesh}")
     return cols
 

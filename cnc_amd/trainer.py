@@ -116,6 +116,13 @@ class TrainConfig:
     background: str = "solid"
     envmap_resolution: int = 16
     envmap_lr: float = 1e-2
+    # floater pruning (cnc_amd.components): `Trainer.prune_floaters()` clears the connected components of
+    # the occupancy grid with fewer than this many cells (the largest always stays); `python -m cnc_amd.train
+    # --prune-floaters N` calls it once, after training and before the first evaluation.  0 = off: no call, launch, log line
+    # or container byte differs.  There is no tuned value: nobody has chosen one on a real capture.  prune_connectivity: 6,
+    # 14 or 26; 26 merges most and so removes least
+    prune_floaters: int = 0
+    prune_connectivity: int = 26
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -250,6 +257,8 @@ class Trainer:
                                  "map's gradient would need a collective of its own")
             if not (c.envmap_lr > 0):
                 raise ValueError("the environment-map background: envmap_lr must be positive")
+        if int(getattr(c, "prune_floaters", 0)) < 0 or getattr(c, "prune_connectivity", 26) not in (6, 14, 26):
+            raise ValueError("floater pruning: prune_floaters must not be negative and prune_connectivity must be 6, 14 or 26")
         # ---- models and dataset
         aabb = torch.tensor(c.aabb, device=self.device)
         self.estimator = OccGridEstimator(roi_aabb=aabb, resolution=c.grid_resolution, levels=c.grid_nlvl).to(self.device)
@@ -1113,18 +1122,31 @@ class Trainer:
         tot = cdist.sum_over_ranks(tot, self.device)
         return tot / max(n_views, 1)
 
+    @torch.no_grad()
+    def prune_floaters(self, min_cells: Optional[int] = None, connectivity: Optional[int] = None) -> Dict[str, int]:
+        """Clear the occupancy grid's floaters: the connected components with fewer than `min_cells` cells,
+        every level on its own, the largest always kept.  None: cfg.prune_floaters / cfg.prune_connectivity.  Everything that
+        reads the grid afterwards — the evaluations, the codec, `save_container`, the mesh — sees the pruned one.  A thin
+        detached part of the scene can be a small component too: compare `evaluate()` before and after.  `min_cells` has no
+        tuned value.  -> {components, cells, removed_components, removed_cells}."""
+        min_cells = int(getattr(self.cfg, "prune_floaters", 0) if min_cells is None else min_cells)
+        connectivity = int(getattr(self.cfg, "prune_connectivity", 26) if connectivity is None else connectivity)
+        return self.estimator.prune_small_components(min_cells, connectivity)
+
     # ------------------------------------------------------------------------------ codec
     def extract_mesh(self, path: Optional[str] = None, resolution: int = 256, threshold: Optional[float] = None,
-                     colors: bool = True, return_lattice: bool = False):
+                     colors: bool = True, return_lattice: bool = False, min_component_points: int = 0):
         """The scene's surface as a `cnc_amd.mesh.Mesh`: marching tetrahedra on a lattice of `resolution`
         cells along the box's longest side, the field's `query_density` evaluated where the estimator's level-0 grid does
         not rule a point out — the scene as the renderer sees it.  threshold None: the density at which one render step
         is half opaque, ln 2 / cfg.render_step_size; it scales with the scene and has not been tuned.  colors: the field
         once on the vertices, seen along -normal.  path: also written there as a binary PLY.  return_lattice (debugging):
-        -> (mesh, the capped float32 lattice it was cut from)."""
+        -> (mesh, the capped float32 lattice it was cut from).  min_component_points > 0: the lattice's inside components
+        with fewer points are dropped first (`cnc_amd.mesh.extract_mesh`); untuned."""
         from .mesh import field_mesh
         out = field_mesh(self.field, self.estimator.aabbs[0], self.estimator.binaries[0], self.cfg.render_step_size,
-                         resolution=resolution, threshold=threshold, colors=colors, return_lattice=return_lattice)
+                         resolution=resolution, threshold=threshold, colors=colors, return_lattice=return_lattice,
+                         min_component_points=min_component_points)
         if path is not None:
             (out[0] if return_lattice else out).save(path)
         return out

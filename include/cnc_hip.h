@@ -1593,6 +1593,28 @@ int cnc_iso_emit_faces(const float* density, int32_t nx, int32_t ny, int32_t nz,
                        const uint8_t* edge_mask, const int32_t* vertex_scan, const uint8_t* cell_tris, const int32_t* cell_scan,
                        int64_t n_vertices, int64_t n_faces, int32_t* faces, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (ABI v33, added entries: no signature changed) Connected components (csrc/components.hip) — an extension.
+ * Stream-ordered, caller-owned buffers, no scratch, no allocation, no host wait, no state between calls; integer atomics
+ * only, and no workgroup waits for another.  No launch caps its grid.  The results are unique: equal inputs give equal bits.
+ *
+ * cnc_components_label_grid: mask u8 [n_grids, d0, d1, d2] (non-zero = set), every grid on its own -> labels i32 of the
+ * same shape: a set cell gets the smallest linear index (i0 d1 + i1) d2 + i2, within its grid, of any cell of its
+ * component, an unset cell -1.  connectivity 6 (face neighbours), 26 (face, edge and corner neighbours) or 14 (the Kuhn
+ * neighbourhood of the mesh export: the offsets in {-1, 0, 1}^3 whose non-zero components all have one sign).  Every d >= 1,
+ * n_grids >= 1, n_grids d0 d1 d2 <= 2^31 - 1; anything else: CNC_ERR_INVALID_VALUE before anything is launched.
+ *
+ * cnc_components_sizes: labels as above -> sizes i32 of the same shape: at a root (labels[i] == i) the cell count of its
+ * component, 0 everywhere else.  The call zeroes `sizes` itself.  A label outside [0, d0 d1 d2) counts nowhere.
+ *
+ * cnc_components_label_graph: faces i32 [n_faces, 3] over n_vertices vertices -> labels i32 [n_vertices]: the smallest
+ * vertex index of the vertex's component, its own index where no face uses it.  A face index outside [0, n_vertices)
+ * joins nothing.  3 n_faces <= 2^31 - 1; n_vertices == 0 succeeds and touches nothing; faces may be NULL for n_faces == 0. */
+int cnc_components_label_grid(const uint8_t* mask, int32_t n_grids, int32_t d0, int32_t d1, int32_t d2, int32_t connectivity,
+                              int32_t* labels, void* stream);
+int cnc_components_sizes(const int32_t* labels, int32_t n_grids, int32_t d0, int32_t d1, int32_t d2, int32_t* sizes, void* stream);
+int cnc_components_label_graph(const int32_t* faces, int64_t n_faces, int32_t n_vertices, int32_t* labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
