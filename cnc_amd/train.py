@@ -17,7 +17,9 @@ Extensions: --max_steps, --test_views (subset of the test images), --results, --
 environment-map background behind the field, for opaque captures; the run then also writes <out_dir>/scene.cnc, the
 container that holds the map, and --prune-floaters N (+ --prune-connectivity): the occupancy grid's small connected
 components cleared once, after training and before the first evaluation, and --mesh-min-component N:
-the same for the lattice a --save-mesh mesh is cut from.
+the same for the lattice a --save-mesh mesh is cut from, and --refine-exposure LR (+ --refine-exposure-from STEP): one
+log-gain per training camera and colour channel learned next to the field, written to
+<out_dir>/exposures.json.
 """
 from __future__ import annotations
 
@@ -110,6 +112,13 @@ def build_parser():
                          "poses to <out_dir>/transforms_refined.json; 0 = off.  The rate has no tuned default")
     ap.add_argument("--refine-poses-from", dest="refine_poses_from", type=int, default=0, metavar="STEP",
                     help="--refine-poses: the first step that moves the poses")
+    ap.add_argument("--refine-exposure", dest="refine_exposure", type=float, default=0.0, metavar="LR",
+                    help="--dataset transforms: learn a log-gain per training camera and colour channel (exposure and white "
+                         "balance, DESIGN.md §4.17) at this Adam learning rate and write them to <out_dir>/exposures.json; "
+                         "evaluation, the mesh and the container render at gain 1, the geometric mean of the training "
+                         "exposures; 0 = off.  The rate has no tuned default: nobody has run this on a real capture here")
+    ap.add_argument("--refine-exposure-from", dest="refine_exposure_from", type=int, default=0, metavar="STEP",
+                    help="--refine-exposure: the first step that moves the gains")
     ap.add_argument("--background", choices=["solid", "envmap"], default="solid",
                     help="what lies behind the field: the batch's colour (solid), or a learned equirectangular texture "
                          "indexed by ray direction (envmap, DESIGN.md §4.15) for opaque captures without an alpha channel; "
@@ -168,6 +177,8 @@ def make_config_and_data(args, device, rank=0, world=1):
               save_mesh=getattr(args, "save_mesh", None), mesh_resolution=int(getattr(args, "mesh_resolution", 256)),
               mesh_threshold=getattr(args, "mesh_threshold", None),
               pose_lr=float(getattr(args, "refine_poses", 0.0)), pose_refine_from=int(getattr(args, "refine_poses_from", 0)),
+              exposure_lr=float(getattr(args, "refine_exposure", 0.0)),
+              exposure_from=int(getattr(args, "refine_exposure_from", 0)),
               background=getattr(args, "background", "solid"), envmap_resolution=int(getattr(args, "envmap_resolution", 16)),
               envmap_lr=float(getattr(args, "envmap_lr", 1e-2)),
               prune_floaters=int(getattr(args, "prune_floaters", 0)),

@@ -123,6 +123,11 @@ class TrainConfig:
     # 14 or 26; 26 merges most and so removes least
     prune_floaters: int = 0
     prune_connectivity: int = 26
+    # per-camera exposure compensation (cnc_amd.exposure): the learning rate of one log-gain per training
+    # camera and colour channel, from step `exposure_from` on.  0 = off: no object, launch, optimizer or batch key more than
+    # without it.  Also CNC_EXPOSURE_LR.  A capture through `TransformsLoader`, one process; the rate has no tuned default
+    exposure_lr: float = 0.0
+    exposure_from: int = 0
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -276,6 +281,9 @@ class Trainer:
         # ---- camera pose refinement: nothing unless asked for (`enable_pose_refinement`, called behind the optimizers)
         self.pose_refiner = self.opt_pose = self._pose_base = None
         self._pose_from, self._pose_on = 0, False
+        # ---- per-camera exposure compensation: nothing unless asked for (`enable_exposure_compensation`, likewise)
+        self.exposure = self.opt_exposure = None
+        self._exposure_from, self._exposure_foreground = 0, False
         # ---- the guarded step's decision, taken here and nowhere else: `_make_optimizers` builds the verdict's buffer from
         # it, the gradient bucket sizes its tail from it
         self._guarded = bool(getattr(c, "guarded_step", False)) or os.environ.get("CNC_GUARDED_STEP", "0") == "1"
@@ -353,6 +361,43 @@ class Trainer:
         pose_lr = float(getattr(c, "pose_lr", 0.0)) or float(os.environ.get("CNC_POSE_LR", "0") or 0.0)
         if pose_lr > 0:
             self.enable_pose_refinement(pose_lr, int(getattr(c, "pose_refine_from", 0)))
+        exposure_lr = float(getattr(c, "exposure_lr", 0.0)) or float(os.environ.get("CNC_EXPOSURE_LR", "0") or 0.0)
+        if exposure_lr != 0:
+            self.enable_exposure_compensation(exposure_lr, int(getattr(c, "exposure_from", 0)))
+
+    # -------------------------------------------------------------------------------- per-camera exposure compensation
+    def enable_exposure_compensation(self, lr: float, start: int = 0) -> None:
+        """From step `start` on, every step also learns one log-gain per training camera and colour channel at rate `lr`
+        (DESIGN.md §4.17): the render is made without a background, `ExposureCompensation` composites the batch's colour
+        and applies the camera's gain (on the foreground only when the training images carry alpha: the loader blended the
+        background in behind the photograph; with the learned background the render is complete as it is and the gain
+        covers all of it), the mse is taken against that, and an Adam of its own (fused, no weight decay, a constant rate;
+        the guarded step's verdict covers it) updates `log_gain`.  Evaluation, the mesh and the container render at gain 1.
+        ValueError where that cannot work: anything but a `LoaderDataset` over a `TransformsLoader` on the GPU, data
+        parallel, or a rate that is not positive."""
+        from .datasets import TransformsLoader
+        from .exposure import ExposureCompensation
+        loader = getattr(self.dataset, "train", None)
+        if not isinstance(self.dataset, LoaderDataset) or not isinstance(loader, TransformsLoader) \
+                or self.device.type != "cuda" or not loader.cameras.is_cuda:
+            raise ValueError("exposure compensation needs a capture with per-camera images on the GPU: a LoaderDataset over a "
+                             "TransformsLoader built with device=cuda (--dataset transforms)")
+        if self.dp:
+            raise ValueError("exposure compensation is not built for data-parallel training (world > 1): the gains' gradient "
+                             "would need a collective of its own")
+        if not (lr > 0):
+            raise ValueError("exposure compensation: the learning rate must be positive")
+        loader.with_camera_ids = True
+        self.exposure = ExposureCompensation(len(loader), self.device)
+        self.opt_exposure = torch.optim.Adam([self.exposure.log_gain], lr=float(lr), eps=1e-15, weight_decay=0.0, fused=True)
+        self._exposure_from, self._exposure_foreground = int(start), _dataset_has_alpha(self.dataset)
+
+    def write_exposures(self, path: Optional[str] = None) -> str:
+        """Every training frame's effective log-gain and gain, to `<out_dir>/exposures.json` (or `path`)."""
+        path = path or os.path.join(self.cfg.out_dir, "exposures.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self.exposure.write(path, self.dataset.train)
+        return path
 
     # -------------------------------------------------------------------------------- camera pose refinement
     def enable_pose_refinement(self, lr: float, start: int = 0) -> None:
@@ -411,6 +456,18 @@ class Trainer:
         from .render import _as_ray_list
         rays, _ = _as_ray_list(data["rays"])
         self.pose_refiner.accumulate(g_x, extra, rays, data["camera_ids"])
+        return True
+
+    def _exposure_gradient(self) -> bool:
+        """Behind the render backward: what the gains' Adam descends along.  False: the ray loss did not reach the gains.
+        It is the gradient with respect to the EFFECTIVE log-gains (`effective_grad`), not its centred form that autograd
+        left in `log_gain.grad`: the two differ by a multiple of (1, ..., 1) per channel, the direction along which no gain
+        changes, but Adam normalises per element — of the centred form it would turn the small common term into a
+        full-rate step of every camera that had no ray in the batch."""
+        ex = self.exposure
+        if ex.log_gain.grad is None:
+            return False
+        ex.log_gain.grad = ex.effective_grad
         return True
 
     def _pose_update(self) -> None:
@@ -778,6 +835,8 @@ class Trainer:
             self.opt2.zero_grad(set_to_none=True)
             if self.opt_env is not None:
                 self.opt_env.zero_grad(set_to_none=True)
+            if self.opt_exposure is not None:
+                self.opt_exposure.zero_grad(set_to_none=True)
         else:
             bucket.zero()
             bucket.bind(force=True)
@@ -857,6 +916,11 @@ class Trainer:
         c = self.cfg
         rays, pixels, bkgd = data["rays"], data["pixels"], data["color_bkgd"]
         refine = self._pose_step(step, data)
+        # exposure compensation composites the batch's colour itself, behind this render (a batch drawn before it was
+        # enabled has no camera ids)
+        gained = self.exposure is not None and step >= self._exposure_from and "camera_ids" in data
+        if gained and self.envmap is None:
+            bkgd = None
         # (`background=`: the learned background, when there is one, takes the place of the batch's colour; None = as ever)
         with _gradsink.activate(self.sink_render):
             if refine:
@@ -888,6 +952,14 @@ class Trainer:
                 self.dataset.update_num_rays(int(len(pixels) * (c.target_sample_batch_size / float(n_samples))))
         # world > 1: no rank leaves the step (the collective below must be entered by everyone; a rank without samples
         # adds a zero ray gradient), and the ray budget follows the all-reduced count of the step before
+        if gained:
+            # the pixel the loss sees: the camera's gain on the render — the learned background's output is complete as it
+            # is; otherwise the batch's colour goes in here, under the gain or behind it (`enable_exposure_compensation`)
+            if self.envmap is not None:
+                rgb = self.exposure(rgb, data["camera_ids"])
+            else:
+                rgb = self.exposure(rgb, data["camera_ids"], acc, data["color_bkgd"],
+                                    gain_background=not self._exposure_foreground)
         mse = F.mse_loss(rgb, pixels)
         # what is back-propagated wherever the mse was: the mse alone, or + the distortion regulariser (this rank's mean over
         # its rays, like the mse; rays without samples count as 0).  The mse itself keeps feeding the statistics
@@ -902,11 +974,15 @@ class Trainer:
             bpp, mb, table_pieces = self._backward_dp(step, ray_loss, ctx_future, tables_fused, len(pixels), n_samples, range_guard)
         if refine:
             refine = self._pose_gradient(data, extra)
+        if gained:
+            gained = self._exposure_gradient()
         if sg is not None:
-            self._verdict(mse, bpp, range_guard, tables_fused, distortion, pose=refine)
+            self._verdict(mse, bpp, range_guard, tables_fused, distortion, pose=refine, exposure=gained)
         self._update(step, table_pieces, tables_fused)
         if refine:
             self._pose_update()
+        if gained:
+            self.opt_exposure.step()
         if self.envmap is not None and self.envmap.texture.grad is not None:
             self.opt_env.step()
             self.envmap.clamp_()            # what the container's uint8 section can hold
@@ -1030,7 +1106,7 @@ class Trainer:
         A.bind(force=True)
         return bpp, mb, table_pieces
 
-    def _verdict(self, mse, bpp, range_guard, tables_fused, distortion=None, pose=False) -> None:
+    def _verdict(self, mse, bpp, range_guard, tables_fused, distortion=None, pose=False, exposure=False) -> None:
         """The guarded step's verdict, on the device and before any update."""
         # Scanned: every gradient the two library optimizers will read (the tables' pieces are not: DESIGN.md §13) and the
         # loss scalars; data parallel: what every rank holds alike — the bucket's summed non-table runs with the entropy
@@ -1045,6 +1121,8 @@ class Trainer:
                 scan.append(self.pose_refiner.delta.grad.reshape(-1))
             if self.envmap is not None and self.envmap.texture.grad is not None:       # ... and so does the background's
                 scan.append(self.envmap.texture.grad.reshape(-1))
+            if exposure:                        # ... and the gains'
+                scan.append(self.exposure.log_gain.grad.reshape(-1))
             sg.scan(scan, range_guard=range_guard)
         else:
             sg.scan([A.flat[lo:hi] for lo, hi in A.runs_excluding(self._tables)] + [A.tail[1:2]])
@@ -1055,6 +1133,8 @@ class Trainer:
             self.opt_pose.found_inf = sg.found_inf
         if self.opt_env is not None:
             self.opt_env.found_inf = sg.found_inf
+        if exposure:
+            self.opt_exposure.found_inf = sg.found_inf
         sg.poll()
 
     def _update(self, step, table_pieces, tables_fused) -> None:
@@ -1097,7 +1177,12 @@ class Trainer:
                 log(f"elapsed_time={time.time() - tic:.2f}s | step={step} | psnr={s['psnr']:.2f} | "
                     f"n_rendering_samples={s['n_rendering_samples']} | num_rays={s['num_rays']} | "
                     f"bits_per_param={s['bpp']:.3f} | embed_bits_MB={s['embed_bits_MB']:.3f}"
-                    + (f" | skipped={self.step_guard.stats()['skipped']}" if self.step_guard is not None else ""))
+                    + (f" | skipped={self.step_guard.stats()['skipped']}" if self.step_guard is not None else "")
+                    + (f" | mean_abs_log_gain={self.exposure.mean_magnitude():.3e}" if self.exposure is not None else ""))
+        if self.exposure is not None and self.rank == 0:
+            path = self.write_exposures()
+            if log:
+                log(f"exposure compensation: mean |log gain|={self.exposure.mean_magnitude():.3e} | written to {path}")
         if self.pose_refiner is not None and self.rank == 0:
             path = self.write_refined_transforms()
             if log:

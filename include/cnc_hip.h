@@ -833,6 +833,53 @@ int cnc_envmap_backward_rays(const float* g_out, const float* opacity /* nullabl
 int cnc_envmap_backward_texture(const int64_t* order, const int64_t* offsets, const float* frac, const float* s, int32_t H,
                                 int64_t n, float* g_texture, void* stream);
 
+/* (ABI v33, added entries: no signature changed) Per-camera exposure compensation (csrc/exposure.hip):
+ * every training camera k has a log-gain e_k (three channels); the pixel the loss sees is the field's composite times
+ * g_k = exp(e_k - mean_j e_j).  n <= 2^31 - 1 rays, n_cams <= (2^31 - 1) / 3; CNC_ERR_INVALID_VALUE otherwise, for a
+ * null pointer that is not marked nullable and for a float array that is not 4-byte (cam_ids: 8-byte) aligned.
+ * n_cams == 0 succeeds, launches nothing and touches nothing; so does n == 0 in cnc_exposure_forward.  No launch caps
+ * its grid.  Everything is float32 with nothing fused, in the order written here; exp alone is evaluated in double and
+ * rounded to float once.
+ *
+ * cnc_exposure_gains: log_gain f32 [n_cams, 3] -> gains f32 [n_cams, 3].  Per channel ch:
+ *     s = 0 ;  s = s + e[k, ch] for k = 0 .. n_cams - 1 in this order ;  mean = s / (float)n_cams
+ *     gains[k, ch] = (float)exp((double)(e[k, ch] - mean))
+ * so that e constant over the cameras (zero included) gives exactly 1.0 wherever e - mean is exactly 0.
+ *
+ * cnc_exposure_forward: out [n, 3] from rgb [n, 3] (c), opacity [n] (a), bkgd (b: 3 floats with bkgd_per_ray == 0,
+ * [n, 3] otherwise), cam_ids i64 [n] clamped into [0, n_cams) as cnc_camera_rays clamps them, g = gains[cam_ids[r]]:
+ *     bkgd == NULL (opacity is then not read and may be NULL):    out = g c
+ *     gain_background != 0 (the gain on the whole pixel):        t = 1 - a ;  out = g (c + t b)
+ *     gain_background == 0 (the gain on the foreground only):    t = 1 - a ;  out = (g c) + (t b)
+ * bkgd without opacity: CNC_ERR_INVALID_VALUE.
+ *
+ * cnc_exposure_backward, from g_out = dL/dout [n, 3] and the forward's inputs (gp = g_out[r], g, c, a, b as above):
+ *     g_rgb[r, ch] = g gp
+ *     g_opacity[r] (nullable; not written when bkgd == NULL):
+ *         whole pixel:      -(((g gp)_0 b_0 + (g gp)_1 b_1) + (g gp)_2 b_2)
+ *         foreground only:  -((gp_0 b_0 + gp_1 b_1) + gp_2 b_2)
+ *     q[r, ch] = gp (g x) with x = c + t b (whole pixel; t b as one rounded product, as in the forward) or x = c
+ * Rays are cut into chunks of 256 consecutive rays.  Per (chunk, camera k) the q[r] of the chunk's rays with
+ * cam_ids[r] == k (clamped) are added in ray order from +0; G_eff[k] = the chunks' sums added in chunk order from +0: the
+ * gradient with respect to the EFFECTIVE log-gain e_k - mean e.  The order is a function of the ray indices alone — no
+ * atomics, nothing that depends on launch geometry or scheduling: equal inputs give equal bits, a camera without rays
+ * gets exact +0, and there is no second route.  Then, per channel, the centring's transpose:
+ *     s = 0 ;  s = s + G_eff[k, ch] for k = 0 .. n_cams - 1 in this order ;  mean = s / (float)n_cams
+ *     G[k, ch] = G_eff[k, ch] - mean                       [the gradient with respect to log_gain itself]
+ * g_gain = G_eff and g_log_gain = G, f32 [n_cams, 3] each, either nullable but not both; every element of each is
+ * written exactly once by a plain store.  n == 0: g_rgb and g_opacity are not touched, G_eff = G = +0.
+ * workspace: cnc_exposure_backward_workspace(n, n_cams) bytes, 4-byte aligned, owned by the call until it has run.   */
+int cnc_exposure_gains(const float* log_gain, int32_t n_cams, float* gains, void* stream);
+int cnc_exposure_forward(const float* rgb, const float* opacity /* nullable */, const float* bkgd /* nullable */,
+                         int32_t bkgd_per_ray, int32_t gain_background, const int64_t* cam_ids, const float* gains,
+                         int32_t n_cams, int64_t n, float* out, void* stream);
+uint64_t cnc_exposure_backward_workspace(int64_t n, int32_t n_cams);
+int cnc_exposure_backward(const float* g_out, const float* rgb, const float* opacity /* nullable */,
+                          const float* bkgd /* nullable */, int32_t bkgd_per_ray, int32_t gain_background,
+                          const int64_t* cam_ids, const float* gains, int32_t n_cams, int64_t n, void* workspace,
+                          uint64_t workspace_bytes, float* g_rgb, float* g_opacity /* nullable */, float* g_gain /* nullable */,
+                          float* g_log_gain /* nullable */, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Context-model heads and the Bernoulli rate  —  replace the ATen chains of examples/utils_bpp_acc.py
  * (context MLPs :378-393 applied at :561-566 / :689-692, hash fusion :567-572 / :693-701,
