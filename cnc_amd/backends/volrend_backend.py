@@ -32,6 +32,13 @@ def _opt(t, name):
     return None if t is None else _f32(t, name)
 
 
+def _one_colour(t):
+    """The kernels read `render_bkgd` as ONE colour, three floats: anything else is an error, not a flat pointer."""
+    if t is not None and t.numel() != 3:
+        raise RuntimeError(f"render_bkgd must hold one colour (3 values), got shape {list(t.shape)}")
+    return _opt(t, "render_bkgd")
+
+
 def _p(t):
     """Device pointer; an EMPTY tensor (no storage, data_ptr 0) is handed down as a valid dummy address —
     the kernels never touch per-sample arrays of rays that have no samples."""
@@ -88,7 +95,7 @@ def volrend_forward(starts, counts, t_starts, t_ends, sigmas, rgbs=None, *, opac
         flags = CNC_VOLREND_FINALIZE if finalize else 0
     check(_lib.lib().cnc_volrend_forward(
         ptr(starts), ptr(counts), _p(t_starts), _p(t_ends), _p(sigmas), _p(rgbs), ptr(_opt(opacity_in, "opacity_in")),
-        _p(_opt(prefix_trans, "prefix_trans")), ptr(_opt(render_bkgd, "render_bkgd")), _p(weights), _p(trans),
+        _p(_opt(prefix_trans, "prefix_trans")), ptr(_one_colour(render_bkgd)), _p(weights), _p(trans),
         _p(alphas), ptr(colors), ptr(opacity), ptr(depth), n_rays, flags, stream(dev)), "volrend_forward")
     return weights, trans, alphas, colors, opacity, depth
 
@@ -103,7 +110,7 @@ def volrend_backward(starts, counts, t_starts, t_ends, rgbs, weights, trans, alp
     c = lambda t, nm: None if t is None else _f32(t.contiguous(), nm)
     check(_lib.lib().cnc_volrend_backward(
         ptr(starts), ptr(counts), _p(t_starts), _p(t_ends), _p(rgbs), _p(weights), _p(trans), _p(alphas),
-        ptr(opacity), ptr(depth), ptr(_opt(render_bkgd, "render_bkgd")), ptr(c(grad_colors, "grad_colors")),
+        ptr(opacity), ptr(depth), ptr(_one_colour(render_bkgd)), ptr(c(grad_colors, "grad_colors")),
         ptr(c(grad_opacity, "grad_opacity")), ptr(c(grad_depth, "grad_depth")), _p(c(grad_weights, "grad_weights")),
         _p(c(grad_trans, "grad_trans")), _p(c(grad_alphas, "grad_alphas")), _p(g_sig), _p(g_rgb), n_rays,
         CNC_VOLREND_FINALIZE if finalize else 0, stream(dev)), "volrend_backward")

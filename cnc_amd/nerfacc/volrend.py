@@ -120,8 +120,15 @@ def rendering(t_starts: Tensor, t_ends: Tensor, ray_indices: Optional[Tensor] = 
 
     chunks = _ray_chunks(t_starts, packed_info, ray_indices, n_rays) if flat else None
     if from_density and _fused(chunks, t_starts, rgbs, dens) and rgbs.dtype == torch.float32:
+        # the kernel composites ONE colour [3]; a colour per ray [n_rays, 3] goes behind its output, as on the generic route
+        per_ray = render_bkgd is not None and render_bkgd.numel() != 3
+        if per_ray and tuple(render_bkgd.shape) != (chunks[0].shape[0], 3):
+            raise ValueError(f"render_bkgd must be one colour [3] or one per ray [{chunks[0].shape[0]}, 3], "
+                             f"got {list(render_bkgd.shape)}")
         colors, opacities, depths, weights, trans, alphas = _Composite.apply(
-            dens, rgbs, t_starts.contiguous(), t_ends.contiguous(), chunks[0], chunks[1], render_bkgd)
+            dens, rgbs, t_starts.contiguous(), t_ends.contiguous(), chunks[0], chunks[1], None if per_ray else render_bkgd)
+        if per_ray:
+            colors = colors + render_bkgd * (1.0 - opacities)
         return colors, opacities, depths, {"weights": weights, "alphas": alphas, "trans": trans, "sigmas": dens,
                                             "rgbs": rgbs, "positions": positions}
 

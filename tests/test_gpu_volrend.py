@@ -165,6 +165,40 @@ def test_autograd_against_float64_chain(cuda, n_rays):
     assert (sg2.grad.double().cpu() - s3.grad).abs().max().item() <= 2e-5 * s3.grad.abs().max().item()
 
 
+def test_per_ray_background_against_float64_chain(cuda):
+    """rendering() with one background colour PER RAY [n_rays, 3] (the kernel composites one colour [3]; a colour per ray
+    goes behind its output): colours and the gradients at sigma and rgb vs float64 autograd of the op chain.  The rays
+    differ in their colour by up to 1, so a composite that took one row for all of them is off by that."""
+    import cnc_amd.nerfacc as n
+    n_rays = 70
+    starts, cnts, ri, t0, t1, sig, rgb = _ragged(n_rays, seed=170, max_len=90)
+    sig = np.minimum(sig, 30)
+    rng = np.random.default_rng(10)
+    gc, bk = rng.normal(size=(n_rays, 3)), rng.uniform(size=(n_rays, 3))
+    s64 = torch.tensor(sig, dtype=torch.float64, requires_grad=True)
+    r64 = torch.tensor(rgb, dtype=torch.float64, requires_grad=True)
+    col, op, _, _, _, _ = _chain64(torch.tensor(t0, dtype=torch.float64), torch.tensor(t1, dtype=torch.float64), s64, r64,
+                                   starts, cnts, torch.tensor(bk))
+    (col * torch.tensor(gc)).sum().backward()
+    assert float((1 - op).max()) > 0.5                       # rays that show their background
+    sg = torch.tensor(sig, device=cuda, requires_grad=True)
+    rg = torch.tensor(rgb, device=cuda, requires_grad=True)
+    T = lambda a: torch.as_tensor(a, device=cuda)
+    col_g, _, _, _ = n.rendering(T(t0), T(t1), T(ri), n_rays=n_rays, rgb_sigma_fn=lambda a, b, c: (rg, sg, None),
+                                 render_bkgd=T(bk.astype(np.float32)))
+    assert torch.allclose(col_g.double().cpu(), col.detach(), atol=2e-6)
+    (col_g * T(gc).float()).sum().backward()
+    assert (sg.grad.double().cpu() - s64.grad).abs().max().item() <= 2e-5 * s64.grad.abs().max().item()
+    assert torch.allclose(rg.grad.double().cpu(), r64.grad, rtol=1e-5, atol=1e-6)
+    # a colour that is neither [3] nor [n_rays, 3] is an error, in rendering() and in the backend's entry point
+    from cnc_amd.backends import volrend_backend as K
+    for bad in (T(bk[:, 0].astype(np.float32)), T(bk[:2].astype(np.float32))):
+        with pytest.raises(ValueError, match="render_bkgd"):
+            n.rendering(T(t0), T(t1), T(ri), n_rays=n_rays, rgb_sigma_fn=lambda a, b, c: (rg, sg, None), render_bkgd=bad)
+    with pytest.raises(RuntimeError, match="one colour"):
+        K.volrend_forward(T(starts), T(cnts), T(t0), T(t1), T(sig), T(rgb), render_bkgd=T(bk.astype(np.float32)), finalize=True)
+
+
 @pytest.mark.parametrize("alpha_thre", [0.0, 0.02])
 def test_visibility_and_compaction(cuda, oracle, alpha_thre):
     from cnc_amd.backends import volrend_backend as K
