@@ -196,6 +196,13 @@ SIGNATURES = {
     "cnc_exposure_forward": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i64, _vp, _vp],
     "cnc_exposure_backward_workspace": [_i64, _i32],
     "cnc_exposure_backward": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp],
+    "cnc_errmap_loss_workspace": [_i64],
+    "cnc_errmap_loss_forward": [_vp, _vp, _vp, _i64, _vp, C.c_uint64, _vp, _vp, _vp],
+    "cnc_errmap_loss_backward": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "cnc_errmap_keys": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
+    "cnc_errmap_update": [_vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp],
+    "cnc_errmap_cdf": [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp],
+    "cnc_errmap_sample": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "cnc_level_stats_forward": [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
     "cnc_level_stats_backward": [_vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _vp, _vp],
     "cnc_field_prepare": [_vp, _vp, _u32, _vp, _vp, _vp],
@@ -268,7 +275,8 @@ RESTYPES = {"cnc_grid_encode_backward_binned_workspace": C.c_uint64,
             "cnc_ctx_mlp_backward_ordered_workspace": C.c_uint64, "cnc_field_backward_chain_ordered_workspace": C.c_uint64,
             "cnc_relu_backward_bias_partials": C.c_uint32, "cnc_occupancy_coarse_words": C.c_uint32,
             "cnc_rans_scratch_bytes": C.c_uint64, "cnc_occ_rank_scratch_bytes": C.c_uint64,
-            "cnc_ray_pose_grad_workspace": C.c_uint64, "cnc_exposure_backward_workspace": C.c_uint64}
+            "cnc_ray_pose_grad_workspace": C.c_uint64, "cnc_exposure_backward_workspace": C.c_uint64,
+            "cnc_errmap_loss_workspace": C.c_uint64}
 
 CNC_FLAG_STE_BINARY = 1
 CNC_FLAG_LEVELS_FINEST_FIRST = 2

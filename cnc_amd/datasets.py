@@ -200,6 +200,10 @@ class TransformsLoader(_PosedImages):
     # set (on the instance) by pose refinement: a training batch also holds "camera_ids" i64 [num_rays], the row of
     # `cameras` every ray was drawn from (cnc_amd.poses).  Off: the batch dict is what it always was
     with_camera_ids = False
+    # set (on the instance) by error-map sampling: an `ErrorMapSampler` (cnc_amd.error_map) whose `draw`, with this loader's
+    # generator, takes the place of the three `randint` draws of a training batch; the batch then also holds "camera_ids",
+    # "pixel_xy" = (px, py) and "ray_weight" f32 [num_rays].  None: the draws and the batch dict are what they always were
+    sampler = None
 
     def __init__(self, subject_id: str, root_fp: str, split: str, color_bkgd_aug: str = "white",
                  num_rays: int = None, near: float = None, far: float = None,
@@ -292,7 +296,11 @@ class TransformsLoader(_PosedImages):
     def __getitem__(self, index):
         from .backends import camera_backend
         dev = self.images.device
-        if self.training or not dev.type == "cuda":
+        weight = None
+        if self.sampler is not None and self.training:
+            ids, x, y, weight = self.sampler.draw(self.num_rays, getattr(self, "_gen", None))
+            shape = (self.num_rays,)
+        elif self.training or not dev.type == "cuda":
             ids, x, y, shape = self._pixels_to_sample(index, dev)
         else:
             ids, shape = None, (self.HEIGHT, self.WIDTH)
@@ -312,6 +320,8 @@ class TransformsLoader(_PosedImages):
                "color_bkgd": bkgd}
         if self.with_camera_ids and self.training:
             out["camera_ids"] = ids
+        if weight is not None:
+            out["camera_ids"], out["pixel_xy"], out["ray_weight"] = ids, (x, y), weight
         return out
 
 

@@ -119,6 +119,13 @@ def build_parser():
                          "exposures; 0 = off.  The rate has no tuned default: nobody has run this on a real capture here")
     ap.add_argument("--refine-exposure-from", dest="refine_exposure_from", type=int, default=0, metavar="STEP",
                     help="--refine-exposure: the first step that moves the gains")
+    ap.add_argument("--error-map-sampling", dest="error_map_sampling", action="store_true",
+                    help="--dataset transforms: draw the training pixels in proportion to a coarse per-image map of the "
+                         "recent loss instead of uniformly, every ray's loss divided by its sampling density (instant-ngp's "
+                         "error map without its sharpness term, DESIGN.md §4.18); one process only.  The uniform floor "
+                         "(0.5), the map's decay (0.9) and the steps between rebuilds of the CDF (16) are untuned")
+    ap.add_argument("--error-map-resolution", dest="error_map_resolution", type=int, default=16, metavar="G",
+                    help="--error-map-sampling: the map holds G x G cells per training image; 1..64.  The default is untuned")
     ap.add_argument("--background", choices=["solid", "envmap"], default="solid",
                     help="what lies behind the field: the batch's colour (solid), or a learned equirectangular texture "
                          "indexed by ray direction (envmap, DESIGN.md §4.15) for opaque captures without an alpha channel; "
@@ -179,6 +186,8 @@ def make_config_and_data(args, device, rank=0, world=1):
               pose_lr=float(getattr(args, "refine_poses", 0.0)), pose_refine_from=int(getattr(args, "refine_poses_from", 0)),
               exposure_lr=float(getattr(args, "refine_exposure", 0.0)),
               exposure_from=int(getattr(args, "refine_exposure_from", 0)),
+              error_map=bool(getattr(args, "error_map_sampling", False)),
+              error_map_resolution=int(getattr(args, "error_map_resolution", 16)),
               background=getattr(args, "background", "solid"), envmap_resolution=int(getattr(args, "envmap_resolution", 16)),
               envmap_lr=float(getattr(args, "envmap_lr", 1e-2)),
               prune_floaters=int(getattr(args, "prune_floaters", 0)),

@@ -128,6 +128,17 @@ class TrainConfig:
     # without it.  Also CNC_EXPOSURE_LR.  A capture through `TransformsLoader`, one process; the rate has no tuned default
     exposure_lr: float = 0.0
     exposure_from: int = 0
+    # error-map pixel sampling (cnc_amd.error_map): training pixels drawn in proportion to a coarse per-image
+    # map of the recent loss ([n_cams, G, G], G = error_map_resolution in 1..64) instead of uniformly, every ray's loss
+    # divided by its sampling density.  False = off: no object, launch, random draw, log field or batch key differs.  Also
+    # CNC_ERROR_MAP=1.  A capture through `TransformsLoader`, one process.  The uniform floor (the least share of its uniform
+    # probability a pixel keeps; weights <= 1 / floor), the map's decay and the steps between rebuilds of the CDF are
+    # UNTUNED defaults: nobody has run this on a real capture here
+    error_map: bool = False
+    error_map_resolution: int = 16
+    error_map_uniform_floor: float = 0.5
+    error_map_decay: float = 0.9
+    error_map_refresh_every: int = 16
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -284,6 +295,8 @@ class Trainer:
         # ---- per-camera exposure compensation: nothing unless asked for (`enable_exposure_compensation`, likewise)
         self.exposure = self.opt_exposure = None
         self._exposure_from, self._exposure_foreground = 0, False
+        # ---- error-map pixel sampling: nothing unless asked for (`enable_error_map_sampling`, likewise)
+        self.error_map = None
         # ---- the guarded step's decision, taken here and nowhere else: `_make_optimizers` builds the verdict's buffer from
         # it, the gradient bucket sizes its tail from it
         self._guarded = bool(getattr(c, "guarded_step", False)) or os.environ.get("CNC_GUARDED_STEP", "0") == "1"
@@ -364,6 +377,40 @@ class Trainer:
         exposure_lr = float(getattr(c, "exposure_lr", 0.0)) or float(os.environ.get("CNC_EXPOSURE_LR", "0") or 0.0)
         if exposure_lr != 0:
             self.enable_exposure_compensation(exposure_lr, int(getattr(c, "exposure_from", 0)))
+        if bool(getattr(c, "error_map", False)) or os.environ.get("CNC_ERROR_MAP", "0") == "1":
+            self.enable_error_map_sampling(int(getattr(c, "error_map_resolution", 16)),
+                                           float(getattr(c, "error_map_uniform_floor", 0.5)),
+                                           float(getattr(c, "error_map_decay", 0.9)),
+                                           int(getattr(c, "error_map_refresh_every", 16)))
+
+    # -------------------------------------------------------------------------------- error-map pixel sampling
+    def enable_error_map_sampling(self, resolution: int = 16, uniform_floor: float = 0.5, decay: float = 0.9,
+                                  refresh_every: int = 16) -> None:
+        """From the next batch drawn on, the training pixels come from an `ErrorMapSampler` over the training cameras
+         instead of the loader's three uniform draws: one `torch.rand` from the loader's own generator and
+        one launch; the batch carries every ray's camera, pixel and weight; the mse of the ray loss becomes the weighted
+        loss kernel's (behind the exposure gain, so the map sees the error the loss sees), whose per-ray errors go into
+        the map; the statistics keep the unweighted mse.  Order of events: the map takes step s's errors right behind
+        step s's loss forward, and where (s + 1) % refresh_every == 0 the CDF is rebuilt right behind that — before the
+        draw for step s + 1 on either schedule (a draw on the look-ahead stream waits for the rebuild's event).
+        `uniform_floor`, `decay` and `refresh_every` have no tuned values.  ValueError where that cannot work: anything but
+        a `LoaderDataset` over a `TransformsLoader` on the GPU that batches over its images, or data parallel."""
+        from .datasets import TransformsLoader
+        from .error_map import ErrorMapSampler
+        loader = getattr(self.dataset, "train", None)
+        if not isinstance(self.dataset, LoaderDataset) or not isinstance(loader, TransformsLoader) \
+                or self.device.type != "cuda" or not loader.cameras.is_cuda:
+            raise ValueError("error-map sampling needs a capture with per-camera images on the GPU: a LoaderDataset over a "
+                             "TransformsLoader built with device=cuda (--dataset transforms)")
+        if self.dp:
+            raise ValueError("error-map sampling is not built for data-parallel training (world > 1): the map would need a "
+                             "collective of its own")
+        if not loader.batch_over_images:
+            raise ValueError("error-map sampling draws every batch over all training images: the TransformsLoader must be "
+                             "built with batch_over_images=True")
+        sampler = ErrorMapSampler(len(loader), loader.HEIGHT, loader.WIDTH, resolution, uniform_floor, decay, refresh_every,
+                                  device=self.device)
+        self.error_map = loader.sampler = sampler          # (a batch drawn ahead of this call carries no weights: plain mse)
 
     # -------------------------------------------------------------------------------- per-camera exposure compensation
     def enable_exposure_compensation(self, lr: float, start: int = 0) -> None:
@@ -947,6 +994,8 @@ class Trainer:
             if n_samples == 0:
                 if ctx_future is not None:
                     torch.cuda.current_stream(self.device).wait_event(ctx_future.result()[2])
+                if self.error_map is not None:
+                    self._error_map_step(step, data, None)      # nothing to observe; a rebuild that is due is still made
                 return None
             if c.target_sample_batch_size > 0:
                 self.dataset.update_num_rays(int(len(pixels) * (c.target_sample_batch_size / float(n_samples))))
@@ -960,13 +1009,23 @@ class Trainer:
             else:
                 rgb = self.exposure(rgb, data["camera_ids"], acc, data["color_bkgd"],
                                     gain_background=not self._exposure_foreground)
-        mse = F.mse_loss(rgb, pixels)
+        if self.error_map is not None and "ray_weight" in data:
+            # error-map sampling: every ray's squared error over its sampling density, so that the gradient's expectation is
+            # the uniform draw's; the per-ray errors go into the map, and their mean — the unweighted mse — keeps feeding
+            # the statistics (and the verdict), so that a logged PSNR means what it meant
+            from .error_map import weighted_mse
+            ray_mse, err = weighted_mse(rgb, pixels, data["ray_weight"])
+            mse = err.mean()
+            self._error_map_step(step, data, err)
+        else:
+            ray_mse = mse = F.mse_loss(rgb, pixels)
         # what is back-propagated wherever the mse was: the mse alone, or + the distortion regulariser (this rank's mean over
-        # its rays, like the mse; rays without samples count as 0).  The mse itself keeps feeding the statistics
-        ray_loss, distortion = mse, None
+        # its rays, like the mse; rays without samples count as 0; not weighted by the error map).  The mse itself keeps
+        # feeding the statistics
+        ray_loss, distortion = ray_mse, None
         if c.distortion_weight > 0:
             distortion = self._distortion(extra, len(pixels))
-            ray_loss = mse + c.distortion_weight * distortion
+            ray_loss = ray_mse + c.distortion_weight * distortion
         range_guard = (ff._buffers["guard"], self.field._guard_seen, ff._pack_id) if guard_live else None
         if self.bucket is None:
             bpp, mb, table_pieces = self._backward_single(step, ray_loss, ctx_future, tables_fused)
@@ -999,6 +1058,18 @@ class Trainer:
         if distortion is not None:
             stats["distortion"] = dist_f[0]
         return stats
+
+    def _error_map_step(self, step: int, data, err) -> None:
+        """Step `step`'s share of the error map, on the main stream right behind the loss forward: its rays' errors into the
+        map, then — where (step + 1) % refresh_every == 0 — the CDF rebuilt from the map that includes them.  Both are
+        enqueued before the next batch is drawn, whether `_prefetch` draws it during this step's backward (its stream waits
+        for the rebuild's event, `ErrorMapSampler.draw`) or `fetch()` at the top of the next step: one sequence of batches."""
+        em = self.error_map
+        if err is not None and "ray_weight" in data:
+            px, py = data["pixel_xy"]
+            em.observe(data["camera_ids"], px, py, err)
+        if (step + 1) % em.refresh_every == 0:
+            em.refresh()
 
     @staticmethod
     def _distortion(extra, num_rays: int):
@@ -1178,7 +1249,8 @@ class Trainer:
                     f"n_rendering_samples={s['n_rendering_samples']} | num_rays={s['num_rays']} | "
                     f"bits_per_param={s['bpp']:.3f} | embed_bits_MB={s['embed_bits_MB']:.3f}"
                     + (f" | skipped={self.step_guard.stats()['skipped']}" if self.step_guard is not None else "")
-                    + (f" | mean_abs_log_gain={self.exposure.mean_magnitude():.3e}" if self.exposure is not None else ""))
+                    + (f" | mean_abs_log_gain={self.exposure.mean_magnitude():.3e}" if self.exposure is not None else "")
+                    + (f" | errmap_cover={self.error_map.effective_fraction():.3f}" if self.error_map is not None else ""))
         if self.exposure is not None and self.rank == 0:
             path = self.write_exposures()
             if log:

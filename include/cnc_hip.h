@@ -880,6 +880,63 @@ int cnc_exposure_backward(const float* g_out, const float* rgb, const float* opa
                           uint64_t workspace_bytes, float* g_rgb, float* g_opacity /* nullable */, float* g_gain /* nullable */,
                           float* g_log_gain /* nullable */, void* stream);
 
+/* (ABI v33, added entries: no signature changed) Error-map pixel sampling (csrc/error_map.hip): a coarse
+ * per-image map of recent loss, training pixels drawn in proportion to it, and a loss that divides every ray by its
+ * sampling density.  State: map f32 [n_cams, G, G], G = `resolution` in [1, 64], n_cams G G <= 2^19 cells.  Cell (gy, gx)
+ * of a camera covers the pixel rows [gy H / G, (gy + 1) H / G) and the columns [gx W / G, (gx + 1) W / G), integer
+ * division; H and W need not be multiples of G, a cell may be empty (G > H), and a_cell is its pixel count.  Pixel row y
+ * lies in gy = ((y + 1) G - 1) / H.  Cells are numbered (k G + gy) G + gx.  n <= 2^31 - 1 rays; CNC_ERR_INVALID_VALUE
+ * otherwise, for a null pointer and for an array that is not aligned to its element.  Everything is float32 with nothing
+ * fused, in the order written here; there are no float atomics and no launch caps its grid: equal inputs give equal bits.
+ *
+ * cnc_errmap_loss_forward: rgb, pixels f32 [n, 3], weight f32 [n] (w), n >= 1 ->
+ *     d_c = rgb[i, c] - pixels[i, c] ;  sq_i = (d_0 d_0 + d_1 d_1) + d_2 d_2 ;  err[i] = sq_i / 3 ;  t_i = w_i sq_i
+ *     Rays are cut into blocks of 256 consecutive rays (t = +0 behind the last ray).  Per block p[j] = p[j] + p[j + s]
+ *     for j < s, s = 128, 64, .., 1 -> the block's partial p[0].  Then q[j] = the partials j, j + 256, j + 512, .. added
+ *     in that order from +0, the same tree over q, and loss[0] = q[0] / (float)(3 n).
+ *     workspace: cnc_errmap_loss_workspace(n) bytes, 4-byte aligned, owned by the call until it has run.
+ * cnc_errmap_loss_backward: g_loss f32 [1] on the device (g) ->  c_i = ((g 2) w_i) / (float)(3 n) ;  g_rgb[i, c] = c_i d_c.
+ *     There is no gradient with respect to pixels or weight.
+ *
+ * cnc_errmap_keys: cam_ids, px, py i64 [n], each clamped into its range as cnc_camera_rays clamps them -> keys i32 [n],
+ *     the ray's cell.
+ * cnc_errmap_update: the caller groups the rays by key with a STABLE sort, so that the segment
+ *     order[offsets[c] .. offsets[c + 1]) (i64 both; offsets [cells + 1]) lists cell c's rays in ascending ray index.
+ *     One wave per cell: lane l adds err of the segment's elements l, l + 64, .. in that order from +0, an element whose
+ *     err is not finite adding +0 and not counting; then p[l] = p[l] + p[l + o] for o = 32, 16, .., 1 (the counts likewise,
+ *     as integers).  count > 0:  mean = p[0] / (float)count ;  map[c] = decay map[c] + (1 - decay) mean.
+ *     count == 0: map[c] is not written.  Segments are cut to [0, n) and list entries outside it are skipped.  n == 0
+ *     succeeds and launches nothing.
+ *
+ * cnc_errmap_cdf: map -> prob f32 [cells] and cdf f32 [cells], with u = uniform_floor in [0, 1], N = (float)(n_cams H W):
+ *     mm_c = map[c] > 0 ? map[c] : 0 (a NaN counts as 0) ;  t_c = mm_c (float)a_c
+ *     Cells are cut into chunks of 64 consecutive cells.  S = the chunks' sums of t (each in cell order from +0) added in
+ *     chunk order from +0.  S > 0 and finite:  prob[c] = ((1 - u) t_c) / S + (u (float)a_c) / N ;  otherwise the uniform
+ *     distribution prob[c] = (float)a_c / N.  Then P_0 = +0, P_(k+1) = P_k + (chunk k's sum of prob in cell order from
+ *     +0), and cdf[c] = P_chunk(c) + (the chunk's running sum of prob through c) — monotone, and equal to its predecessor
+ *     exactly where prob[c] == 0 — except that cdf[c] = 1 exactly for every c from the last cell with a_c > 0 on.
+ *
+ * cnc_errmap_sample: rand f32 [n, 3] in [0, 1), the two arrays above -> cam_ids, px, py i64 [n] (what cnc_camera_rays
+ *     takes) and weight f32 [n].  cell = the first c with cdf[c] > rand[i, 0] by binary search, the last cell if there is
+ *     none; (k, gy, gx) from it; px = gx W / G + min((int)(rand[i, 1] (float)w_c), w_c - 1), py likewise from rand[i, 2]
+ *     and the cell's height (a product that is not >= 0 gives the first pixel), both clamped into the image;
+ *     inv = 1 / N ;  pp = prob[cell] / (float)a_cell ;  weight[i] = pp > 0 ? inv / pp : 0     [= (1 / N_pix) / p(pixel)]
+ *     No load leaves cdf or prob whatever rand holds.                                                                 */
+uint64_t cnc_errmap_loss_workspace(int64_t n);
+int cnc_errmap_loss_forward(const float* rgb, const float* pixels, const float* weight, int64_t n, void* workspace,
+                            uint64_t workspace_bytes, float* loss, float* err, void* stream);
+int cnc_errmap_loss_backward(const float* g_loss, const float* rgb, const float* pixels, const float* weight, int64_t n,
+                             float* g_rgb, void* stream);
+int cnc_errmap_keys(const int64_t* cam_ids, const int64_t* px, const int64_t* py, int64_t n, int32_t n_cams, int32_t height,
+                    int32_t width, int32_t resolution, int32_t* keys, void* stream);
+int cnc_errmap_update(const int64_t* order, const int64_t* offsets, const float* err, int64_t n, int32_t n_cams,
+                      int32_t resolution, float decay, float* map, void* stream);
+int cnc_errmap_cdf(const float* map, int32_t n_cams, int32_t height, int32_t width, int32_t resolution, float uniform_floor,
+                   float* prob, float* cdf, void* stream);
+int cnc_errmap_sample(const float* rand, const float* cdf, const float* prob, int64_t n, int32_t n_cams, int32_t height,
+                      int32_t width, int32_t resolution, int64_t* cam_ids, int64_t* px, int64_t* py, float* weight,
+                      void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Context-model heads and the Bernoulli rate  —  replace the ATen chains of examples/utils_bpp_acc.py
  * (context MLPs :378-393 applied at :561-566 / :689-692, hash fusion :567-572 / :693-701,
