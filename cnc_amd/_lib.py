@@ -183,6 +183,9 @@ SIGNATURES = {
     "cnc_pack_bounds": [_vp, _i64, _vp, _vp, _i64, _vp],
     "cnc_distortion_forward": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _u32, _vp],
     "cnc_distortion_backward": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "cnc_depth_loss_forward": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _u32, _vp],
+    "cnc_depth_loss_backward": [_vp, _vp, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _u32, _vp],
+    "cnc_depth_fetch": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "cnc_lens_undistort": [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _i64, _vp],
     "cnc_lens_undistort_fisheye": [_vp, _vp, _i64, _f32, _i32, _vp, _i64, _vp],
     "cnc_camera_rays": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],

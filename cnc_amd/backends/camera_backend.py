@@ -67,6 +67,40 @@ def camera_rays(cams, model, opengl, cam_ids=None, px=None, py=None, *, cam0=0, 
     return origins, viewdirs, pixels
 
 
+def depth_fetch(planes, cams, opengl, euclidean, cam_ids, px, py, viewdirs):
+    """-> float32 [n]: the measured distance along each ray (cnc_depth_fetch), 0 = no measurement.  planes f32
+    [n_cams, H, W]; cam_ids, px, py int64 [n]; viewdirs f32 [n, 3], what `camera_rays` returned for the same list."""
+    for name, t, dtype in (("planes", planes, torch.float32), ("cams", cams, torch.float32), ("cam_ids", cam_ids, torch.int64),
+                           ("px", px, torch.int64), ("py", py, torch.int64), ("viewdirs", viewdirs, torch.float32)):
+        check_input(t, name)
+        if t.dtype != dtype:
+            raise RuntimeError(f"depth_fetch: {name} must be {dtype}")
+    n = cam_ids.shape[0]
+    if planes.dim() != 3 or cams.dim() != 2 or cams.shape[1] != _lib.CNC_CAMERA_ROW or planes.shape[0] != cams.shape[0]:
+        raise RuntimeError(f"depth_fetch: planes must be [n_cams, H, W] next to cams [n_cams, {_lib.CNC_CAMERA_ROW}]")
+    if cam_ids.dim() != 1 or px.shape != cam_ids.shape or py.shape != cam_ids.shape or tuple(viewdirs.shape) != (n, 3):
+        raise RuntimeError("depth_fetch: cam_ids, px, py must be [n] and viewdirs [n, 3]")
+    depth = torch.empty((n,), dtype=torch.float32, device=planes.device)
+    check(_lib.lib().cnc_depth_fetch(ptr(planes), ptr(cams), planes.shape[0], planes.shape[1], planes.shape[2],
+                                     int(bool(opengl)), int(bool(euclidean)), ptr(cam_ids), ptr(px), ptr(py), ptr(viewdirs),
+                                     n, ptr(depth), stream(planes.device)), "depth_fetch")
+    return depth
+
+
+def depth_fetch_torch(planes, cams, opengl, euclidean, cam_ids, px, py, viewdirs):
+    """The same in torch ops, for loaders on a host device."""
+    z = planes[cam_ids, py, px]
+    if euclidean:
+        t, c = z, torch.ones_like(z)
+    else:
+        row = cams[cam_ids]
+        c = (viewdirs[:, 0] * row[:, 6] + viewdirs[:, 1] * row[:, 10]) + viewdirs[:, 2] * row[:, 14]
+        c = -c if opengl else c
+        t = z / c
+    ok = torch.isfinite(z) & (z > 0) & (c > 0)
+    return torch.where(ok, t, torch.zeros_like(t))
+
+
 def camera_rays_torch(cams, model, opengl, cam_ids, px, py, images=None, bkgd=None, eps=1e-6, iters=10):
     """The same in torch ops, for loaders on a host device (parsing and geometry testable without a GPU)."""
     from ..nerfacc import cameras

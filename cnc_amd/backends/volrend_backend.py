@@ -161,6 +161,41 @@ def distortion_backward(starts, counts, t_starts, t_ends, weights, grad_loss):
     return g_w
 
 
+def _depth_target(target, lead):
+    _f32(target, "target")
+    if tuple(target.shape) != lead:
+        raise RuntimeError(f"target must have shape {lead}")
+    return target
+
+
+def depth_loss_forward(starts, counts, t_starts, t_ends, weights, target, spread):
+    """The depth loss per ray and its S1 (cnc_depth_loss_forward) -> (loss, s1), each shaped like `distortion_forward`'s
+    result; `target` has that shape too."""
+    n_rays, row_len, lead = _distortion_layout(starts, counts, t_starts, t_ends, weights)
+    _depth_target(target, lead)
+    loss = torch.empty(lead, dtype=torch.float32, device=weights.device)
+    s1 = torch.empty(lead, dtype=torch.float32, device=weights.device)
+    check(_lib.lib().cnc_depth_loss_forward(ptr(starts), ptr(counts), row_len, _p(t_starts), _p(t_ends), _p(weights),
+                                            _p(target), float(spread), _p(loss), _p(s1), n_rays, stream(weights.device)),
+          "depth_loss_forward")
+    return loss, s1
+
+
+def depth_loss_backward(starts, counts, t_starts, t_ends, weights, target, spread, s1, grad_loss):
+    """dL/dweights (the shape of `weights`, which is not read: the gradient does not depend on it beyond `s1`) from dL/dloss
+    per ray and the forward's `s1` (cnc_depth_loss_backward); t and target are constants."""
+    n_rays, row_len, lead = _distortion_layout(starts, counts, t_starts, t_ends, weights)
+    _depth_target(target, lead)
+    _f32(grad_loss, "grad_loss"), _f32(s1, "s1")
+    if tuple(grad_loss.shape) != lead or tuple(s1.shape) != lead:
+        raise RuntimeError(f"grad_loss and s1 must have shape {lead}")
+    g_w = torch.empty_like(weights)
+    check(_lib.lib().cnc_depth_loss_backward(ptr(starts), ptr(counts), row_len, _p(t_starts), _p(t_ends), _p(target),
+                                             float(spread), _p(s1), _p(grad_loss), _p(g_w), n_rays, stream(weights.device)),
+          "depth_loss_backward")
+    return g_w
+
+
 def render_visibility(starts, counts, values, t_starts=None, t_ends=None, *, from_alpha=False,
                       early_stop_eps=1e-4, alpha_thre=0.0, alpha_thre_cap=None, want_kept=True):
     """(mask uint8 [N], kept int64 [n_rays] or None)."""

@@ -186,7 +186,10 @@ class TransformsLoader(_PosedImages):
     there is no `fl_x`; `frames[].file_path` (looked up with and without an extension) and `frames[].transform_matrix`
     (camera-to-world, OpenGL convention); an optional top-level `aabb` (six numbers) exposed as `.aabb` / `.scene_bbox`.
     OPENCV reads k1 k2 p1 p2 k3 (rational-radial + tangential), OPENCV_FISHEYE k1..k4.  All images must have one size; an
-    image without alpha is opaque.
+    image without alpha is opaque.  Measured depth, read only under `with_depth`: `frames[].depth_file_path` (a 16-bit PNG or
+    a `.npy` float array of the images' size), the top-level `depth_unit_scale_factor` (nerfstudio; default 0.001) or
+    `integer_depth_scale` (instant-ngp) that takes an integer file to scene units, and `is_euclidean_depth` (default false:
+    z-depth along the optical axis, converted to the distance along each ray by cnc_depth_fetch).
 
     The cameras go into one table on the device (backends/camera_backend.py); a training batch is the base class's three
     `randint` draws, the background, and ONE launch of cnc_camera_rays with the pixel fetch; a view is one launch in its
@@ -204,6 +207,10 @@ class TransformsLoader(_PosedImages):
     # generator, takes the place of the three `randint` draws of a training batch; the batch then also holds "camera_ids",
     # "pixel_xy" = (px, py) and "ray_weight" f32 [num_rays].  None: the draws and the batch dict are what they always were
     sampler = None
+    # set (on the instance) by depth supervision, before the first draw: a training batch also holds "depth" f32 [num_rays],
+    # the measured distance ALONG each ray in scene units, 0 = no measurement (`depth_planes`: the frames'
+    # `depth_file_path`, read at the first use).  Off: nothing is read and the batch dict is what it always was
+    with_depth = False
 
     def __init__(self, subject_id: str, root_fp: str, split: str, color_bkgd_aug: str = "white",
                  num_rays: int = None, near: float = None, far: float = None,
@@ -266,6 +273,15 @@ class TransformsLoader(_PosedImages):
         self.camera_model = models.pop()
         self.model = camera_backend.MODELS[self.camera_model]
         self.HEIGHT, self.WIDTH = images[0].shape[:2]
+        # measured depth (read by `depth_planes`, and only when asked for): a file per frame or None, the factor that takes an
+        # integer file's counts to scene units, and whether the values are distances along the ray or along the optical axis
+        self._scene_dir, self._depth_planes = scene_dir, None
+        self.depth_files = [fr.get("depth_file_path") for fr in frames]
+        if meta.get("depth_unit_scale_factor") is not None:
+            self.depth_scale = float(meta["depth_unit_scale_factor"])
+        else:
+            self.depth_scale = float(meta.get("integer_depth_scale", 0.001))
+        self.is_euclidean_depth = bool(meta.get("is_euclidean_depth", False))
         self.images = torch.from_numpy(np.stack(images)).to(device)
         poses = np.asarray([fr["transform_matrix"] for fr in frames], dtype=np.float32)
         self.camtoworlds = torch.from_numpy(poses).to(device)
@@ -291,6 +307,41 @@ class TransformsLoader(_PosedImages):
             if os.path.isfile(file):
                 return file
         raise FileNotFoundError(f"{os.path.join(scene_dir, file_path)}: no such image (with or without an extension)")
+
+    def depth_planes(self):
+        """float32 [n_cams, H, W] on the images' device: every frame's `depth_file_path` in scene units, read once — a
+        16-bit PNG (or any integer image / array: times `depth_scale`) or a `.npy` float array (as it is); an all-zero plane,
+        no measurement, for a frame without one.  ValueError: a file of another size than the images, or no file at all."""
+        if self._depth_planes is not None:
+            return self._depth_planes
+        if not any(self.depth_files):
+            raise ValueError(f"{self.transforms_path}: depth was asked for, but no frame of split '{self.split}' has a "
+                             "depth_file_path")
+        planes = np.zeros((len(self.depth_files), self.HEIGHT, self.WIDTH), np.float32)
+        for k, name in enumerate(self.depth_files):
+            if not name:
+                continue
+            file = os.path.join(self._scene_dir, name)
+            if file.endswith(".npy"):
+                raw = np.load(file)
+            else:
+                from PIL import Image
+                with Image.open(file) as img:
+                    raw = np.asarray(img)
+            if raw.shape != (self.HEIGHT, self.WIDTH):
+                raise ValueError(f"{file}: depth is {' x '.join(str(s) for s in raw.shape[::-1])}, the images are "
+                                 f"{self.WIDTH} x {self.HEIGHT}")
+            integer = np.issubdtype(raw.dtype, np.integer)
+            planes[k] = raw.astype(np.float32) * np.float32(self.depth_scale) if integer else raw.astype(np.float32)
+        self._depth_planes = torch.from_numpy(planes).to(self.images.device)
+        return self._depth_planes
+
+    def _fetch_depth(self, ids, x, y, dirs):
+        from .backends import camera_backend
+        planes = self.depth_planes()
+        fetch = camera_backend.depth_fetch if planes.is_cuda else camera_backend.depth_fetch_torch
+        return fetch(planes, self.cameras, self.OPENGL_CAMERA, self.is_euclidean_depth, ids.expand(x.shape[0]).contiguous(),
+                     x, y, dirs)
 
     @torch.no_grad()
     def __getitem__(self, index):
@@ -322,6 +373,8 @@ class TransformsLoader(_PosedImages):
             out["camera_ids"] = ids
         if weight is not None:
             out["camera_ids"], out["pixel_xy"], out["ray_weight"] = ids, (x, y), weight
+        if self.with_depth and self.training:
+            out["depth"] = self._fetch_depth(ids, x, y, d)          # one launch behind the rays', on the same stream
         return out
 
 
@@ -333,6 +386,9 @@ class SyntheticBallDataset:
 
     RADIUS = 0.8
     has_alpha = True         # pixels a ray misses the ball with are transparent, blended with the batch's colour (`fetch`)
+    # set (on the instance) by depth supervision: `fetch()` also returns "depth" f32 [n], the analytic distance along each ray
+    # to the ball, 0 where it misses.  Off: the batch dict and the draws are what they always were (no draw is added either way)
+    with_depth = False
 
     def __init__(self, image_size=200, n_train_views=100, device="cuda", seed=0):
         self.H = self.W = image_size
@@ -399,6 +455,23 @@ class SyntheticBallDataset:
             self._images = torch.stack(views)
         return self._images
 
+    def _train_depth(self):
+        """The training views' exact depth [n, H, W], computed once: the distance along each pixel's ray to the first hit
+        of the ball (Euclidean depth), 0 — no measurement — where the ray misses it."""
+        if getattr(self, "_depth", None) is None:
+            ys, xs = torch.meshgrid(torch.arange(self.H, device=self.device),
+                                    torch.arange(self.W, device=self.device), indexing="ij")
+            x, y = xs.reshape(-1).float(), ys.reshape(-1).float()
+            views = []
+            for c2w in self.train_c2w:
+                o, d = self._rays(c2w[None].expand(x.shape[0], 3, 4), x, y)
+                b = (o * d).sum(-1)
+                disc = b * b - ((o * o).sum(-1) - self.RADIUS ** 2)
+                t = -b - torch.sqrt(disc.clamp_min(0))
+                views.append(torch.where(disc > 0, t, torch.zeros_like(t)).view(self.H, self.W))
+            self._depth = torch.stack(views)
+        return self._depth
+
     def fetch(self, num_rays=None):
         n = self.num_rays if num_rays is None else num_rays
         img = torch.randint(0, self.train_c2w.shape[0], (n,), device=self.device, generator=self.gen)
@@ -408,7 +481,10 @@ class SyntheticBallDataset:
         rgba = self._train_images()[img, yi, xi]            # the same numbers as shading the fetched rays
         rgb, alpha = rgba[:, :3], rgba[:, 3:]
         bkgd = torch.rand(3, device=self.device, generator=self.gen)     # random bkgd in training
-        return {"rays": Rays(o, d), "pixels": rgb * alpha + bkgd * (1 - alpha), "color_bkgd": bkgd}
+        out = {"rays": Rays(o, d), "pixels": rgb * alpha + bkgd * (1 - alpha), "color_bkgd": bkgd}
+        if self.with_depth:
+            out["depth"] = self._train_depth()[img, yi, xi]
+        return out
 
     def view(self, i):
         ys, xs = torch.meshgrid(torch.arange(self.H, device=self.device),

@@ -19,7 +19,8 @@ container that holds the map, and --prune-floaters N (+ --prune-connectivity): t
 components cleared once, after training and before the first evaluation, and --mesh-min-component N:
 the same for the lattice a --save-mesh mesh is cut from, and --refine-exposure LR (+ --refine-exposure-from STEP): one
 log-gain per training camera and colour channel learned next to the field, written to
-<out_dir>/exposures.json.
+<out_dir>/exposures.json, and --depth-weight W (+ --depth-spread K): depth supervision against a capture's measured
+depth, or the procedural scene's exact one.
 """
 from __future__ import annotations
 
@@ -98,6 +99,13 @@ def build_parser():
     ap.add_argument("--distortion-weight", dest="distortion_weight", type=float, default=0.0,
                     help="weight of mip-NeRF 360's interval-distortion loss on the rendered samples, added to the ray loss "
                          "(mean over the batch's rays; DESIGN.md §4.10); 0 = off")
+    ap.add_argument("--depth-weight", dest="depth_weight", type=float, default=0.0, metavar="W",
+                    help="weight of depth supervision, added to the ray loss: the batch mean of (sum w e)^2 + K sum w e^2 over "
+                         "the rendered samples, e = a sample's distance from the ray's measured depth (DESIGN.md §4.19).  "
+                         "--dataset transforms with a depth_file_path per frame, or --dataset procedural; one process; "
+                         "0 = off.  UNTUNED: nobody has run this on a real capture here")
+    ap.add_argument("--depth-spread", dest="depth_spread", type=float, default=1.0, metavar="K",
+                    help="--depth-weight: the weight K of the line-of-sight term sum w e^2 inside the depth loss; >= 0")
     ap.add_argument("--save-mesh", dest="save_mesh", type=str, default=None, metavar="PATH",
                     help="at the very end, write the scene's surface as a binary PLY: marching tetrahedra on the density of "
                          "the model a receiver would hold (decoded tables, 13-bit MLP; DESIGN.md §4.13); default: off")
@@ -181,6 +189,7 @@ def make_config_and_data(args, device, rank=0, world=1):
               occupancy_coder=getattr(args, "occupancy_coder", "iid"),
               mlp_coder=getattr(args, "mlp_coder", "packed"),
               distortion_weight=float(getattr(args, "distortion_weight", 0.0)),
+              depth_weight=float(getattr(args, "depth_weight", 0.0)), depth_spread=float(getattr(args, "depth_spread", 1.0)),
               save_mesh=getattr(args, "save_mesh", None), mesh_resolution=int(getattr(args, "mesh_resolution", 256)),
               mesh_threshold=getattr(args, "mesh_threshold", None),
               pose_lr=float(getattr(args, "refine_poses", 0.0)), pose_refine_from=int(getattr(args, "refine_poses_from", 0)),

@@ -139,6 +139,13 @@ class TrainConfig:
     error_map_uniform_floor: float = 0.5
     error_map_decay: float = 0.9
     error_map_refresh_every: int = 16
+    # depth supervision (cnc_amd.nerfacc.losses.depth_loss): the ray loss gains this weight times the mean over
+    # the batch's rays of (sum w e)^2 + depth_spread sum w e^2, e = a sample's distance from the ray's measured depth; rays
+    # without a measurement count as 0.  0 = off: no batch key, launch, log field or byte differs, and depth_spread is not
+    # read.  Also CNC_DEPTH_WEIGHT.  A capture through `TransformsLoader` whose frames name depth files, or the procedural
+    # scene; one process.  UNTUNED: nobody has run this on a real capture here
+    depth_weight: float = 0.0
+    depth_spread: float = 1.0
 
 
 def quantize_params(state: Dict[str, torch.Tensor], digits=13):
@@ -273,6 +280,9 @@ class Trainer:
                                  "map's gradient would need a collective of its own")
             if not (c.envmap_lr > 0):
                 raise ValueError("the environment-map background: envmap_lr must be positive")
+        depth_weight = float(getattr(c, "depth_weight", 0.0)) or float(os.environ.get("CNC_DEPTH_WEIGHT", "0") or 0.0)
+        if depth_weight != 0 and self.dp:
+            raise ValueError("depth supervision is not built for data-parallel training (world > 1)")
         if int(getattr(c, "prune_floaters", 0)) < 0 or getattr(c, "prune_connectivity", 26) not in (6, 14, 26):
             raise ValueError("floater pruning: prune_floaters must not be negative and prune_connectivity must be 6, 14 or 26")
         # ---- models and dataset
@@ -382,6 +392,35 @@ class Trainer:
                                            float(getattr(c, "error_map_uniform_floor", 0.5)),
                                            float(getattr(c, "error_map_decay", 0.9)),
                                            int(getattr(c, "error_map_refresh_every", 16)))
+        # ---- depth supervision: nothing unless asked for
+        self._depth_weight = 0.0
+        self.on_depth_loss = None
+        if depth_weight != 0:
+            self.enable_depth_supervision(depth_weight)
+
+    # -------------------------------------------------------------------------------- depth supervision
+    def enable_depth_supervision(self, weight: float) -> None:
+        """From the next batch drawn on, the dataset also hands out every ray's measured distance ("depth", 0 = none) and the
+        ray loss gains `weight` times the batch mean of `depth_loss` on the rendered samples, with
+        `cfg.depth_spread` read at every step.  `on_depth_loss`, when set, is called with (extras, target, per-ray loss)
+        right after the loss is formed (diagnostics).  ValueError where that cannot work: data parallel, a weight that is
+        not positive, or a dataset that has no depth to give — anything but the procedural scene or a `LoaderDataset` over a
+        `TransformsLoader` whose frames name depth files."""
+        from .datasets import TransformsLoader
+        if self.dp:
+            raise ValueError("depth supervision is not built for data-parallel training (world > 1)")
+        if not (weight > 0) or not (float(getattr(self.cfg, "depth_spread", 1.0)) >= 0):
+            raise ValueError("depth supervision: depth_weight must be positive and depth_spread must not be negative")
+        loader = getattr(self.dataset, "train", None)
+        if isinstance(self.dataset, SyntheticBallDataset):
+            self.dataset.with_depth = True
+        elif isinstance(self.dataset, LoaderDataset) and isinstance(loader, TransformsLoader):
+            loader.depth_planes()              # read now: a capture without depth files, or one of another size, fails HERE
+            loader.with_depth = True
+        else:
+            raise ValueError("depth supervision needs a dataset with measured depth: a LoaderDataset over a TransformsLoader "
+                             "whose frames name a depth_file_path (--dataset transforms), or the procedural scene")
+        self._depth_weight = float(weight)
 
     # -------------------------------------------------------------------------------- error-map pixel sampling
     def enable_error_map_sampling(self, resolution: int = 16, uniform_floor: float = 0.5, decay: float = 0.9,
@@ -968,6 +1007,8 @@ class Trainer:
         gained = self.exposure is not None and step >= self._exposure_from and "camera_ids" in data
         if gained and self.envmap is None:
             bkgd = None
+        # depth supervision reads the samples' weights (a batch drawn before it was enabled has no depth)
+        depth_on = self._depth_weight > 0 and "depth" in data
         # (`background=`: the learned background, when there is one, takes the place of the batch's colour; None = as ever)
         with _gradsink.activate(self.sink_render):
             if refine:
@@ -979,7 +1020,7 @@ class Trainer:
                 rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
                     self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
                     render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
-                    with_samples=c.distortion_weight > 0, background=self.envmap)
+                    with_samples=c.distortion_weight > 0 or depth_on, background=self.envmap)
         self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event()
         # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
         # fused one is asked before the poll below can switch it off)
@@ -1026,6 +1067,11 @@ class Trainer:
         if c.distortion_weight > 0:
             distortion = self._distortion(extra, len(pixels))
             ray_loss = ray_mse + c.distortion_weight * distortion
+        # ... + the depth term, by the same conventions (rays without a measurement count as 0 too)
+        depth_term = None
+        if depth_on:
+            depth_term = self._depth_loss(extra, data["depth"], len(pixels))
+            ray_loss = ray_loss + self._depth_weight * depth_term
         range_guard = (ff._buffers["guard"], self.field._guard_seen, ff._pack_id) if guard_live else None
         if self.bucket is None:
             bpp, mb, table_pieces = self._backward_single(step, ray_loss, ctx_future, tables_fused)
@@ -1036,7 +1082,7 @@ class Trainer:
         if gained:
             gained = self._exposure_gradient()
         if sg is not None:
-            self._verdict(mse, bpp, range_guard, tables_fused, distortion, pose=refine, exposure=gained)
+            self._verdict(mse, bpp, range_guard, tables_fused, distortion, pose=refine, exposure=gained, depth=depth_term)
         self._update(step, table_pieces, tables_fused)
         if refine:
             self._pose_update()
@@ -1052,11 +1098,15 @@ class Trainer:
                    torch.as_tensor(mb, device=mse.device).detach().float()]
         if distortion is not None:
             scalars.append(distortion.detach())
+        if depth_term is not None:
+            scalars.append(depth_term.detach())
         mse_f, bpp_f, mb_f, *dist_f = torch.stack(scalars).tolist()
         stats = {"mse": mse_f, "psnr": -10.0 * math.log10(max(mse_f, 1e-12)), "bpp": bpp_f,
                  "embed_bits_MB": mb_f, "n_rendering_samples": n_samples, "num_rays": len(pixels)}
         if distortion is not None:
             stats["distortion"] = dist_f[0]
+        if depth_term is not None:
+            stats["depth"] = dist_f[-1]
         return stats
 
     def _error_map_step(self, step: int, data, err) -> None:
@@ -1078,6 +1128,17 @@ class Trainer:
         from .nerfacc.losses import distortion
         per_ray = distortion(extra["weights"], extra["t_starts"], extra["t_ends"], ray_indices=extra["ray_indices"],
                              n_rays=num_rays, packed_info=extra["packed_info"])
+        return per_ray.sum() / float(max(num_rays, 1))
+
+    def _depth_loss(self, extra, target, num_rays: int):
+        """Mean over the batch's rays of the depth loss on the samples the render just composited: one kernel, and one more
+        behind the render backward's root."""
+        from .nerfacc.losses import depth_loss
+        per_ray = depth_loss(extra["weights"], extra["t_starts"], extra["t_ends"], target.reshape(-1).float(),
+                             ray_indices=extra["ray_indices"], n_rays=num_rays, packed_info=extra["packed_info"],
+                             spread=float(self.cfg.depth_spread))
+        if self.on_depth_loss is not None:
+            self.on_depth_loss(extra, target, per_ray)
         return per_ray.sum() / float(max(num_rays, 1))
 
     def _backward_single(self, step, ray_loss, ctx_future, tables_fused):
@@ -1177,7 +1238,7 @@ class Trainer:
         A.bind(force=True)
         return bpp, mb, table_pieces
 
-    def _verdict(self, mse, bpp, range_guard, tables_fused, distortion=None, pose=False, exposure=False) -> None:
+    def _verdict(self, mse, bpp, range_guard, tables_fused, distortion=None, pose=False, exposure=False, depth=None) -> None:
         """The guarded step's verdict, on the device and before any update."""
         # Scanned: every gradient the two library optimizers will read (the tables' pieces are not: DESIGN.md §13) and the
         # loss scalars; data parallel: what every rank holds alike — the bucket's summed non-table runs with the entropy
@@ -1186,7 +1247,7 @@ class Trainer:
         if A is None:
             scan = [p.grad for o in (self.opt, self.opt2) for g in o.param_groups for p in g["params"]
                     if p.grad is not None and id(p) not in self._table_ids]
-            scan += [t.detach().reshape(-1) for t in (mse, bpp, distortion)
+            scan += [t.detach().reshape(-1) for t in (mse, bpp, distortion, depth)
                      if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
             if pose:                            # the pose gradient joins the scan, the poses' Adam takes the same word
                 scan.append(self.pose_refiner.delta.grad.reshape(-1))
@@ -1249,6 +1310,7 @@ class Trainer:
                     f"n_rendering_samples={s['n_rendering_samples']} | num_rays={s['num_rays']} | "
                     f"bits_per_param={s['bpp']:.3f} | embed_bits_MB={s['embed_bits_MB']:.3f}"
                     + (f" | skipped={self.step_guard.stats()['skipped']}" if self.step_guard is not None else "")
+                    + (f" | depth={s['depth']:.3e}" if "depth" in s else "")
                     + (f" | mean_abs_log_gain={self.exposure.mean_magnitude():.3e}" if self.exposure is not None else "")
                     + (f" | errmap_cover={self.error_map.effective_fraction():.3f}" if self.error_map is not None else ""))
         if self.exposure is not None and self.rank == 0:

@@ -698,6 +698,39 @@ int cnc_distortion_backward(const int64_t* chunk_starts, const int64_t* chunk_cn
                             const float* t_starts, const float* t_ends, const float* weights,
                             const float* grad_loss /* [n_rays] */, float* grad_weights, uint32_t n_rays, void* stream);
 
+/* (ABI v33, added entries: no signature changed) Depth supervision per ray (csrc/depth_loss.hip; the reference
+ * has no such term).  With target[ray] = D, the measured distance along the ray in scene units:
+ *   e_i = 0.5 ((t_start_i - D) + (t_end_i - D)),   S1 = sum_i w_i e_i,   S2 = sum_i w_i e_i^2
+ *   loss[ray] = S1^2 + spread S2,     dloss/dw_i = 2 S1 e_i + spread e_i^2          (spread >= 0)
+ * e_i is formed per sample as written (never sum w m - D sum w, which cancels on a thin surface far from the origin).  The
+ * sums: the products of each tile of 32 consecutive samples through a butterfly (lane j adds lane j ^ 16, 8, 4, 2, 1), the
+ * tiles' sums added to the ray's running sum in sample order from +0.  Per sample: a = w e ; b = a e ; then
+ * loss = S1 S1 + spread S2 and grad_weights[s] = grad_loss[ray] ((2 S1) e + spread (e e)).
+ * The sample layouts are cnc_distortion_forward's (packed through chunk_starts / chunk_cnts, or both NULL and row_len).
+ * A target that is not finite or is <= 0 means "no measurement": loss[ray] = s1[ray] = +0 exactly, none of the ray's
+ * samples is read, and every one of them gets grad_weights = +0 exactly, whatever grad_loss[ray] holds (a NaN included).
+ * loss and s1 are written for every ray (a ray without samples: 0); the backward takes the forward's s1 and writes
+ * grad_weights exactly once per sample of every ray, and nothing else.  No gradient to t or target.  No atomics: equal
+ * inputs give equal bits.                                                                                             */
+int cnc_depth_loss_forward(const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t row_len,
+                           const float* t_starts, const float* t_ends, const float* weights,
+                           const float* target /* [n_rays] */, float spread, float* loss /* [n_rays] */,
+                           float* s1 /* [n_rays] */, uint32_t n_rays, void* stream);
+int cnc_depth_loss_backward(const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t row_len,
+                            const float* t_starts, const float* t_ends, const float* target, float spread,
+                            const float* s1 /* [n_rays] */, const float* grad_loss /* [n_rays] */, float* grad_weights,
+                            uint32_t n_rays, void* stream);
+/* cnc_depth_fetch: the measured distance along each ray of a batch, behind cnc_camera_rays on the same stream.
+ * planes f32 [n_cams, height, width]; cam_ids, px, py i64 [n], each clamped into its range as cnc_camera_rays clamps them;
+ * viewdirs f32 [n, 3], the unit directions that call produced; cams its camera table.  z = planes[cam, py, px];
+ *     euclidean != 0:  t = z                                         (cams and viewdirs are not read and may be NULL)
+ *     euclidean == 0:  c = s ((d0 R02 + d1 R12) + d2 R22), s = -1 with opengl else +1;   t = z / c
+ * (R02, R12, R22: slots 6, 10, 14 of the camera row — the optical axis in world space).  depth[i] = t, or +0 where z is
+ * not finite, z <= 0, or c <= 0 (a ray at or past 90 degrees from the axis): no measurement.                          */
+int cnc_depth_fetch(const float* planes, const float* cams, int32_t n_cams, int32_t height, int32_t width, int32_t opengl,
+                    int32_t euclidean, const int64_t* cam_ids, const int64_t* px, const int64_t* py, const float* viewdirs,
+                    int64_t n, float* depth, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * (ABI v33, added entries: no signature changed) Cameras (csrc/camera.hip)  —  replace
  * opencv_lens_undistortion / opencv_lens_undistortion_fisheye of nerfacc/cuda/csrc/camera.cu:114-183; the pixel -> ray
