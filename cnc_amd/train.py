@@ -183,24 +183,15 @@ def make_config_and_data(args, device, rank=0, world=1):
               log2_hashmap_size=args.log2_hashmap_size, log2_hashmap_size_2D=args.log2_hashmap_size_2D,
               sample_num=args.sample_num, max_context_layer_num=args.max_context_layer_num,
               n_features=args.n_features, max_steps=args.max_steps, image_size=args.image_size, seed=args.seed,
-              out_dir=args.out_dir or f"./bitstreams/{scene}", reproducible=bool(getattr(args, "reproducible", False)),
-              guarded_step=bool(getattr(args, "guarded_step", False)),
-              device_coder=bool(getattr(args, "device_coder", False)),
-              occupancy_coder=getattr(args, "occupancy_coder", "iid"),
-              mlp_coder=getattr(args, "mlp_coder", "packed"),
-              distortion_weight=float(getattr(args, "distortion_weight", 0.0)),
-              depth_weight=float(getattr(args, "depth_weight", 0.0)), depth_spread=float(getattr(args, "depth_spread", 1.0)),
-              save_mesh=getattr(args, "save_mesh", None), mesh_resolution=int(getattr(args, "mesh_resolution", 256)),
-              mesh_threshold=getattr(args, "mesh_threshold", None),
-              pose_lr=float(getattr(args, "refine_poses", 0.0)), pose_refine_from=int(getattr(args, "refine_poses_from", 0)),
-              exposure_lr=float(getattr(args, "refine_exposure", 0.0)),
-              exposure_from=int(getattr(args, "refine_exposure_from", 0)),
-              error_map=bool(getattr(args, "error_map_sampling", False)),
-              error_map_resolution=int(getattr(args, "error_map_resolution", 16)),
-              background=getattr(args, "background", "solid"), envmap_resolution=int(getattr(args, "envmap_resolution", 16)),
-              envmap_lr=float(getattr(args, "envmap_lr", 1e-2)),
-              prune_floaters=int(getattr(args, "prune_floaters", 0)),
-              prune_connectivity=int(getattr(args, "prune_connectivity", 26)),
+              out_dir=args.out_dir or f"./bitstreams/{scene}", reproducible=args.reproducible, guarded_step=args.guarded_step,
+              device_coder=args.device_coder, occupancy_coder=args.occupancy_coder, mlp_coder=args.mlp_coder,
+              distortion_weight=args.distortion_weight, depth_weight=args.depth_weight, depth_spread=args.depth_spread,
+              save_mesh=args.save_mesh, mesh_resolution=args.mesh_resolution, mesh_threshold=args.mesh_threshold,
+              pose_lr=args.refine_poses, pose_refine_from=args.refine_poses_from, exposure_lr=args.refine_exposure,
+              exposure_from=args.refine_exposure_from, error_map=args.error_map_sampling,
+              error_map_resolution=args.error_map_resolution, background=args.background,
+              envmap_resolution=args.envmap_resolution, envmap_lr=args.envmap_lr, prune_floaters=args.prune_floaters,
+              prune_connectivity=args.prune_connectivity,
               weight_decay=2e-5 if scene == "drums" else 2e-6)           # train:170-172
     if args.max_steps != 20000:      # the milestones of a shortened run keep their relative positions
         f = args.max_steps / 20000.0

@@ -17,7 +17,7 @@ import math
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from . import _gradsink, _repro, _step_guard, _table_adam
 from . import dist as cdist
 from .context import CNC_context_models
-from .datasets import LoaderDataset, SyntheticBallDataset  # noqa: F401  (re-exported: bench.py and the tests import them from here)
+from .datasets import LoaderDataset, SyntheticBallDataset, TransformsLoader  # noqa: F401  (re-exported: bench.py and the tests import them from here)
 from .field import NGPRadianceField_mygrid_2D3D
 from .nerfacc import OccGridEstimator
 from .render import Rays, render_image_with_occgrid, render_image_with_occgrid_test, set_random_seed
@@ -95,7 +95,7 @@ class TrainConfig:
     mlp_coder: str = "packed"
     # the distortion regulariser (cnc_amd.nerfacc.losses.distortion): the ray loss becomes mse + this weight
     # times the mean over the batch's rays of mip-NeRF 360's interval-distortion loss on the rendered samples.  0 = off: the
-    # step makes exactly the calls it makes without it
+    # step makes exactly the calls it makes without it.  Read once, when the Trainer is built
     distortion_weight: float = 0.0
     # mesh export (cnc_amd.mesh): `python -m cnc_amd.train --save-mesh PATH` writes the trained scene's
     # iso-surface as a PLY at the very end of the run.  None = off: the run and its results line are what they were.
@@ -251,6 +251,34 @@ def _dataset_has_alpha(dataset) -> bool:
     return False
 
 
+# The ray-side options' records: one per option that is on, which the step's phases loop over instead of
+# naming an option each.  Their order: the loss terms as the ray loss adds them, the learned parameters as the update steps them
+_RECORD_ORDER = ("distortion", "depth", "pose", "exposure", "envmap")
+
+
+@dataclass
+class LossTerm:
+    """One more term of the ray loss: `weight` times the mean over the batch's rays of `per_ray(extra, data, n_rays)` on the
+    samples the render just composited.  `needs`: a batch key without which the term is off for that batch."""
+    name: str
+    weight: float
+    per_ray: Callable
+    needs: Optional[str] = None
+
+
+@dataclass
+class LearnedParam:
+    """One learned parameter with an Adam of its own.  `live`, set per step behind the backward: the ray loss reached it;
+    only a live one is scanned and stepped.  `prepare_grad(data, extra)`, behind the backward of a step that uses the
+    parameter, leaves in `param.grad` what the Adam descends along, or None; `after_step()` runs right behind `opt.step()`."""
+    name: str
+    param: Any
+    opt: Any
+    prepare_grad: Callable = lambda data, extra: None
+    after_step: Callable = lambda: None
+    live: bool = False
+
+
 class Trainer:
     def __init__(self, cfg: TrainConfig, device="cuda", dataset=None):
         """Built in dependency order: device, models and dataset, the guard's decision, optimizers, gradient sinks, the
@@ -269,21 +297,9 @@ class Trainer:
         elif on_gpu and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())     # the worker threads select it by index
         set_random_seed(c.seed)
-        background = getattr(c, "background", "solid")
-        if background not in ("solid", "envmap"):
-            raise ValueError(f"background must be 'solid' or 'envmap', got {background!r}")
-        if background == "envmap":
-            from .backends.envmap_backend import check_resolution
-            check_resolution(c.envmap_resolution)
-            if self.dp:
-                raise ValueError("the environment-map background is not built for data-parallel training (world > 1): the "
-                                 "map's gradient would need a collective of its own")
-            if not (c.envmap_lr > 0):
-                raise ValueError("the environment-map background: envmap_lr must be positive")
-        depth_weight = float(getattr(c, "depth_weight", 0.0)) or float(os.environ.get("CNC_DEPTH_WEIGHT", "0") or 0.0)
-        if depth_weight != 0 and self.dp:
-            raise ValueError("depth supervision is not built for data-parallel training (world > 1)")
-        if int(getattr(c, "prune_floaters", 0)) < 0 or getattr(c, "prune_connectivity", 26) not in (6, 14, 26):
+        # ---- the options: config + environment, looked at once; what needs no model to be refused is refused here
+        want = self._resolve_options()
+        if int(c.prune_floaters) < 0 or c.prune_connectivity not in (6, 14, 26):
             raise ValueError("floater pruning: prune_floaters must not be negative and prune_connectivity must be 6, 14 or 26")
         # ---- models and dataset
         aabb = torch.tensor(c.aabb, device=self.device)
@@ -299,17 +315,15 @@ class Trainer:
         self.dataset = dataset if dataset is not None else \
             SyntheticBallDataset(c.image_size, device=self.device, seed=c.seed + 1000 * self.rank)
         self.dataset.update_num_rays(c.init_batch_size)
-        # ---- camera pose refinement: nothing unless asked for (`enable_pose_refinement`, called behind the optimizers)
-        self.pose_refiner = self.opt_pose = self._pose_base = None
-        self._pose_from, self._pose_on = 0, False
-        # ---- per-camera exposure compensation: nothing unless asked for (`enable_exposure_compensation`, likewise)
-        self.exposure = self.opt_exposure = None
-        self._exposure_from, self._exposure_foreground = 0, False
-        # ---- error-map pixel sampling: nothing unless asked for (`enable_error_map_sampling`, likewise)
-        self.error_map = None
+        # ---- the ray-side options: nothing unless asked for.  Each one that is on adds ONE record (`LossTerm`, `LearnedParam`) to
+        # `_terms` or `_learned`, which the step's phases loop over; enabled at the end, in one block and in the lists' order
+        self._terms, self._learned, self._log_fields = [], [], {}
+        self.pose_refiner = self._pose_base = self.exposure = self.envmap = self.error_map = self.on_depth_loss = None
+        self.opt_pose = self.opt_exposure = self.opt_env = None
+        self._pose_from, self._pose_on, self._exposure_from, self._exposure_foreground, self._depth_weight = 0, False, 0, False, 0.0
         # ---- the guarded step's decision, taken here and nowhere else: `_make_optimizers` builds the verdict's buffer from
         # it, the gradient bucket sizes its tail from it
-        self._guarded = bool(getattr(c, "guarded_step", False)) or os.environ.get("CNC_GUARDED_STEP", "0") == "1"
+        self._guarded = want["guarded"]
         # The reproducible mode fixes what is not a kernel by taking the schedule that has nothing to fix: the entropy pass
         # on the main stream from the main thread, behind the render forward (one order of random draws on the default
         # generator, ONE backward call whose engine adds the gradient pieces in the graph's order), no captured graph.
@@ -318,10 +332,6 @@ class Trainer:
         # gradients add into ONE buffer per parameter and pass instead of a fresh zero-filled tensor per call
         # (CNC_GRAD_SINK=0: off)
         self._make_optimizers()
-        # ---- the learned background: nothing unless asked for
-        self.envmap = self.opt_env = None
-        if background == "envmap":
-            self._enable_envmap()
         self.loss_scale = 2.0 ** 10          # GradScaler(2**10), never unscaled (train:211,361-362)
         self._make_sinks()
         # ---- the planes' half of the entropy pass as one captured graph per refresh interval (CNC_PLANES_GRAPH=0: op by op)
@@ -381,22 +391,62 @@ class Trainer:
             self._ctx_rand = None
             self.context.rand_like = synced_rand_like
         self._check_table_adam()
-        pose_lr = float(getattr(c, "pose_lr", 0.0)) or float(os.environ.get("CNC_POSE_LR", "0") or 0.0)
-        if pose_lr > 0:
-            self.enable_pose_refinement(pose_lr, int(getattr(c, "pose_refine_from", 0)))
-        exposure_lr = float(getattr(c, "exposure_lr", 0.0)) or float(os.environ.get("CNC_EXPOSURE_LR", "0") or 0.0)
-        if exposure_lr != 0:
-            self.enable_exposure_compensation(exposure_lr, int(getattr(c, "exposure_from", 0)))
-        if bool(getattr(c, "error_map", False)) or os.environ.get("CNC_ERROR_MAP", "0") == "1":
-            self.enable_error_map_sampling(int(getattr(c, "error_map_resolution", 16)),
-                                           float(getattr(c, "error_map_uniform_floor", 0.5)),
-                                           float(getattr(c, "error_map_decay", 0.9)),
-                                           int(getattr(c, "error_map_refresh_every", 16)))
-        # ---- depth supervision: nothing unless asked for
-        self._depth_weight = 0.0
-        self.on_depth_loss = None
+        # ---- the ray-side options that are on (nothing above looks at them, none of them draws a random number)
+        if c.distortion_weight > 0:
+            self._add(self._terms, LossTerm("distortion", float(c.distortion_weight), self._distortion_per_ray))
+        if c.background == "envmap":
+            self._enable_envmap()
+        if want["pose_lr"] > 0:
+            self.enable_pose_refinement(want["pose_lr"], int(c.pose_refine_from))
+        if want["exposure_lr"] != 0:
+            self.enable_exposure_compensation(want["exposure_lr"], int(c.exposure_from))
+        if want["error_map"]:
+            self.enable_error_map_sampling(c.error_map_resolution, c.error_map_uniform_floor, c.error_map_decay,
+                                           c.error_map_refresh_every)
+        if want["depth_weight"] != 0:
+            self.enable_depth_supervision(want["depth_weight"])
+
+    # -------------------------------------------------------------------------------- the ray-side options
+    def _resolve_options(self) -> dict:
+        """`cfg` + the environment's overrides, each looked at once (a float option: the config's value unless it is 0, then
+        the environment's), and what can be refused before a model is built, refused."""
+        c, env = self.cfg, os.environ.get
+        if c.background not in ("solid", "envmap"):
+            raise ValueError(f"background must be 'solid' or 'envmap', got {c.background!r}")
+        if c.background == "envmap":
+            from .backends.envmap_backend import check_resolution
+            check_resolution(c.envmap_resolution)
+            self._refuse_dp("the environment-map background")
+            if not (c.envmap_lr > 0):
+                raise ValueError("the environment-map background: envmap_lr must be positive")
+        depth_weight = float(c.depth_weight) or float(env("CNC_DEPTH_WEIGHT", "0") or 0.0)
         if depth_weight != 0:
-            self.enable_depth_supervision(depth_weight)
+            self._refuse_dp("depth supervision")
+        return dict(guarded=bool(c.guarded_step) or env("CNC_GUARDED_STEP", "0") == "1", depth_weight=depth_weight,
+                    pose_lr=float(c.pose_lr) or float(env("CNC_POSE_LR", "0") or 0.0),
+                    exposure_lr=float(c.exposure_lr) or float(env("CNC_EXPOSURE_LR", "0") or 0.0),
+                    error_map=bool(c.error_map) or env("CNC_ERROR_MAP", "0") == "1")
+
+    def _refuse_dp(self, option: str) -> None:
+        if self.dp:
+            raise ValueError(f"{option} is not built for data-parallel training (world > 1): it would need a collective of its own")
+
+    def _add(self, records, rec):
+        """`rec` into `records`, in place of an earlier one of its name, in `_RECORD_ORDER` whatever the order of calls."""
+        records[:] = sorted([o for o in records if o.name != rec.name] + [rec], key=lambda o: _RECORD_ORDER.index(o.name))
+
+    def _own_adam(self, param, lr: float):      # of one learned ray-side parameter: a constant rate, no weight decay
+        return torch.optim.Adam([param], lr=float(lr), eps=1e-15, weight_decay=0.0, fused=self.device.type == "cuda")
+
+    def _capture_loader(self, option: str) -> TransformsLoader:
+        """The training `TransformsLoader`; ValueError naming `option` where it is not one on the GPU, or under data parallel."""
+        loader = getattr(self.dataset, "train", None)
+        if not isinstance(self.dataset, LoaderDataset) or not isinstance(loader, TransformsLoader) \
+                or self.device.type != "cuda" or not loader.cameras.is_cuda:
+            raise ValueError(f"{option} needs a capture with per-camera images and poses on the GPU: a LoaderDataset over a "
+                             "TransformsLoader built with device=cuda (--dataset transforms)")
+        self._refuse_dp(option)
+        return loader
 
     # -------------------------------------------------------------------------------- depth supervision
     def enable_depth_supervision(self, weight: float) -> None:
@@ -404,12 +454,9 @@ class Trainer:
         ray loss gains `weight` times the batch mean of `depth_loss` on the rendered samples, with
         `cfg.depth_spread` read at every step.  `on_depth_loss`, when set, is called with (extras, target, per-ray loss)
         right after the loss is formed (diagnostics).  ValueError where that cannot work: data parallel, a weight that is
-        not positive, or a dataset that has no depth to give — anything but the procedural scene or a `LoaderDataset` over a
-        `TransformsLoader` whose frames name depth files."""
-        from .datasets import TransformsLoader
-        if self.dp:
-            raise ValueError("depth supervision is not built for data-parallel training (world > 1)")
-        if not (weight > 0) or not (float(getattr(self.cfg, "depth_spread", 1.0)) >= 0):
+        not positive, or a dataset without depth — neither the procedural scene nor a capture whose frames name depth files."""
+        self._refuse_dp("depth supervision")
+        if not (weight > 0) or not (float(self.cfg.depth_spread) >= 0):
             raise ValueError("depth supervision: depth_weight must be positive and depth_spread must not be negative")
         loader = getattr(self.dataset, "train", None)
         if isinstance(self.dataset, SyntheticBallDataset):
@@ -421,6 +468,18 @@ class Trainer:
             raise ValueError("depth supervision needs a dataset with measured depth: a LoaderDataset over a TransformsLoader "
                              "whose frames name a depth_file_path (--dataset transforms), or the procedural scene")
         self._depth_weight = float(weight)
+        self._add(self._terms, LossTerm("depth", self._depth_weight, self._depth_per_ray, needs="depth"))
+        self._log_fields["depth"] = lambda s: f" | depth={s['depth']:.3e}" if "depth" in s else ""
+
+    def _depth_per_ray(self, extra, data, num_rays: int):
+        """Every ray's depth loss on the samples the render just composited: one kernel, one more behind the backward's root."""
+        from .nerfacc.losses import depth_loss
+        per_ray = depth_loss(extra["weights"], extra["t_starts"], extra["t_ends"], data["depth"].reshape(-1).float(),
+                             ray_indices=extra["ray_indices"], n_rays=num_rays, packed_info=extra["packed_info"],
+                             spread=float(self.cfg.depth_spread))
+        if self.on_depth_loss is not None:
+            self.on_depth_loss(extra, data["depth"], per_ray)
+        return per_ray
 
     # -------------------------------------------------------------------------------- error-map pixel sampling
     def enable_error_map_sampling(self, resolution: int = 16, uniform_floor: float = 0.5, decay: float = 0.9,
@@ -432,24 +491,17 @@ class Trainer:
         the map; the statistics keep the unweighted mse.  Order of events: the map takes step s's errors right behind
         step s's loss forward, and where (s + 1) % refresh_every == 0 the CDF is rebuilt right behind that — before the
         draw for step s + 1 on either schedule (a draw on the look-ahead stream waits for the rebuild's event).
-        `uniform_floor`, `decay` and `refresh_every` have no tuned values.  ValueError where that cannot work: anything but
-        a `LoaderDataset` over a `TransformsLoader` on the GPU that batches over its images, or data parallel."""
-        from .datasets import TransformsLoader
+        `uniform_floor`, `decay` and `refresh_every` have no tuned values.  ValueError where that cannot work
+        (`_capture_loader`, or a loader that does not batch over its images)."""
         from .error_map import ErrorMapSampler
-        loader = getattr(self.dataset, "train", None)
-        if not isinstance(self.dataset, LoaderDataset) or not isinstance(loader, TransformsLoader) \
-                or self.device.type != "cuda" or not loader.cameras.is_cuda:
-            raise ValueError("error-map sampling needs a capture with per-camera images on the GPU: a LoaderDataset over a "
-                             "TransformsLoader built with device=cuda (--dataset transforms)")
-        if self.dp:
-            raise ValueError("error-map sampling is not built for data-parallel training (world > 1): the map would need a "
-                             "collective of its own")
+        loader = self._capture_loader("error-map sampling")
         if not loader.batch_over_images:
             raise ValueError("error-map sampling draws every batch over all training images: the TransformsLoader must be "
                              "built with batch_over_images=True")
         sampler = ErrorMapSampler(len(loader), loader.HEIGHT, loader.WIDTH, resolution, uniform_floor, decay, refresh_every,
                                   device=self.device)
         self.error_map = loader.sampler = sampler          # (a batch drawn ahead of this call carries no weights: plain mse)
+        self._log_fields["errmap_cover"] = lambda s: f" | errmap_cover={self.error_map.effective_fraction():.3f}"
 
     # -------------------------------------------------------------------------------- per-camera exposure compensation
     def enable_exposure_compensation(self, lr: float, start: int = 0) -> None:
@@ -457,26 +509,18 @@ class Trainer:
         (DESIGN.md §4.17): the render is made without a background, `ExposureCompensation` composites the batch's colour
         and applies the camera's gain (on the foreground only when the training images carry alpha: the loader blended the
         background in behind the photograph; with the learned background the render is complete as it is and the gain
-        covers all of it), the mse is taken against that, and an Adam of its own (fused, no weight decay, a constant rate;
-        the guarded step's verdict covers it) updates `log_gain`.  Evaluation, the mesh and the container render at gain 1.
-        ValueError where that cannot work: anything but a `LoaderDataset` over a `TransformsLoader` on the GPU, data
-        parallel, or a rate that is not positive."""
-        from .datasets import TransformsLoader
+        covers all of it), the mse is taken against that, and an Adam of its own (`_own_adam`) updates `log_gain`.  Evaluation,
+        the mesh and the container render at gain 1.  ValueError: `_capture_loader`'s, or a rate that is not positive."""
         from .exposure import ExposureCompensation
-        loader = getattr(self.dataset, "train", None)
-        if not isinstance(self.dataset, LoaderDataset) or not isinstance(loader, TransformsLoader) \
-                or self.device.type != "cuda" or not loader.cameras.is_cuda:
-            raise ValueError("exposure compensation needs a capture with per-camera images on the GPU: a LoaderDataset over a "
-                             "TransformsLoader built with device=cuda (--dataset transforms)")
-        if self.dp:
-            raise ValueError("exposure compensation is not built for data-parallel training (world > 1): the gains' gradient "
-                             "would need a collective of its own")
+        loader = self._capture_loader("exposure compensation")
         if not (lr > 0):
             raise ValueError("exposure compensation: the learning rate must be positive")
         loader.with_camera_ids = True
-        self.exposure = ExposureCompensation(len(loader), self.device)
-        self.opt_exposure = torch.optim.Adam([self.exposure.log_gain], lr=float(lr), eps=1e-15, weight_decay=0.0, fused=True)
+        self.exposure = ex = ExposureCompensation(len(loader), self.device)
         self._exposure_from, self._exposure_foreground = int(start), _dataset_has_alpha(self.dataset)
+        self.opt_exposure = self._own_adam(ex.log_gain, lr)
+        self._add(self._learned, LearnedParam("exposure", ex.log_gain, self.opt_exposure, self._exposure_gradient))
+        self._log_fields["mean_abs_log_gain"] = lambda s: f" | mean_abs_log_gain={self.exposure.mean_magnitude():.3e}"
 
     def write_exposures(self, path: Optional[str] = None) -> str:
         """Every training frame's effective log-gain and gain, to `<out_dir>/exposures.json` (or `path`)."""
@@ -489,21 +533,12 @@ class Trainer:
     def enable_pose_refinement(self, lr: float, start: int = 0) -> None:
         """From step `start` on, every step also learns one (omega, tau) per training camera at rate `lr` (DESIGN.md
         §4.14): the render pass hands back dL/dx per sample, `CameraPoseRefiner.accumulate` folds it per camera, an Adam of
-        its own (fused, no weight decay; the guarded step's verdict covers it) updates `delta`, and
-        cnc_camera_pose_apply rewrites the loader's camera table from a copy of the file's.  ValueError where that cannot
-        work: anything but a `LoaderDataset` over a `TransformsLoader` on the GPU, data parallel, an unbounded field, or a
-        model outside the fused training path's shapes (the only path with position gradients)."""
-        from .datasets import TransformsLoader
+        its own (`_own_adam`) updates `delta`, and cnc_camera_pose_apply rewrites the loader's camera table from a copy of
+        the file's.  ValueError: `_capture_loader`'s, an unbounded field, or a model outside the fused training path's
+        shapes (the only path with position gradients)."""
         from .field import FusedFieldForward
         from .poses import CameraPoseRefiner
-        loader = getattr(self.dataset, "train", None)
-        if not isinstance(self.dataset, LoaderDataset) or not isinstance(loader, TransformsLoader) \
-                or self.device.type != "cuda" or not loader.cameras.is_cuda:
-            raise ValueError("pose refinement needs a capture with per-camera poses on the GPU: a LoaderDataset over a "
-                             "TransformsLoader built with device=cuda (--dataset transforms)")
-        if self.dp:
-            raise ValueError("pose refinement is not built for data-parallel training (world > 1): the pose gradient would "
-                             "need a collective of its own")
+        loader = self._capture_loader("pose refinement")
         if self.field.unbounded:
             raise ValueError("pose refinement needs a bounded field: position gradients are not built for the contraction")
         if not (lr > 0):
@@ -517,50 +552,45 @@ class Trainer:
         loader.with_camera_ids = True
         self.pose_refiner = CameraPoseRefiner(len(loader), self.device)
         self._pose_base = loader.cameras.clone()
-        self.opt_pose = torch.optim.Adam([self.pose_refiner.delta], lr=float(lr), eps=1e-15, weight_decay=0.0, fused=True)
         self._pose_from, self._pose_on = int(start), True
+        delta = self.pose_refiner.delta
+        self.opt_pose = self._own_adam(delta, lr)
+        self._add(self._learned, LearnedParam("pose", delta, self.opt_pose, self._pose_gradient, self._pose_apply))
 
     def _pose_step(self, step: int, data) -> bool:
         """Does this step refine poses?  Stops for good, with a warning, once the range guard has switched the fused
         training forward off: no other path provides position gradients."""
-        if not self._pose_on:
-            return False
-        if not self.field.fused_train:
+        if self._pose_on and not self.field.fused_train:
             import warnings
             warnings.warn("cnc_amd: pose refinement stops here: the fused training forward was switched off (fp16 range "
                           "guard) and no other path provides position gradients; the poses keep their current values")
             self._pose_on = False
-            return False
-        return step >= self._pose_from and "camera_ids" in data      # (a batch drawn before refinement was enabled has none)
+        # (a batch drawn before refinement was enabled has no camera ids)
+        return self._pose_on and step >= self._pose_from and "camera_ids" in data
 
-    def _pose_gradient(self, data, extra) -> bool:
-        """Behind the render backward: dL/dx of the samples -> `delta.grad`.  False: the ray loss reached no sample."""
+    def _pose_gradient(self, data, extra) -> None:
+        """Behind the render backward: dL/dx of the samples -> `delta.grad`, folded per camera (`accumulate` WRITES it: what
+        `_clear_grads` set to None is never added to).  None: the ray loss reached no sample."""
         g_x = extra["positions"].grad if extra is not None and extra.get("positions") is not None else None
-        if g_x is None:
-            self.pose_refiner.delta.grad = None
-            return False
-        from .render import _as_ray_list
-        rays, _ = _as_ray_list(data["rays"])
-        self.pose_refiner.accumulate(g_x, extra, rays, data["camera_ids"])
-        return True
+        self.pose_refiner.delta.grad = None
+        if g_x is not None:
+            from .render import _as_ray_list
+            self.pose_refiner.accumulate(g_x, extra, _as_ray_list(data["rays"])[0], data["camera_ids"])
 
-    def _exposure_gradient(self) -> bool:
-        """Behind the render backward: what the gains' Adam descends along.  False: the ray loss did not reach the gains.
+    def _exposure_gradient(self, data, extra) -> None:
+        """Behind the render backward: what the gains' Adam descends along (None: the ray loss did not reach the gains).
         It is the gradient with respect to the EFFECTIVE log-gains (`effective_grad`), not its centred form that autograd
         left in `log_gain.grad`: the two differ by a multiple of (1, ..., 1) per channel, the direction along which no gain
         changes, but Adam normalises per element — of the centred form it would turn the small common term into a
         full-rate step of every camera that had no ray in the batch."""
         ex = self.exposure
-        if ex.log_gain.grad is None:
-            return False
-        ex.log_gain.grad = ex.effective_grad
-        return True
+        if ex.log_gain.grad is not None:
+            ex.log_gain.grad = ex.effective_grad
 
-    def _pose_update(self) -> None:
-        """The poses' Adam step and the loader's table rewritten from the file's poses.  The look-ahead batch of the NEXT
+    def _pose_apply(self) -> None:
+        """Behind the poses' Adam step: the loader's table rewritten from the file's poses.  The look-ahead batch of the NEXT
         step has been drawn already, from the table as the step before left it: a one-step lag, the same every run — the
         rewrite waits for that draw, and the draw after it is ordered behind this step's kernels."""
-        self.opt_pose.step()
         if self._next_ready is not None:
             torch.cuda.current_stream(self.device).wait_event(self._next_ready)
         self.pose_refiner.apply(self._pose_base, out=self.dataset.train.cameras)
@@ -580,9 +610,9 @@ class Trainer:
         opaque captures; with RGBA images the loader still blends its pixels with its own background colour."""
         from .envmap import EnvMapBackground
         c = self.cfg
-        self.envmap = EnvMapBackground(c.envmap_resolution, device=self.device)
-        self.opt_env = torch.optim.Adam([self.envmap.texture], lr=float(c.envmap_lr), eps=1e-15, weight_decay=0.0,
-                                        fused=self.device.type == "cuda")
+        self.envmap = env = EnvMapBackground(c.envmap_resolution, device=self.device)
+        self.opt_env = self._own_adam(env.texture, c.envmap_lr)      # (`clamp_`: to what the container's uint8 section holds)
+        self._add(self._learned, LearnedParam("envmap", env.texture, self.opt_env, after_step=env.clamp_))
         if _dataset_has_alpha(self.dataset):
             import warnings
             warnings.warn("cnc_amd: background='envmap' with training images that carry alpha below 1: the loader still "
@@ -919,10 +949,8 @@ class Trainer:
         if bucket is None:
             self.opt.zero_grad(set_to_none=True)
             self.opt2.zero_grad(set_to_none=True)
-            if self.opt_env is not None:
-                self.opt_env.zero_grad(set_to_none=True)
-            if self.opt_exposure is not None:
-                self.opt_exposure.zero_grad(set_to_none=True)
+            for rec in self._learned:       # every one: none of their gradients is read before this step's backward or
+                rec.opt.zero_grad(set_to_none=True)                    # `prepare_grad` has written it anew
         else:
             bucket.zero()
             bucket.bind(force=True)
@@ -998,39 +1026,12 @@ class Trainer:
         self.bucket.tail[:1].fill_(float(n_samples))    # enqueued before the backward; the bucket is zeroed before this
 
     def _render_and_update(self, step, want_stats, data, ctx_future, tables_fused):
-        """Render forward and loss, backward and gradient assembly, verdict, update, stats."""
-        c = self.cfg
-        rays, pixels, bkgd = data["rays"], data["pixels"], data["color_bkgd"]
+        """The step behind its fork: render forward, ray loss, backward, the ray-side gradients, verdict, update, stats."""
+        c, num_rays = self.cfg, len(data["pixels"])
         refine = self._pose_step(step, data)
-        # exposure compensation composites the batch's colour itself, behind this render (a batch drawn before it was
-        # enabled has no camera ids)
         gained = self.exposure is not None and step >= self._exposure_from and "camera_ids" in data
-        if gained and self.envmap is None:
-            bkgd = None
-        # depth supervision reads the samples' weights (a batch drawn before it was enabled has no depth)
-        depth_on = self._depth_weight > 0 and "depth" in data
-        # (`background=`: the learned background, when there is one, takes the place of the batch's colour; None = as ever)
-        with _gradsink.activate(self.sink_render):
-            if refine:
-                rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
-                    self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
-                    render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
-                    position_grad=True, background=self.envmap)
-            else:
-                rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
-                    self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
-                    render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
-                    with_samples=c.distortion_weight > 0 or depth_on, background=self.envmap)
-        self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event()
-        # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
-        # fused one is asked before the poll below can switch it off)
-        sg, ff = self.step_guard, self.field._field_fused
-        guard_live = sg is not None and bool(ff) and self.field.fused_train \
-            and ff._buffers is not None and getattr(ff, "_train_calls", False)
-        # the fused training forward's fp16 range guard, every step and without a wait: the words of the step before have
-        # arrived by now (the sampler has synchronised the host since), this step's are sent on their way
-        self.field.poll_range_guard()
-        self.field.snapshot_range_guard()
+        terms = [t for t in self._terms if t.needs is None or t.needs in data]     # the extra loss terms of this batch
+        rgb, acc, n_samples, extra, range_guard = self._render_forward(data, refine, gained, with_samples=bool(terms))
         if not self.dp:
             if n_samples == 0:
                 if ctx_future is not None:
@@ -1039,9 +1040,54 @@ class Trainer:
                     self._error_map_step(step, data, None)      # nothing to observe; a rebuild that is due is still made
                 return None
             if c.target_sample_batch_size > 0:
-                self.dataset.update_num_rays(int(len(pixels) * (c.target_sample_batch_size / float(n_samples))))
+                self.dataset.update_num_rays(int(num_rays * (c.target_sample_batch_size / float(n_samples))))
         # world > 1: no rank leaves the step (the collective below must be entered by everyone; a rank without samples
         # adds a zero ray gradient), and the ray budget follows the all-reduced count of the step before
+        ray_loss, scalars = self._ray_loss(step, data, rgb, acc, extra, terms, gained)
+        if self.bucket is None:
+            bpp, mb, table_pieces = self._backward_single(step, ray_loss, ctx_future, tables_fused)
+        else:
+            bpp, mb, table_pieces = self._backward_dp(step, ray_loss, ctx_future, tables_fused, num_rays, n_samples, range_guard)
+        for rec in self._learned:           # live: the ray loss reached the parameter (`_clear_grads` cleared every one)
+            if {"pose": refine, "exposure": gained}.get(rec.name, True):
+                rec.prepare_grad(data, extra)
+            rec.live = rec.param.grad is not None
+        if self.step_guard is not None:
+            self._verdict([scalars["mse"], bpp] + [scalars[t.name] for t in terms], range_guard, tables_fused)
+        self._update(step, table_pieces, tables_fused)
+        if not want_stats:
+            return {"n_rendering_samples": n_samples, "num_rays": num_rays}
+        return self._stats(scalars, bpp, mb, n_samples, num_rays)
+
+    def _render_forward(self, data, refine: bool, gained: bool, with_samples: bool):
+        """The render forward -> (rgb, opacity, sample count, extras, the range guard's words for the verdict or None)."""
+        c, rays, bkgd = self.cfg, data["rays"], data["color_bkgd"]
+        # exposure compensation composites the batch's colour itself, behind this render
+        if gained and self.envmap is None:
+            bkgd = None
+        # (`background=`: the learned background, when there is one, takes the place of the batch's colour; None = as ever)
+        own = dict(position_grad=True) if refine else dict(with_samples=with_samples)
+        with _gradsink.activate(self.sink_render):
+            rgb, acc, depth, n_samples, extra = render_image_with_occgrid(
+                self.field, self.estimator, rays, near_plane=c.near_plane, render_step_size=c.render_step_size,
+                render_bkgd=bkgd, cone_angle=c.cone_angle, alpha_thre=c.alpha_thre, return_extra=True,
+                background=self.envmap, **own)
+        self._fwd_enqueued = torch.cuda.current_stream(self.device).record_event()
+        # (the guarded step judges THIS forward's guard words on the device: whether the forward just enqueued was the
+        # fused one is asked before the poll below can switch it off)
+        ff = self.field._field_fused
+        guard_live = self.step_guard is not None and bool(ff) and self.field.fused_train \
+            and ff._buffers is not None and getattr(ff, "_train_calls", False)
+        # the fused training forward's fp16 range guard, every step and without a wait: the words of the step before have
+        # arrived by now (the sampler has synchronised the host since), this step's are sent on their way
+        self.field.poll_range_guard()
+        self.field.snapshot_range_guard()
+        range_guard = (ff._buffers["guard"], self.field._guard_seen, ff._pack_id) if guard_live else None
+        return rgb, acc, n_samples, extra, range_guard
+
+    def _ray_loss(self, step, data, rgb, acc, extra, terms, gained: bool):
+        """gain -> weighted or plain mse -> `terms`.  -> (what is back-propagated, the loss scalars by name: "mse", the terms)."""
+        pixels = data["pixels"]
         if gained:
             # the pixel the loss sees: the camera's gain on the render — the learned background's output is complete as it
             # is; otherwise the batch's colour goes in here, under the gain or behind it (`enable_exposure_compensation`)
@@ -1055,59 +1101,26 @@ class Trainer:
             # the uniform draw's; the per-ray errors go into the map, and their mean — the unweighted mse — keeps feeding
             # the statistics (and the verdict), so that a logged PSNR means what it meant
             from .error_map import weighted_mse
-            ray_mse, err = weighted_mse(rgb, pixels, data["ray_weight"])
+            ray_loss, err = weighted_mse(rgb, pixels, data["ray_weight"])
             mse = err.mean()
             self._error_map_step(step, data, err)
         else:
-            ray_mse = mse = F.mse_loss(rgb, pixels)
-        # what is back-propagated wherever the mse was: the mse alone, or + the distortion regulariser (this rank's mean over
-        # its rays, like the mse; rays without samples count as 0; not weighted by the error map).  The mse itself keeps
-        # feeding the statistics
-        ray_loss, distortion = ray_mse, None
-        if c.distortion_weight > 0:
-            distortion = self._distortion(extra, len(pixels))
-            ray_loss = ray_mse + c.distortion_weight * distortion
-        # ... + the depth term, by the same conventions (rays without a measurement count as 0 too)
-        depth_term = None
-        if depth_on:
-            depth_term = self._depth_loss(extra, data["depth"], len(pixels))
-            ray_loss = ray_loss + self._depth_weight * depth_term
-        range_guard = (ff._buffers["guard"], self.field._guard_seen, ff._pack_id) if guard_live else None
-        if self.bucket is None:
-            bpp, mb, table_pieces = self._backward_single(step, ray_loss, ctx_future, tables_fused)
-        else:
-            bpp, mb, table_pieces = self._backward_dp(step, ray_loss, ctx_future, tables_fused, len(pixels), n_samples, range_guard)
-        if refine:
-            refine = self._pose_gradient(data, extra)
-        if gained:
-            gained = self._exposure_gradient()
-        if sg is not None:
-            self._verdict(mse, bpp, range_guard, tables_fused, distortion, pose=refine, exposure=gained, depth=depth_term)
-        self._update(step, table_pieces, tables_fused)
-        if refine:
-            self._pose_update()
-        if gained:
-            self.opt_exposure.step()
-        if self.envmap is not None and self.envmap.texture.grad is not None:
-            self.opt_env.step()
-            self.envmap.clamp_()            # what the container's uint8 section can hold
-        if not want_stats:
-            return {"n_rendering_samples": n_samples, "num_rays": len(pixels)}
-        # the step's scalars in one device->host copy
-        scalars = [mse.detach(), torch.as_tensor(bpp, device=mse.device).detach().float(),
-                   torch.as_tensor(mb, device=mse.device).detach().float()]
-        if distortion is not None:
-            scalars.append(distortion.detach())
-        if depth_term is not None:
-            scalars.append(depth_term.detach())
-        mse_f, bpp_f, mb_f, *dist_f = torch.stack(scalars).tolist()
-        stats = {"mse": mse_f, "psnr": -10.0 * math.log10(max(mse_f, 1e-12)), "bpp": bpp_f,
-                 "embed_bits_MB": mb_f, "n_rendering_samples": n_samples, "num_rays": len(pixels)}
-        if distortion is not None:
-            stats["distortion"] = dist_f[0]
-        if depth_term is not None:
-            stats["depth"] = dist_f[-1]
-        return stats
+            ray_loss = mse = F.mse_loss(rgb, pixels)
+        # + weight times each term's mean over this rank's rays, like the mse (`LossTerm`)
+        scalars = {"mse": mse}
+        for t in terms:
+            scalars[t.name] = t.per_ray(extra, data, len(pixels)).sum() / float(max(len(pixels), 1))
+            ray_loss = ray_loss + t.weight * scalars[t.name]
+        return ray_loss, scalars
+
+    def _stats(self, scalars, bpp, mb, n_samples, num_rays):
+        """The step's scalars in one device->host copy -> the result dict: the fixed keys, then one per loss term."""
+        mse, names = scalars["mse"], [n for n in scalars if n != "mse"]
+        mse_f, bpp_f, mb_f, *rest = torch.stack([mse.detach(), torch.as_tensor(bpp, device=mse.device).detach().float(),
+                                                 torch.as_tensor(mb, device=mse.device).detach().float()]
+                                                + [scalars[n].detach() for n in names]).tolist()
+        return {"mse": mse_f, "psnr": -10.0 * math.log10(max(mse_f, 1e-12)), "bpp": bpp_f, "embed_bits_MB": mb_f,
+                "n_rendering_samples": n_samples, "num_rays": num_rays, **dict(zip(names, rest))}
 
     def _error_map_step(self, step: int, data, err) -> None:
         """Step `step`'s share of the error map, on the main stream right behind the loss forward: its rays' errors into the
@@ -1122,24 +1135,16 @@ class Trainer:
             em.refresh()
 
     @staticmethod
-    def _distortion(extra, num_rays: int):
-        """Mean over the batch's rays of the distortion loss on the samples the render just composited (`with_samples`
-        extras): one kernel, and one more behind the render backward's root."""
+    def _distortion_per_ray(extra, data, num_rays: int):
+        """Every ray's distortion loss on the samples the render just composited: one kernel, one more behind the backward."""
         from .nerfacc.losses import distortion
-        per_ray = distortion(extra["weights"], extra["t_starts"], extra["t_ends"], ray_indices=extra["ray_indices"],
-                             n_rays=num_rays, packed_info=extra["packed_info"])
-        return per_ray.sum() / float(max(num_rays, 1))
+        return distortion(extra["weights"], extra["t_starts"], extra["t_ends"], ray_indices=extra["ray_indices"],
+                          n_rays=num_rays, packed_info=extra["packed_info"])
 
-    def _depth_loss(self, extra, target, num_rays: int):
-        """Mean over the batch's rays of the depth loss on the samples the render just composited: one kernel, and one more
-        behind the render backward's root."""
-        from .nerfacc.losses import depth_loss
-        per_ray = depth_loss(extra["weights"], extra["t_starts"], extra["t_ends"], target.reshape(-1).float(),
-                             ray_indices=extra["ray_indices"], n_rays=num_rays, packed_info=extra["packed_info"],
-                             spread=float(self.cfg.depth_spread))
-        if self.on_depth_loss is not None:
-            self.on_depth_loss(extra, target, per_ray)
-        return per_ray.sum() / float(max(num_rays, 1))
+    @staticmethod
+    def _distortion(extra, num_rays: int):
+        """Its mean over the batch's rays (`with_samples` extras)."""
+        return Trainer._distortion_per_ray(extra, None, num_rays).sum() / float(max(num_rays, 1))
 
     def _backward_single(self, step, ray_loss, ctx_future, tables_fused):
         """Single process: both backward passes in this step's schedule -> (bits per parameter, MB, the tables' pieces)."""
@@ -1238,39 +1243,31 @@ class Trainer:
         A.bind(force=True)
         return bpp, mb, table_pieces
 
-    def _verdict(self, mse, bpp, range_guard, tables_fused, distortion=None, pose=False, exposure=False, depth=None) -> None:
-        """The guarded step's verdict, on the device and before any update."""
-        # Scanned: every gradient the two library optimizers will read (the tables' pieces are not: DESIGN.md §13) and the
-        # loss scalars; data parallel: what every rank holds alike — the bucket's summed non-table runs with the entropy
-        # gradient added, and the all-reduced guard slot.
+    def _verdict(self, losses, range_guard, tables_fused) -> None:
+        """The guarded step's verdict, on the device and before any update.  `losses`: the step's loss scalars."""
+        # Scanned: every gradient the two library optimizers will read (the tables' pieces are not: DESIGN.md §13), the
+        # loss scalars, and the gradient of every live ray-side parameter, whose Adam takes the same word; data parallel:
+        # what every rank holds alike — the bucket's summed non-table runs with the entropy gradient added, and the
+        # all-reduced guard slot.
         sg, A = self.step_guard, self.bucket
+        live = [rec for rec in self._learned if rec.live]
         if A is None:
             scan = [p.grad for o in (self.opt, self.opt2) for g in o.param_groups for p in g["params"]
                     if p.grad is not None and id(p) not in self._table_ids]
-            scan += [t.detach().reshape(-1) for t in (mse, bpp, distortion, depth)
-                     if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
-            if pose:                            # the pose gradient joins the scan, the poses' Adam takes the same word
-                scan.append(self.pose_refiner.delta.grad.reshape(-1))
-            if self.envmap is not None and self.envmap.texture.grad is not None:       # ... and so does the background's
-                scan.append(self.envmap.texture.grad.reshape(-1))
-            if exposure:                        # ... and the gains'
-                scan.append(self.exposure.log_gain.grad.reshape(-1))
+            scan += [t.detach().reshape(-1) for t in losses if isinstance(t, torch.Tensor) and t.dtype == torch.float32]
+            scan += [rec.param.grad.reshape(-1) for rec in live]
             sg.scan(scan, range_guard=range_guard)
         else:
             sg.scan([A.flat[lo:hi] for lo, hi in A.runs_excluding(self._tables)] + [A.tail[1:2]])
         grp = self.opt.param_groups[1]
         sg.seal(grp["lr"], grp["eps"], grp["weight_decay"], self.table_adam.clip_counters() if tables_fused else ())
         self.opt.found_inf = self.opt2.found_inf = sg.found_inf
-        if pose:
-            self.opt_pose.found_inf = sg.found_inf
-        if self.opt_env is not None:
-            self.opt_env.found_inf = sg.found_inf
-        if exposure:
-            self.opt_exposure.found_inf = sg.found_inf
+        for rec in self._learned:
+            rec.opt.found_inf = sg.found_inf
         sg.poll()
 
     def _update(self, step, table_pieces, tables_fused) -> None:
-        """Both optimizers (the tables through their kernel when `tables_fused`), the schedules, the replicas' resync."""
+        """Both optimizers (the tables through their kernel when `tables_fused`), the schedules, the resync, the ray-side Adams."""
         c = self.cfg
         if tables_fused:
             # leaves the tables' `.grad` None: the library's step skips them.  Data parallel: `.grad` is the bucket's view
@@ -1295,6 +1292,10 @@ class Trainer:
             self.resync["fired"] += 1 if n else 0
             self.resync["tensors"] += n
             self.resync["bytes"] += nbytes
+        for rec in self._learned:           # the ray-side parameters the loss reached: each one's Adam and what follows it
+            if rec.live:
+                rec.opt.step()
+                rec.after_step()
 
     def train(self, steps: Optional[int] = None, log=print):
         steps = self.cfg.max_steps if steps is None else steps
@@ -1310,9 +1311,8 @@ class Trainer:
                     f"n_rendering_samples={s['n_rendering_samples']} | num_rays={s['num_rays']} | "
                     f"bits_per_param={s['bpp']:.3f} | embed_bits_MB={s['embed_bits_MB']:.3f}"
                     + (f" | skipped={self.step_guard.stats()['skipped']}" if self.step_guard is not None else "")
-                    + (f" | depth={s['depth']:.3e}" if "depth" in s else "")
-                    + (f" | mean_abs_log_gain={self.exposure.mean_magnitude():.3e}" if self.exposure is not None else "")
-                    + (f" | errmap_cover={self.error_map.effective_fraction():.3f}" if self.error_map is not None else ""))
+                    + "".join(self._log_fields[k](s) for k in ("depth", "mean_abs_log_gain", "errmap_cover")
+                              if k in self._log_fields))
         if self.exposure is not None and self.rank == 0:
             path = self.write_exposures()
             if log:
@@ -1348,8 +1348,8 @@ class Trainer:
         reads the grid afterwards — the evaluations, the codec, `save_container`, the mesh — sees the pruned one.  A thin
         detached part of the scene can be a small component too: compare `evaluate()` before and after.  `min_cells` has no
         tuned value.  -> {components, cells, removed_components, removed_cells}."""
-        min_cells = int(getattr(self.cfg, "prune_floaters", 0) if min_cells is None else min_cells)
-        connectivity = int(getattr(self.cfg, "prune_connectivity", 26) if connectivity is None else connectivity)
+        min_cells = int(self.cfg.prune_floaters if min_cells is None else min_cells)
+        connectivity = int(self.cfg.prune_connectivity if connectivity is None else connectivity)
         return self.estimator.prune_small_components(min_cells, connectivity)
 
     # ------------------------------------------------------------------------------ codec
@@ -1372,13 +1372,13 @@ class Trainer:
 
     def coder_name(self) -> str:
         """"device" when this Trainer codes with the device coder (TrainConfig.device_coder or CNC_DEVICE_CODER=1)."""
-        on = bool(getattr(self.cfg, "device_coder", False)) or os.environ.get("CNC_DEVICE_CODER", "0") == "1"
+        on = bool(self.cfg.device_coder) or os.environ.get("CNC_DEVICE_CODER", "0") == "1"
         return "device" if on else "host"
 
     def occupancy_coder_name(self) -> str:
         """"pyramid" when this Trainer's containers code the occupancy grid with the pyramid model
         (TrainConfig.occupancy_coder or CNC_OCC_CODER=pyramid), else "iid"."""
-        name = os.environ.get("CNC_OCC_CODER") or getattr(self.cfg, "occupancy_coder", "iid")
+        name = os.environ.get("CNC_OCC_CODER") or self.cfg.occupancy_coder
         if name not in ("iid", "pyramid"):
             raise ValueError(f"occupancy coder must be 'iid' or 'pyramid', got {name!r}")
         return name
@@ -1386,7 +1386,7 @@ class Trainer:
     def mlp_coder_name(self) -> str:
         """"tree" when this Trainer's containers code the MLP's indices with the bit-tree model (TrainConfig.mlp_coder or
         CNC_MLP_CODER=tree), else "packed"."""
-        name = os.environ.get("CNC_MLP_CODER") or getattr(self.cfg, "mlp_coder", "packed")
+        name = os.environ.get("CNC_MLP_CODER") or self.cfg.mlp_coder
         if name not in ("packed", "tree"):
             raise ValueError(f"mlp coder must be 'packed' or 'tree', got {name!r}")
         return name
@@ -1401,7 +1401,7 @@ class Trainer:
         return self.context.encode_binary_vxl_mixPg_3D2D(e.encoding_xyz, e.encoding_xy, e.encoding_xz,
                                                          e.encoding_yz, self.estimator.binaries,
                                                          filename_prefix=prefix, coder=coder or self.coder_name(),
-                                                         symbols_per_lane=getattr(self.cfg, "symbols_per_lane", None)) + (prefix,)
+                                                         symbols_per_lane=self.cfg.symbols_per_lane) + (prefix,)
 
     @torch.no_grad()
     def decode_into_field(self, Pgs, prefix, coder: Optional[str] = None):
@@ -1452,7 +1452,7 @@ class Trainer:
         occ, mlp = self.occupancy_coder_name(), self.mlp_coder_name()
         size = write_container(path, meta=meta, table_streams=streams, binaries=self.estimator.binaries,
                                field_mlp=self._mlp_state(), context_state=self.context.state_dict(), occupancy_coder=occ,
-                               coder=self.coder_name(), symbols_per_lane=getattr(self.cfg, "symbols_per_lane", None),
+                               coder=self.coder_name(), symbols_per_lane=self.cfg.symbols_per_lane,
                                mlp_coder=mlp, envmap=None if self.envmap is None else self.envmap.quantized())
         res = {"file_KB": size / 1024.0, "embeddings_KB": coded_MB * 1024.0, "estimate_KB": est_MB * 1024.0}
         if occ == "pyramid":       # the section as written (the Bernoulli one still, for a grid with an odd side)
